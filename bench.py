@@ -6,7 +6,13 @@ Default workload (c3, BASELINE.json configs[2], the north star's roofline config
 per-row runs -> Golomb stream AND EG stream for every plane. MPix = binary pixels =
 rows*cols*planes. N GPUs = N independent images (weak scaling, no data-path collective).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step).
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy. --full adds
+everything else: the per-kernel breakdown and the dominant kernel's roofline (event-bracketed,
+on steps of their own and inside the timed region), the predictor pass on its own, the bit-exact
+check against the CPU oracle and the CPU baselines (--no-check / --no-cpu drop those two).
 
 Multi-GPU: one rank per GPU (RCCL = backend "nccl"). Under torch.distributed.run (WORLD_SIZE set) this
 process is one rank; `bench.py --gpus N` without a launcher starts the N ranks itself, as a child
@@ -70,8 +76,17 @@ def parse():
                     help="c3 (one-call, planes NULL): images in flight -- this many contexts, each on its own HIP "
                          "stream, take successive images, so one image's emission overlaps the next one's count "
                          "pass (serving throughput; the roofline kernel is timed on the first context's launches)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-kernel timing and "
+                         "roofline, the predictor pass alone, the bit-exact check against the oracle, the CPU "
+                         "baselines (the result line's roofline, predictor_pass, kernels, bit_exact_check, "
+                         "cpu_baseline; null without --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (what the caller of the timed path "
+                         "holds) as DIR/<name>.npy, float32 / float64; large arrays as a seeded byte sample plus "
+                         "chunk sums over all their bytes")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-check", action="store_true", help="--full without the bit-exact check")
     return ap.parse_args()
 
 
@@ -210,6 +225,47 @@ def rand_words(t, shape, dev, g):
     return t.randint(0, 256, (n * 8,), dtype=t.uint8, device=dev, generator=g).view(t.int64).view(*shape)
 
 
+DUMP_WHOLE = 1 << 22   # arrays of up to this many bytes are written whole
+DUMP_SAMPLE = 1 << 20  # bytes sampled from a larger array
+DUMP_SUMS = 1 << 12    # contiguous chunks a larger array's bytes are summed over
+DUMP_LIMIT = 64 << 20  # bytes written per run, at most
+
+
+def host(t):
+    """device tensor -> numpy array, 64-bit words as uint64"""
+    a = t.detach().cpu().numpy()
+    return a.view(np.uint64) if a.dtype == np.int64 else a
+
+
+def dump_outputs(d, arrays):
+    """Write {name: integer numpy array} under d as float .npy files two builds can be compared by. An array
+    of up to DUMP_WHOLE bytes is written whole: its values as float64 where they are exact there, else its
+    bytes as float32. A larger one gives <name>_sample.npy (DUMP_SAMPLE of its bytes, at positions drawn from
+    a fixed seed: the same positions whenever the array has the same length) and <name>_sums.npy (the byte
+    sums of DUMP_SUMS contiguous chunks, every byte in one of them)."""
+    os.makedirs(d, exist_ok=True)
+    written = 0
+
+    def save(name, a):
+        nonlocal written
+        written += a.nbytes
+        if written > DUMP_LIMIT:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_LIMIT >> 20} MB of outputs at {name}")
+        np.save(os.path.join(d, name + ".npy"), a)
+
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        b = a.reshape(-1).view(np.uint8)
+        if a.nbytes <= DUMP_WHOLE:
+            exact = a.size == 0 or (int(a.max()) < 2 ** 53 and int(a.min()) > -2 ** 53)
+            save(name, a.astype(np.float64) if exact else b.astype(np.float32))
+            continue
+        idx = np.sort(np.random.default_rng(0x5EED).integers(0, b.size, DUMP_SAMPLE))
+        save(name + "_sample", b[idx].astype(np.float32))
+        edges = np.arange(DUMP_SUMS, dtype=np.int64) * b.size // DUMP_SUMS
+        save(name + "_sums", np.add.reduceat(b, edges, dtype=np.float64))
+
+
 # ------------------------------------------------------------------------------------------
 class C3:
     """gray image -> 8 bitplanes -> med -> Golomb + EG (per GPU)."""
@@ -300,6 +356,20 @@ class C3:
                 "med_count": plane_b, "golomb_bits": plane_b,
                 "golomb_emit": plane_b + g, "eg_emit": plane_b + e, "encode_rows_golomb_eg": plane_b + g + e,
                 "encode_rows_golomb_egsrc": e + g}
+
+    def outputs(self):
+        """what the last step's caller holds: per coder the planes' bit counts and the streams (each plane's
+        ceil(bits / 64) words, plane after plane), and the bitplanes where the step returns them"""
+        res = {}
+        for name, out, bits in (("golomb", self.out_g, self.bits_g), ("eg", self.out_e, self.bits_e)):
+            if out is None:
+                continue
+            B = host(bits)[:self.nplanes]
+            res[name + "_bits"] = B
+            res[name + "_stream"] = np.concatenate([host(out[k][:(int(b) + 63) // 64]) for k, b in enumerate(B)])
+        if getattr(self, "store_planes", False):
+            res["planes"] = host(self.planes)
+        return res
 
     def host_planes(self, rows):
         if self.planes is None:  # the last step's image's planes (device bitplane kernel), for the CPU leg
@@ -433,6 +503,18 @@ class C3Planes(C3):
                 got.append((packed, off))  # (no host sync in the step: the check reads the total)
         self.gathered = tuple(got)
         self.k += 1
+
+    def outputs(self):
+        """rank 0: its own planes' bit counts and, per coder, the packed streams it ends the step with (every
+        rank's, in plane order)"""
+        res = {}
+        for name, (words, offs), bits in zip(("golomb", "eg"), self.gathered, (self.bits_g, self.bits_e)):
+            total = int(host(offs)[-1]) if self.world == 1 else int(offs[-1])
+            res[name + "_bits"] = host(bits[:self.nplanes])
+            res[name + "_stream"] = host(words[:total])
+        if self.store_planes:
+            res["planes"] = host(self.planes[:self.nplanes])
+        return res
 
     def collect(self):
         """every rank's per-plane bit counts on every rank (collective, after the timed steps)"""
@@ -673,6 +755,20 @@ class C4(C3):
                 self.gathered = gather_streams(self.packed, self.word_off[-1:], self.world, self.rank)
         self.k += 1
 
+    def outputs(self):
+        """rank 0: its own frames' bit counts and word offsets, and the packed streams it ends the step with
+        (its own at N = 1, every rank's as gathered at N > 1)"""
+        res = {"golomb_bits": host(self.bits_g[:self.nplanes])}
+        if self.world == 1:
+            off = host(self.word_off)
+            res["word_off"] = off
+            res["golomb_stream"] = host(self.packed[:int(off[-1])])
+        else:
+            words, offs = self.gathered
+            res["rank_off"] = np.asarray(offs, np.uint64)
+            res["golomb_stream"] = host(words[:int(offs[-1])])
+        return res
+
     def collect(self):
         """after the timed steps (collective): every rank's per-frame bit counts and a fingerprint of
         its input frames, on every rank"""
@@ -779,6 +875,19 @@ class C5(C3):
             self.merged, self.merged_bits = sharded_golomb(enc, wts.numel(), total, c.dev, lengths=lengths)
         self.k += 1
 
+    def outputs(self):
+        """the tile weights, modes, residual and stats of this rank's band and the stream: the band's own at
+        N = 1, the merged stream of the whole plane on rank 0 at N > 1"""
+        st = host(self.res["stats"])
+        res = {k: host(self.res[k]) for k in ("weights", "w_nonpred", "w_pred", "modes", "resid")}
+        res["stats"] = st
+        if self.world == 1:
+            res["stream"] = host(self.res["stream"][:(int(st[0]) + 63) // 64])
+        else:
+            res["stream"] = host(self.merged)
+            res["stream_bits"] = np.asarray([self.merged_bits], np.uint64)
+        return res
+
     def out_bytes(self):
         if self.world > 1:
             return self.own_bits / 8.0
@@ -840,6 +949,9 @@ class C1(C3):
 
     def out_bytes(self):
         return 0.0
+
+    def outputs(self):
+        return {k: host(v).view(np.uint32) for k, v in zip(("besti", "bestj", "bestd"), self.res)}
 
     def kernel_bytes(self):
         return {}
@@ -911,6 +1023,14 @@ class C1M(C1):
     def out_bytes(self):
         st = self.pybic.as_u64(self.res["stats"])
         return (int(st[1]) + int(st[2]) + int(st[3])) / 8.0
+
+    def outputs(self):
+        st = host(self.res["stats"])
+        res = {k: host(self.res[k]).view(np.uint32) for k in ("besti", "bestj", "bestd", "weights")}
+        res.update(modes=host(self.res["modes"]), resid=host(self.resid), stats=st,
+                   stream_match=host(self.res["stream_match"][:(int(st[1]) + 63) // 64]),
+                   stream_nomatch=host(self.res["stream_nomatch"][:(int(st[2]) + 63) // 64]))
+        return res
 
     def check(self, oracle):
         exp = oracle.match_encode(self.host, self.cols, self.W, self.T, self.R, self.enuml)
@@ -1029,21 +1149,23 @@ def main():
     for _ in range(args.warmup):
         wl.step()
     ctx.sync()
-    # per-kernel breakdown (every launch bracketed by HIP events) on untimed steps: it names the
-    # dominant kernel. Event pairs drain the pipeline between launches (≈45 µs of a 0.5 ms C3
-    # step with all of them), so the timed region below brackets only the dominant kernel.
-    ctx.prof_enable(True)
-    ctx.prof_only(None)
-    for _ in range(max(args.warmup, 2)):
-        wl.step()
-    ctx.sync()
-    prof_all = ctx.prof_collect()
-    kb = wl.kernel_bytes()
-    timed = {k: v for k, v in prof_all.items() if k in kb}
-    dom = max(timed, key=lambda k: timed[k][1]) if timed else None
-    ctx.prof_only(dom)
-    if not dom:
-        ctx.prof_enable(False)
+    prof_all, dom = {}, None
+    if args.full:
+        # per-kernel breakdown (every launch bracketed by HIP events) on untimed steps: it names the
+        # dominant kernel. Event pairs drain the pipeline between launches (≈45 µs of a 0.5 ms C3
+        # step with all of them), so the timed region below brackets only the dominant kernel.
+        ctx.prof_enable(True)
+        ctx.prof_only(None)
+        for _ in range(max(args.warmup, 2)):
+            wl.step()
+        ctx.sync()
+        prof_all = ctx.prof_collect()
+        kb = wl.kernel_bytes()
+        timed = {k: v for k, v in prof_all.items() if k in kb}
+        dom = max(timed, key=lambda k: timed[k][1]) if timed else None
+        ctx.prof_only(dom)
+        if not dom:
+            ctx.prof_enable(False)
     barrier(world)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -1051,16 +1173,20 @@ def main():
     barrier(world)
     dt = time.perf_counter() - t0
     ctx.sync()
-    prof = ctx.prof_collect()
-    ctx.prof_enable(False)
-    ctx.prof_only(None)
+    prof = {}
+    if args.full:
+        prof = ctx.prof_collect()
+        ctx.prof_enable(False)
+        ctx.prof_only(None)
     dt_max = max_over_ranks(dt, world, dev)
     pixels_all = sum_over_ranks(float(wl.pixels), world, dev) * args.steps
     out_all = sum_over_ranks(wl.out_bytes(), world, dev) * args.steps
     value = pixels_all / dt_max / 1e6
-    # dominant kernel and its roofline (algorithmic bytes / its average launch time, measured with
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.outputs())
+    # --full: dominant kernel and its roofline (algorithmic bytes / its average launch time, measured with
     # HIP events inside the timed region)
-    kb = wl.kernel_bytes()
+    kb = wl.kernel_bytes() if args.full else {}
     roof = None
     per_kernel = {k: {"launches": n, "avg_us": 1e3 * ms / max(n, 1)} for k, (n, ms) in prof_all.items()}
     if dom and dom in prof:
@@ -1079,7 +1205,7 @@ def main():
                             "(k_emit_k01 / k_emit_known; k_emit_rest's ~1 % of the rows run beside it on a second "
                             "stream and their bytes are counted too); stage_avg_us: the whole stage, that second "
                             "stream's fork and join included (untimed profiled steps)")
-    pred_pass = wl.predictor_pass(max(args.steps, 5)) if hasattr(wl, "predictor_pass") and type(wl) is C3 else None
+    pred_pass = wl.predictor_pass(max(args.steps, 5)) if args.full and type(wl) is C3 else None
     if pred_pass is not None and "bitplanes_count" in per_kernel:
         # the pass that runs inside the step: bic_encode_gray's count pass (k_gray_strips: gray -> planes,
         # med residual, per-strip run statistics), gray read + planes written, alternating images
@@ -1088,14 +1214,14 @@ def main():
         pred_pass["in_step"] = {"kernel": "bitplanes_count (k_gray_strips)", "algorithmic_bytes_per_launch": b,
                                 "achieved": round(b / us / 1e3, 1), "frac": round(b / us / 1e3 / HBM_PEAK_GBS, 4),
                                 "avg_launch_us": round(us, 2)}
-    if hasattr(wl, "collect"):
+    if args.full and hasattr(wl, "collect"):
         wl.collect()
     ok = None
     cpu = None
-    if rank == 0 and not args.no_check:
+    if rank == 0 and args.full and not args.no_check:
         from oracle_lib import Oracle
         ok = bool(wl.check(Oracle()))
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu = cpu_baseline(wl, args)
     if rank == 0:
         line = {
@@ -1111,8 +1237,10 @@ def main():
                                            args.workload, f"dp{world} (independent images per GPU)")},
             "mb_per_s_out": round(out_all / dt_max / 1e6, 1),
             "gray_mpix_per_s": round(value / 8, 1) if args.workload == "c3" else None,
-            "roofline": roof, "predictor_pass": pred_pass, "kernels": per_kernel,
-            "kernels_note": "all launches event-bracketed on untimed steps; the timed region brackets only roofline.kernel",
+            "full": args.full, "roofline": roof, "predictor_pass": pred_pass,
+            "kernels": per_kernel if args.full else None,
+            "kernels_note": ("all launches event-bracketed on untimed steps; the timed region brackets only "
+                             "roofline.kernel") if args.full else None,
             "bit_exact_check": ok, "cpu_baseline": cpu,
         }
         print(json.dumps(line))

@@ -69,7 +69,8 @@ def test_bench_gpus2_spawns_ranks(workload):
     import json
     env = dict(os.environ, BIC_BENCH_BACKEND="gloo", OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *workload, "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *workload, "--steps", "2", "--warmup", "1",
+           "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
@@ -82,7 +83,7 @@ def test_bench_plane_count_one_rank():
     """--plane-count 1 at N = 1: the per-rank step of an 8-GPU plane-sharded run, bit-exact"""
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c3", "--shard", "planes", "--plane-count",
-           "1", "--rows", "512", "--cols", "4096", "--steps", "2", "--warmup", "1", "--no-cpu"]
+           "1", "--rows", "512", "--cols", "4096", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     j = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])

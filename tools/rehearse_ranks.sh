@@ -3,14 +3,15 @@
 # (BIC_BENCH_BACKEND=gloo). Times are not scaling numbers (both ranks share one device); the
 # lines show the launcher, barriers, max-over-ranks timing and the stream gathers run end to end.
 set -o pipefail
+O=${BIC_OUT_DIR:-bench_out}; mkdir -p $O  # where the logs go
 export BIC_BENCH_BACKEND=gloo MASTER_ADDR=127.0.0.1
-OUT=gpurun_out/rehearsal_2rank.jsonl
+OUT=$O/rehearsal_2rank.jsonl
 : > $OUT
 for args in "--workload c3" "--workload c3 --shard planes" "--workload c4" "--workload c5"; do
   timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29512 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu $args > gpurun_out/reh.log 2>&1 \
-    || { echo "failed: $args"; tail -20 gpurun_out/reh.log; exit 1; }
-  grep '^{' gpurun_out/reh.log | tail -1 >> $OUT
+    --master-port 29512 bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu $args > $O/reh.log 2>&1 \
+    || { echo "failed: $args"; tail -20 $O/reh.log; exit 1; }
+  grep '^{' $O/reh.log | tail -1 >> $OUT
 done
 python3 -c "
 import json
