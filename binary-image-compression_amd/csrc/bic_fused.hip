@@ -53,9 +53,9 @@ __device__ unsigned long long g_known[2][1 << 17];
     const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();                               \
     if (threadIdx.x == 0) g_stamps[(1u << 21) + (ONES ? 0u : 8192u) + blockIdx.x * 8u + (slot)] = t_; \
   } while (0)
-// the class launch's phases (tools/k01_stamps.py), 4 slots per index: per kmix row (index 1 << 18 + its
-// row id; slots 0-2: entry, loads done, stored), per wave of k_emit_k01 (index 1 << 19 + 8192 + its wave;
-// slots 0-3: entry, k = 0 rows done (rest role: kmix rows done), -, exit)
+// the class launch's phases (tools/k01_stamps.py), 4 slots per index: per k = 1 row (YSTAMP, index
+// 1 << 18 + its row id; slots 0-3: entry, words assembled, image built, stored), per wave of k_emit_k01
+// (index 1 << 19 + 8192 + its wave; slots 0-3: entry, k = 0 rows done, -, exit)
 #define XSTAMP(idx, slot)                                                                          \
   do {                                                                                             \
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                    \
@@ -91,56 +91,10 @@ constexpr int kGImg = 684;    // u32 words of Golomb row image per wave (21760 b
                               // the k = 1, 2 byte tables 4 workgroups (32 waves) fit one CU's LDS)
 constexpr int kEImg = 520;    // u32 words of EG row image per wave (cols <= 16384)
 constexpr int kPad = 4;       // zeroed words after an image's end (get64 reads ahead)
-#ifndef BIC_K1_LC
-#define BIC_K1_LC 1  // lane l holds the row's words l WPL .. (one wave scan per row, not per word group)
-#endif
-#ifndef BIC_K1_PI
-#define BIC_K1_PI 1  // k = 1 rows by the backward parity (k1_pi, the [pi][byte] table); 0: encode_word_k1b
-#endif
-#if BIC_K1_PI && !BIC_K1_LC
-#error "BIC_K1_PI needs BIC_K1_LC"
-#endif
-constexpr uint32_t kK1Table = BIC_K1_PI ? 512u : 0u;  // the k = 1 rows' table in the u32 byte tables
-#ifndef BIC_KNOWN_PI
-// k_emit_known's k = 1 rows (C4, C2, predict): 1 the backward parity, 0 encode_word_k1b (C4 0.268 ms
-// against 0.283 with the parity's strided lanes)
-#define BIC_KNOWN_PI 0
-#endif
-constexpr uint32_t kKnownTable = BIC_KNOWN_PI ? 512u : 0u;
-#ifndef BIC_SLOW_REST
-#define BIC_SLOW_REST 1  // class kernels' path: the slow rows by k_emit_rest (listed by the LEN scan), no k_rows_global
-#endif
-constexpr bool kSlowRest = BIC_SLOW_REST != 0;
-#ifndef BIC_K01_REST
-#define BIC_K01_REST 0
-#endif
-// the class kernels' path (EG source): the mixed-k and slow rows by k_emit_k01's own leading workgroups
-// (rest_role: one CU slot each, beside the persistent class waves) instead of k_emit_rest on the second
-// stream -- the emission is one launch, without the fork / join events
-constexpr bool kK01Rest = BIC_K01_REST != 0;
-#ifndef BIC_KMIX
-#define BIC_KMIX 0
-#endif
-// the class kernels' path: rows mixing k = 0 and k = 1 by kmix_rows inside k_emit_k01 (the walk's k = 1
-// masks, bic_k1pi.h kmix_*) instead of k_emit_rest's per-codeword encoder
-constexpr bool kKMixRows = BIC_KMIX != 0;
-#ifndef BIC_KNOWN_MIX
-#define BIC_KNOWN_MIX 0
-#endif
-// k_emit_known (planes in, Golomb alone: C4's path): the walked rows mixing k = 0 and k = 1 written by the
-// row's own wave from the walk's k = 1 masks (kmix_encode) instead of by k_emit_rest beside it
-constexpr bool kKnownMix = BIC_KNOWN_MIX != 0;
-#ifndef BIC_K01_RG
-#define BIC_K01_RG 0  // (A/B: the rest role's workgroups; 0: one per CU, the persistent ones one fewer per CU)
-#endif
-constexpr uint32_t kK01Rg = BIC_K01_RG;
-#ifndef BIC_K01_PRIO
-#define BIC_K01_PRIO 0
-#endif
-#ifndef BIC_K01_RLAST
-#define BIC_K01_RLAST 0
-#endif
-constexpr bool kK01Prio = BIC_K01_PRIO != 0, kK01RLast = BIC_K01_RLAST != 0;
+constexpr uint32_t kK1Table = 512u;  // the k = 1 rows' table in the u32 byte tables (k1_pi, the [pi][byte] table)
+// k_emit_known's k = 1 rows (C4, C2, predict) go by encode_word_k1b, table 0 (C4 0.268 ms against 0.283
+// with the backward parity's strided lanes)
+constexpr uint32_t kKnownTable = 0u;
 
 // One lane's codewords for one residual word.
 struct LaneEnc {
@@ -708,9 +662,7 @@ __device__ __forceinline__ void write_row(const uint32_t* img, uint64_t L, uint6
 // consumer masks them off, so the two emission launches never write glen)
 constexpr uint64_t kK0Row = 1ull << 63;  // every codeword of the row has k = 0
 constexpr uint64_t kK1Row = 1ull << 62;  // every codeword of the row has k = 1
-constexpr uint64_t kKMix = 1ull << 61;   // k = 0 and k = 1 mixed, masks stored (kmix_rows)
-constexpr uint64_t kKEol1 = 1ull << 60;  // (kKMix) the end-of-row codeword has k = 1
-constexpr uint64_t kLenMask = kKEol1 - 1;
+constexpr uint64_t kLenMask = (1ull << 60) - 1;
 
 struct FusedArgs {
   Geom g;
@@ -754,12 +706,6 @@ struct FusedArgs {
                   // keeps these loads on the scalar cache: no wait on the vector memory counter)
   uint64_t* sink;     // FusedScratch::sink
   uint32_t* walk_o;   // FusedScratch::walk_o (the walked rows' row_o)
-  uint32_t rgrid;     // k_emit_k01: its leading workgroups in the rest role (0: k_emit_rest writes those rows)
-  // class kernels' path: per walked row (walk list index < kcap) the k = 1 masks of its words (kmix_rows),
-  // and per kKMix row its walk list index
-  uint64_t* kmask;
-  uint32_t* row_wi;
-  uint32_t kcap;
 #ifdef BIC_STAMPS
   int known;
 #endif
@@ -1573,22 +1519,14 @@ __device__ __forceinline__ void plane_bases(const FusedArgs& a, uint64_t* tmp) {
 // bits_g[] the plane's total; rows past the slot's end get glen = 0 and raise the overflow flag
 // (a later chunk may then sum a zeroed length: its offsets stay inside the slot, and the call
 // reports BIC_ENOSPC with the stream undefined).
-#ifndef BIC_LEN_REV
-#define BIC_LEN_REV 0
-#endif
-constexpr bool kLenRev = BIC_LEN_REV != 0;
 constexpr uint32_t kScanPer = 1, kScanChunk = 1024 * kScanPer;  // (1024-row chunks: twice the workgroups of 2048, C3 prefix 51 -> 42 us)
 template <bool ONES, bool CLASSIFY>
 __global__ __launch_bounds__(1024) void k_scan_rows(FusedArgs a) {
   __shared__ uint64_t tmp[17];
   const Geom& g = a.g;
   const uint32_t nb = (g.rows + kScanChunk - 1) / kScanChunk;
-  // (BIC_LEN_REV, the LEN scan: chunks dealt bottom row chunk first, planes interleaved, so the class
-  // lists -- appended in about this order -- lead with the rows the count pass wrote last, the part of
-  // the EG stream the Infinity Cache may still hold when the emission reads it)
-  const bool rev = kLenRev && !ONES;
-  const uint32_t plane = rev ? blockIdx.x % g.nplanes : blockIdx.x / nb;
-  const uint32_t b = rev ? nb - 1 - blockIdx.x / g.nplanes : blockIdx.x % nb;
+  const uint32_t plane = blockIdx.x / nb;
+  const uint32_t b = blockIdx.x % nb;
   const uint64_t base = (uint64_t)plane * g.rows;
   auto val = [&](uint32_t r) -> uint64_t {
     if constexpr (ONES) {
@@ -1713,34 +1651,10 @@ __global__ __launch_bounds__(1024) void k_scan_rows(FusedArgs a) {
       // (row_global; k = 0 rows are shifted copies, no image): the list is complete before the emission
       constexpr uint32_t kCapBitsRest = (kGImg - kPad) * 32;
       const bool big = v[0] > kCapBitsRest;
-      const uint32_t c0 = ok && (f & kK0Row) ? 1u : 0u, c1 = ok && (f & kK1Row) && (!big || !kSlowRest) ? 1u : 0u;
-      if (ok && !(f & kK0Row) && big && (kSlowRest || !(f & kK1Row))) {
+      const uint32_t c0 = ok && (f & kK0Row) ? 1u : 0u, c1 = ok && (f & kK1Row) && !big ? 1u : 0u;
+      if (ok && !(f & kK0Row) && big) {
         a.gslow[base + r] = a.row_o[base + r] + r + 1;
         a.slow_ids[atomicAdd(a.slow_n, 1u)] = base + r;
-      }
-      // the mixed rows that fit an LDS image: those with the walk's k = 1 masks (kKMix) listed for kmix_rows
-      // (the class entries' third list, counter[8]), the others (a codeword with k >= 2) for k_emit_k01's
-      // rest role (rest_ids, counter[6]). ~1 % of the rows: most waves append nothing.
-      const bool cx = kK01Rest && ok && (f & kKMix) && !big;
-      const bool cm = kK01Rest && ok && !(f & (kK0Row | kK1Row | kKMix)) && !big;
-      const uint64_t mx = __ballot(cx), mm = __ballot(cm);
-      if (mx) {
-        const int leader = __builtin_ctzll(mx);
-        uint32_t wb = 0;
-        if (lane_id() == leader) wb = atomicAdd(a.counter + 8, (uint32_t)__popcll(mx));
-        wb = (uint32_t)__shfl((int)wb, leader);
-        if (cx) {
-          const uint64_t e = 2 * (uint64_t)g.rows * g.nplanes + wb + (uint32_t)__popcll(mx & ((1ull << lane_id()) - 1ull));
-          a.cls[2 * e] = (base + r) | ((v[0] & kLenMask) << 32);
-          a.cls[2 * e + 1] = (uint64_t)plane * cap + pre;
-        }
-      }
-      if (mm) {
-        const int leader = __builtin_ctzll(mm);
-        uint32_t wb = 0;
-        if (lane_id() == leader) wb = atomicAdd(a.counter + 6, (uint32_t)__popcll(mm));
-        wb = (uint32_t)__shfl((int)wb, leader);
-        if (cm) a.rest_ids[wb + (uint32_t)__popcll(mm & ((1ull << lane_id()) - 1ull))] = (uint32_t)(base + r);
       }
       uint32_t t0, t1;
       const uint32_t x0 = block_excl_scan<uint32_t>(c0, reinterpret_cast<uint32_t*>(tmp), t0);
@@ -1866,22 +1780,16 @@ __global__ __launch_bounds__(512) void k_row_walk(FusedArgs a) {
                                              : resid_word_at<PREDICT>(a.planes, g, plane, row, w)) & hmask;
     WSTAMP(5);
     const WideRow p = wide_prefix(x, w, O + row, sh);
-    uint32_t kor = 0, keol = 0;
-    uint64_t kt = 0;
+    uint32_t kor = 0;
     const bool eol = w == g.used - 1 && h == 1;
-    uint32_t ll = (kKMixRows || kKnownMix) && a.kmask ? word_len_kt(x, w, p.n, p.jp, row * (g.cols + 1), eol, g.cols, kor, kt, keol)
-                                       : word_len(x, w, p.n, p.jp, row * (g.cols + 1), eol, g.cols, kor);
+    uint32_t ll = word_len(x, w, p.n, p.jp, row * (g.cols + 1), eol, g.cols, kor);
     ll = wave_sum_u32(ll);
     WSTAMP(6);
     const uint64_t ks = __ballot(kor & ~1u), k1s = __ballot(kor & ~2u);  // some k != 0 / some k != 1
-    const uint64_t kbig = __ballot(kor & ~3u), ke = __ballot(keol);     // some k >= 2 / the end-of-row k = 1
-    if ((kKMixRows || kKnownMix) && a.kmask && i < a.kcap) {  // the word's k = 1 mask (its two halves' lanes combined) for kmix_row
-      const uint64_t kw = kWalkSplit == 2 ? kt | shfl_u64(kt, lane ^ 1) : kt;
-      if ((kWalkSplit == 1 || h == 0) && w < g.used) a.kmask[(uint64_t)i * g.used + w] = kw;
-    }
+    const uint64_t kbig = __ballot(kor & ~3u);                           // some k >= 2
     if (lane == 0) {
       sl[v] = ll;
-      sk[v] = (ks ? 1u : 0u) | (k1s ? 2u : 0u) | (kbig ? 4u : 0u) | (ke ? 8u : 0u);
+      sk[v] = (ks ? 1u : 0u) | (k1s ? 2u : 0u) | (kbig ? 4u : 0u);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1892,12 +1800,8 @@ __global__ __launch_bounds__(512) void k_row_walk(FusedArgs a) {
       }
       // (mixed-k rows and the plane's first-1 row are k_emit_rest's: it finds them in this list by
       // glen's flags and row_o, so no row is appended here -- thousands of same-address atomics
-      // would serialise this kernel; on the class kernels' path the mixed rows whose codewords all have
-      // k <= 1 and whose masks were stored are kmix_rows', flagged kKMix)
-      const bool kmix = a.kmask && i < a.kcap && (kk & 3u) == 3u && !(kk & 4u);
-      a.glen[id] = L | (!(kk & 1u) ? kK0Row : (!(kk & 2u) ? kK1Row : 0)) | (kmix ? kKMix : 0) |
-                   (kmix && (kk & 8u) ? kKEol1 : 0);
-      if (kmix) a.row_wi[id] = i;
+      // would serialise this kernel)
+      a.glen[id] = L | (!(kk & 1u) ? kK0Row : (!(kk & 2u) ? kK1Row : 0));
     }
     WSTAMP(7);
     __syncthreads();
@@ -1914,20 +1818,9 @@ __global__ __launch_bounds__(512) void k_row_walk(FusedArgs a) {
 // tables are staged (XCD-remapped block order: the waves of one XCD hold consecutive rows, the
 // row above is an L2 hit).
 constexpr int kEmitWaves = 4;
-#ifndef BIC_REST_AUX
-#define BIC_REST_AUX 1
-#endif
-constexpr bool kRestAux = BIC_REST_AUX != 0;
-#ifndef BIC_REST_PRIO
-#define BIC_REST_PRIO 0  // (A/B: k_emit_rest's waves at s_setprio(N) beside the class kernels)
-#endif  // k_emit_rest on the context's second stream (beside k_emit_known)
-#ifndef BIC_CLASS_NT
-#define BIC_CLASS_NT 0
-#endif
-// the class kernels' output stores (typed unsigned long long; BIC_CLASS_NT: non-temporal)
+// the class kernels' output stores (typed unsigned long long: see FusedArgs::cls)
 __device__ __forceinline__ void class_store(uint64_t* dst, uint64_t v) {
-  if constexpr (BIC_CLASS_NT) __builtin_nontemporal_store((unsigned long long)v, reinterpret_cast<unsigned long long*>(dst));
-  else *reinterpret_cast<unsigned long long*>(dst) = v;
+  *reinterpret_cast<unsigned long long*>(dst) = v;
 }
 // write_row64 with a fixed number of store instructions (MAXT per lane, the idle lanes' to a.sink)
 // and its stores typed unsigned long long (k_emit_k0)
@@ -1953,102 +1846,12 @@ __device__ __forceinline__ void write_row64_fixed(const uint64_t* img, uint64_t 
   }
 }
 
-// Rows mixing k = 0 and k = 1 (the walk stored each word's k = 1 mask): the backward-parity rows of
-// k1_rows with every column's k from the masks (bic_k1pi.h kmix_kk / kmix_word_*: a byte whose columns
-// share one k through the k = 1 table or verbatim, a byte where k changes column by column).
-// GolombCoder.cpp:13-34 per codeword. Lane l holds words t * 64 + l (one word group at a time: few
-// registers). kmix_encode: the row's residual words rr and k = 1 masks ktw into the wave's LDS image
-// gimg, then out (L bits at G; the words shared with neighbouring rows to the fragment table).
-template <int WPL>
-__device__ __forceinline__ void kmix_encode(const FusedArgs& a, const uint64_t (&rr)[WPL], const uint64_t (&ktw)[WPL],
-                                            uint32_t keol, uint64_t id, uint64_t L, uint64_t G, uint32_t* gimg,
-                                            const uint32_t* s_lut) {
-  const Geom& g = a.g;
-  const int lane = lane_id();
-  constexpr uint32_t kCapBits = (kGImg - kPad) * 32;
-  const uint32_t tail = g.cols & 63u;  // columns of the row's last word (0: a full word)
-    unsigned long long* z = reinterpret_cast<unsigned long long*>(gimg);
-    for (int j = lane; j < kGImg / 2; j += 64) z[j] = 0ull;
-    uint64_t* img = reinterpret_cast<uint64_t*>(gimg);
-    auto ws = [&](int t, uint64_t& xt, uint64_t& Z, uint64_t& kt) {
-      const uint32_t w = (uint32_t)t * 64 + lane;
-      const uint64_t valid = w < g.used ? (w == g.used - 1 ? g.trail : ~0ull) : 0ull;
-      const uint64_t eb = (w == g.used - 1 && tail) ? (BIC_MSB >> tail) : 0ull;  // the end-of-row 1
-      xt = rr[t] | eb;
-      Z = ~xt & valid;
-      kt = (ktw[t] & rr[t]) | (keol ? eb : 0ull);
-    };
-    // zeta (pi right of the word) and nk (the k of the first codeword ending after the word): from the
-    // nearest lane to the right in the word's group holding a 1, else from the first such word of a
-    // later group (carried), else the end of the row
-    uint32_t zb = 0, kb = 0, zc = 0, kc = keol;
-#pragma unroll
-    for (int t = WPL - 1; t >= 0; --t) {
-      uint64_t xt, Z, kt;
-      ws(t, xt, Z, kt);
-      const uint32_t cz = xt ? (uint32_t)__builtin_clzll(xt) : 0u;
-      const uint32_t lead = cz & 1u, leadk = (uint32_t)(kt >> (63 - cz)) & 1u;
-      const uint64_t m1 = __ballot(xt != 0);
-      const uint64_t nm = m1 & ~((2ull << lane) - 1ull);
-      const int src = nm ? (int)__builtin_ctzll(nm) : lane;
-      const uint32_t ln = (uint32_t)__shfl((int)lead, src), lnk = (uint32_t)__shfl((int)leadk, src);
-      zb |= (nm ? ln : zc) << t;
-      kb |= (nm ? lnk : kc) << t;
-      if (m1) {
-        const int f = (int)__builtin_ctzll(m1);
-        zc = (uint32_t)__builtin_amdgcn_readlane((int)lead, f);
-        kc = (uint32_t)__builtin_amdgcn_readlane((int)leadk, f);
-      }
-    }
-    const uint32_t kk0 = kc, lf = zc;  // the row's first codeword's k (its remainder bit leads), pi(-1)
-    const uint32_t* T = s_lut;
-    uint32_t loc = kk0;
-#pragma unroll
-    for (int t = 0; t < WPL; ++t) {
-      if (t * 64 >= (int)g.used) break;
-      const uint32_t w = (uint32_t)t * 64 + lane;
-      uint64_t xt, Z, kt;
-      ws(t, xt, Z, kt);
-      const uint32_t zt = (zb >> t) & 1u, nt = (kb >> t) & 1u;
-      const uint64_t Pi = k1_pi(xt, Z, zt), KK = kmix_kk(xt, Z, kt, nt);
-      uint64_t hi = 0, lo = 0, A, B;
-      uint32_t Lw = 0;
-      if (w < g.used) {
-        if (w == g.used - 1 && tail) Lw = kmix_word_last(rr[t], Pi, KK, nt, tail, hi, lo);
-        else Lw = kmix_word_full2(rr[t], Pi, KK, nt, T, hi, lo);
-      }
-      left128(hi, lo, Lw ? Lw : 128u, A, B);
-      const uint32_t inc = wave_incl_sum_u32(Lw);
-      place128_64(img, loc + inc - Lw, A, B, Lw);
-      loc += lane63_u32(inc);
-    }
-    const uint32_t tot = loc + (tail ? 0u : 1u);
-    if (lane == 0) {
-      if (kk0 && lf) lds_or64(img, 0, BIC_MSB);
-      if (!tail) lds_or64(img, (tot - 1) >> 6, BIC_MSB >> ((tot - 1) & 63));  // the end-of-row '1'
-      if (tot != L) atomicOr(&a.flags[3], 1u);  // the walk's length disagrees with the emission
-    }
-    write_row64_fixed<(kCapBits / 64 + 1 + 63) / 64>(img, L, G, a.out_g, a.gfrag + 2 * (uint64_t)id, a.sink);
-}
-
-// kmask / row_wi of a kKMix row: its words' k = 1 masks (word t * 64 + lane)
-template <int WPL>
-__device__ __forceinline__ void kmix_masks(const FusedArgs& a, uint64_t id, uint64_t (&ktw)[WPL]) {
-  const uint64_t* km = a.kmask + (uint64_t)a.row_wi[id] * a.g.used;
-#pragma unroll
-  for (int t = 0; t < WPL; ++t) {
-    const uint32_t w = (uint32_t)t * 64 + lane_id();
-    ktw[t] = km[w < a.g.used ? w : a.g.used - 1];
-  }
-}
-
 // One row of k_emit_known (rr: its residual words; O, Lf, Gb: its ones before, Golomb length + flags,
 // absolute Golomb bit offset; Eb: its plane's EG start bit), by one wave with its LDS image gimg.
 template <int WPL, bool PREDICT, bool DO_G, bool DO_E>
 __device__ __forceinline__ void emit_known_row(const FusedArgs& a, uint64_t id, uint32_t plane, uint32_t row,
                                                const uint64_t (&rr)[WPL], uint32_t O, uint64_t Lf, uint64_t Gb,
-                                               uint64_t Eb, uint32_t* gimg, const uint32_t* s_lut,
-                                               const uint32_t* s_lut2 = nullptr) {
+                                               uint64_t Eb, uint32_t* gimg, const uint32_t* s_lut) {
   const Geom& g = a.g;
   const int lane = lane_id();
   constexpr uint32_t kCapBits = (kGImg - kPad) * 32;
@@ -2094,57 +1897,6 @@ __device__ __forceinline__ void emit_known_row(const FusedArgs& a, uint64_t id, 
       eg_row_regs<WPL, false>(rr, g, Gb, L, a.out_g, a.gfrag + 2 * id);
     } else if (gk1) {  // every codeword k = 1: branch-free byte-table words into a 64-bit LDS image
       uint64_t* img = reinterpret_cast<uint64_t*>(gimg);
-#if BIC_KNOWN_PI
-      // the backward parity (k1_pi) over words t * 64 + lane: zeta of a word from the next word of the
-      // row holding a 1 -- in its group t to the right (ballot, bpermute), else the first such word of a
-      // later group (uniform)
-      const uint32_t tail = g.cols & 63u;
-      uint64_t xt[WPL], Zm[WPL];
-      uint32_t lead[WPL];
-      uint64_t m1[WPL];
-#pragma unroll
-      for (int t = 0; t < WPL; ++t) {
-        const uint32_t w = t * 64 + lane;
-        const uint64_t valid = w < g.used ? (w == g.used - 1 ? g.trail : ~0ull) : 0ull;
-        xt[t] = rr[t] | ((w == g.used - 1 && tail) ? (BIC_MSB >> tail) : 0ull);
-        Zm[t] = ~xt[t] & valid;
-        lead[t] = xt[t] ? (uint32_t)__builtin_clzll(xt[t]) & 1u : 0u;
-        m1[t] = __ballot(xt[t] != 0);
-      }
-      uint32_t carry = 0, first_r = 0;  // lead of the first word holding a 1 in the groups after t
-      uint32_t zeta[WPL];
-#pragma unroll
-      for (int t = WPL - 1; t >= 0; --t) {
-        const uint64_t nm = m1[t] & ~((2ull << lane) - 1ull);
-        const uint32_t ln = (uint32_t)__shfl((int)lead[t], nm ? (int)__builtin_ctzll(nm) : lane);
-        zeta[t] = nm ? ln : carry;
-        if (m1[t]) carry = (uint32_t)__builtin_amdgcn_readlane((int)lead[t], (int)__builtin_ctzll(m1[t]));
-      }
-      first_r = carry;  // (the lead of the row's first word holding a 1; 0: none)
-      const uint32_t* T = s_lut;
-      uint32_t loc = 1;  // bit 0: the first run's remainder
-#pragma unroll
-      for (int t = 0; t < WPL; ++t) {
-        if (t * 64 >= (int)g.used) break;
-        const uint32_t w = t * 64 + lane;
-        const uint64_t Pi = k1_pi(xt[t], Zm[t], zeta[t]);
-        uint64_t hi = 0, lo = 0, A, B;
-        uint32_t Lw = 0;
-        if (w < g.used) {
-          if (w == g.used - 1 && tail) Lw = k1_word_last(rr[t], Pi, tail, hi, lo);
-          else Lw = k1_word_full(rr[t], Pi, T, hi, lo);
-        }
-        left128(hi, lo, Lw ? Lw : 128u, A, B);
-        const uint32_t inc = wave_incl_sum_u32(Lw);
-        place128_64(img, loc + inc - Lw, A, B, Lw);
-        loc += lane63_u32(inc);
-      }
-      if (!tail) ++loc;  // the end-of-row '1' after the last word
-      if (lane == 0) {
-        if (first_r) lds_or64(img, 0, BIC_MSB);
-        if (!tail) lds_or64(img, (loc - 1) >> 6, BIC_MSB >> ((loc - 1) & 63));
-      }
-#else
       int jpc = -1;
       uint32_t loc = 0;
 #pragma unroll
@@ -2167,15 +1919,10 @@ __device__ __forceinline__ void emit_known_row(const FusedArgs& a, uint64_t id, 
           ls.flush();
         }
       }
-#endif
       if (lane == 0 && loc != L) atomicOr(&a.flags[3], 1u);  // word_len disagrees with the emission
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
       write_row64(img, L, Gb, a.out_g, a.gfrag + 2 * id);
-    } else if (kKnownMix && !DO_E && a.kmask && (Lf & kKMix) && L && fits) {  // k = 0 and k = 1 mixed
-      uint64_t ktw[WPL];
-      kmix_masks<WPL>(a, id, ktw);
-      kmix_encode<WPL>(a, rr, ktw, (Lf & kKEol1) ? 1u : 0u, id, L, Gb, gimg, s_lut2);
     }
     if (lane == 0) {
       // glen keeps its flags: k_emit_rest (on the other stream) reads them too
@@ -2186,67 +1933,23 @@ __device__ __forceinline__ void emit_known_row(const FusedArgs& a, uint64_t id, 
   }
 }
 
-#ifndef BIC_KNOWN_BATCH
-#define BIC_KNOWN_BATCH 1  // (4: C4 0.272 -> 0.309 ms; kept as a build-time A/B knob)
-#endif
-template <int WPL>
-constexpr int kKnownBatch = WPL == 1 ? BIC_KNOWN_BATCH : 1;
 // ES: the residual rows from the EG stream the count pass wrote (FusedArgs::esrc; PREDICT false)
 template <int WPL, bool PREDICT, bool DO_G, bool DO_E, bool ES = false>
-#ifndef BIC_KNOWN_MINW
-#define BIC_KNOWN_MINW 4  // (k_emit_known<1>: minimum waves per SIMD the compiler must fit)
-#endif
-__global__ __launch_bounds__(64 * kEmitWaves, WPL == 1 ? BIC_KNOWN_MINW : 4) void k_emit_known(FusedArgs a) {
+__global__ __launch_bounds__(64 * kEmitWaves, 4) void k_emit_known(FusedArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t lds[kEmitWaves * kGImg];
   __shared__ uint32_t s_lut[512];
-  __shared__ uint32_t s_lut2[kKnownMix && DO_G && !DO_E ? 512 : 1];  // (kmix_encode: the k = 1 parity table)
   const Geom& g = a.g;
   [[maybe_unused]] const int lane = lane_id();
   const int wave = (int)wave_id();
   uint32_t* gimg = lds + wave * kGImg;
   if (DO_G)
     for (uint32_t i = threadIdx.x; i < 512; i += blockDim.x) s_lut[i] = reinterpret_cast<const uint32_t*>(a.lut + 256)[kKnownTable + i];
-  if constexpr (kKnownMix && DO_G && !DO_E)
-    for (uint32_t i = threadIdx.x; i < 512; i += blockDim.x) s_lut2[i] = reinterpret_cast<const uint32_t*>(a.lut + 256)[kK1Table + i];
   __syncthreads();  // the only workgroup barrier
   const uint64_t nrows = (uint64_t)g.rows * g.nplanes;
   // persistent waves: rows id, id + stride, ...
   const uint64_t stride = (uint64_t)gridDim.x * kEmitWaves;
   const uint64_t id0 = (uint64_t)xcd_remap(blockIdx.x, gridDim.x) * kEmitWaves +
                        (uint32_t)__builtin_amdgcn_readfirstlane(wave);  // (uniform, as the compiler sees it)
-  if constexpr (!ES && kKnownBatch<WPL> > 1) {
-    // one-word rows (WPL = 1: rows of <= 4096 columns, e.g. C4's frames) are latency-bound: a wave
-    // loads kKnownBatch rows before it stores the first one's output (a wave that loaded after
-    // storing would wait for its stores' acknowledgements every row: vmcnt counts both)
-    constexpr int B = kKnownBatch<WPL>;
-    for (uint64_t id = id0; id < nrows; id += stride * B) {
-      uint64_t cp_[B][WPL], cu_[B][WPL];
-      uint32_t O[B];
-      uint64_t Lf[B], Gb[B];
-#pragma unroll
-      for (int u = 0; u < B; ++u) {
-        const uint64_t iu = id + u * stride < nrows ? id + u * stride : id;
-        const uint32_t plane = (uint32_t)(iu / g.rows), row = (uint32_t)(iu % g.rows);
-        row_load<WPL, PREDICT>(a.planes, g, plane, row, cp_[u], cu_[u]);
-        O[u] = a.row_o[iu];
-        Lf[u] = DO_G ? a.glen[iu] : 0;
-        Gb[u] = DO_G ? gb_abs(a, iu, plane) : 0;
-      }
-#pragma unroll
-      for (int u = 0; u < B; ++u) {
-        const uint64_t iu = id + u * stride;
-        if (iu >= nrows) break;
-        const uint32_t plane = (uint32_t)(iu / g.rows), row = (uint32_t)(iu % g.rows);
-        uint64_t rr[WPL];
-        row_resid<WPL, PREDICT>(g, row, cp_[u], cu_[u], rr);
-        const uint64_t Eb = DO_E ? (a.ebase ? a.ebase[plane] : (uint64_t)plane * a.slot_e * 64) : 0;
-        emit_known_row<WPL, PREDICT, DO_G, DO_E>(a, iu, plane, row, rr, O[u], Lf[u], Gb[u], Eb, gimg, s_lut, s_lut2);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the next row reuses the LDS image
-        __builtin_amdgcn_wave_barrier();
-      }
-    }
-    return;
-  }
   for (uint64_t id = id0; id < nrows; id += stride) {
     const uint32_t plane = (uint32_t)(id / g.rows), row = (uint32_t)(id % g.rows);
     STAMP(0);
@@ -2267,7 +1970,7 @@ __global__ __launch_bounds__(64 * kEmitWaves, WPL == 1 ? BIC_KNOWN_MINW : 4) voi
       row_resid<WPL, PREDICT>(g, row, cp_, cu_, rr);
     }
     const uint64_t Eb = DO_E ? (a.ebase ? a.ebase[plane] : (uint64_t)plane * a.slot_e * 64) : 0;
-    emit_known_row<WPL, PREDICT, DO_G, DO_E>(a, id, plane, row, rr, O, Lf, Gb, Eb, gimg, s_lut, s_lut2);
+    emit_known_row<WPL, PREDICT, DO_G, DO_E>(a, id, plane, row, rr, O, Lf, Gb, Eb, gimg, s_lut);
     STAMP(2);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the next row reuses the LDS image
     __builtin_amdgcn_wave_barrier();
@@ -2300,31 +2003,16 @@ __device__ __forceinline__ uint64_t cls_ld(const FusedArgs& a, uint64_t i) { ret
 // sample's zeros and its '1'), i.e. the EG row ~R '1' (eg.cpp:20-37) with its first cols bits inverted.
 // Output word t of the row (at bit Gb) holds row bits [64 t - g, 64 t - g + 64), g = Gb % 64: the
 // stream bits from Bsrc + 64 t - g (Bsrc: the row in the EG slot), one funnel shift per word.
-#ifndef BIC_K0_W16
-#define BIC_K0_W16 0
-#endif
 #ifndef BIC_K0_BATCH
 // (8-byte lanes, pipelined batches of 3: C3 emission 162-165 -> 157-158 us; of 2: 159-162; of 4: 170-173.
-// Batches of 2 keep k_emit_k01 at <= 128 VGPRs (113; batches of 3: 129), which its rest role needs
-// (BIC_K01_REST: a fourth workgroup slot per CU beside three persistent ones). 16-byte lanes: 115 VGPRs
-// at batches of 2). Round 6: batches of 2 with four workgroups per CU (BIC_K01_OCC 4, 113 VGPRs) --
+// Batches of 2 keep k_emit_k01 at <= 128 VGPRs (113; batches of 3: 129), a fourth workgroup slot per CU.
+// 16-byte lanes: 115 VGPRs at batches of 2, emission 167-168 us against 158-164).
+// Round 6: batches of 2 with four workgroups per CU (BIC_K01_OCC 4, 113 VGPRs) --
 // k_emit_k01 137 -> 132-137 us against 142-147 at batches of 3 and three per CU, same box
 // (profiles/r06/ab_emission.txt gj25, gj26); the C3 step unchanged (k_emit_rest beside it takes the slack)
 #define BIC_K0_BATCH 2
 #endif
 constexpr int kK0Batch = BIC_K0_BATCH;
-#ifndef BIC_DIAG_K0
-#define BIC_DIAG_K0 0
-#endif
-#ifndef BIC_K0_PLACE_AHEAD
-#define BIC_K0_PLACE_AHEAD 0
-#endif
-#ifndef BIC_K0_PIPE
-#define BIC_K0_PIPE 1
-#endif
-#ifndef BIC_K0_FAST
-#define BIC_K0_FAST 1
-#endif
 // the k = 0 list's entries i0, i0 + nw, ... (one wave; i0 and nw wave-uniform)
 template <int WPL, int BATCH = kK0Batch>
 __device__ __forceinline__ void k0_rows(const FusedArgs& a, uint32_t i0, uint32_t nw) {
@@ -2358,7 +2046,6 @@ __device__ __forceinline__ void k0_rows(const FusedArgs& a, uint32_t i0, uint32_
     r.d = (uint32_t)(s0 & 63);
     return r;
   };
-#if !BIC_K0_W16 && BIC_K0_FAST
   // Word groups 64 k .. 64 k + 63 of the output row. A group wholly inside the row (k >= 1 and before
   // the row's last word: C3's groups 1-3 of 5) needs no masks, clamps or fragment selects -- a uniform
   // branch on the row's scalar offsets -- and loads / stores through a scalar base plus the lane's
@@ -2410,57 +2097,6 @@ __device__ __forceinline__ void k0_rows(const FusedArgs& a, uint32_t i0, uint32_
       const bool in = t < nwo;
       const bool whole = in && (t != 0 || gs == 0) && (t != nwo - 1 || ((cur.G + L) & 63) == 0);
       uint64_t* dst = whole ? a.out_g + w0 + t : (in ? a.gfrag + 2 * (uint64_t)cur.id + (t == 0 ? 0 : 1) : a.sink + lane);
-      if (k < WPL || in) class_store(dst, whole ? bswap64(x) : x);
-    }
-  };
-#elif !BIC_K0_W16
-  // the row's source words (those holding its bits through its end-of-row '1'; the slot may end
-  // there): every lane loads, at a clamped index, the words outside masked where used
-  auto load = [&](const Row& r, uint64_t (&v)[WPL + 1]) {
-    const int64_t jend = r.si + (int64_t)((r.d + (r.G & 63) + g.cols) >> 6);
-#pragma unroll
-    for (int k = 0; k <= WPL; ++k) {
-      const int64_t j = r.si + 64 * k + lane;
-      const int64_t jc = j > jend ? jend : j;
-#if BIC_DIAG_K0 == 2  // diagnostic build only (wrong output): the copies' loads from one cached line
-      v[k] = S[lane + (r.id & 1)];
-      (void)jc;
-#else
-      v[k] = S[jc < 0 ? 0 : jc];
-#endif
-    }
-  };
-  auto emit = [&](const Row& cur, uint64_t (&v)[WPL + 1]) {
-    const uint32_t gs = (uint32_t)(cur.G & 63);
-    const uint64_t w0 = cur.G >> 6, nwo = ((cur.G + L - 1) >> 6) - w0 + 1;  // output words (<= used + 2)
-    const uint64_t eolw = (uint64_t)(g.cols + gs) >> 6, eolb = BIC_MSB >> ((g.cols + gs) & 63);
-    const int64_t jend = cur.si + (int64_t)((cur.d + gs + g.cols) >> 6);
-#pragma unroll
-    for (int k = 0; k <= WPL; ++k) {
-      const int64_t j = cur.si + 64 * k + lane;
-      v[k] &= 0ull - (uint64_t)((j >= 0) & (j <= jend));
-    }
-#pragma unroll
-    for (int k = 0; k <= WPL; ++k) {
-      const uint32_t t = 64 * k + lane;
-      uint64_t nx = ((uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v[k] >> 32), 0x130, 0xf, 0xf, true) << 32) |
-                    (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v[k], 0x130, 0xf, 0xf, true);
-      if (k < WPL) {
-        const uint64_t n0 = rl64(v[k + 1 <= WPL ? k + 1 : k], 0);
-        if (lane == 63) nx = n0;
-      }
-      const uint64_t hi = bswap64(v[k]);
-      uint64_t x = ~(cur.d ? funnel64(hi, bswap64(nx), 64 - cur.d) : hi);
-      // row bits outside [0, cols) are not the row's: before it (word 0's first gs bits) and from the
-      // end-of-row '1' on
-      if (t == 0) x &= ~0ull >> gs;
-      if (t >= eolw) x = t == eolw ? (x & ~((eolb << 1) - 1)) | eolb : 0ull;
-      const bool in = t < nwo;
-      const bool whole = in && (t != 0 || gs == 0) && (t != nwo - 1 || ((cur.G + L) & 63) == 0);
-      uint64_t* dst = whole ? a.out_g + w0 + t : (in ? a.gfrag + 2 * (uint64_t)cur.id + (t == 0 ? 0 : 1) : a.sink + lane);
-#if BIC_DIAG_K0 == 1  // diagnostic build only (wrong output): the copies' stores all to the sink
-      dst = a.sink + lane;
-#endif
       // (unsigned long long: a type apart from the u64 loads, so no load is taken to depend on it)
       // Only the last word group has lanes past the row (the row's 257-258 words of C3): those store
       // nothing (exec-masked, the instruction count unchanged) instead of writing the sink (emission
@@ -2468,103 +2104,12 @@ __device__ __forceinline__ void k0_rows(const FusedArgs& a, uint32_t i0, uint32_
       if (k < WPL || in) class_store(dst, whole ? bswap64(x) : x);
     }
   };
-#else
-  // 16 bytes per lane: lane q holds output words t0 = 128 k + 2 q - e and t0 + 1 (e = w0 & 1, so the
-  // pair's store is 16-byte aligned) and loads the source words si + t0, si + t0 + 1 with one 16-byte
-  // load (8-byte aligned: dword alignment is all global dwordx4 needs); si + t0 + 2 is lane q + 1's
-  // first word (DPP), lane 63's from the next group's lane 0. Half the memory instructions of the
-  // 8-byte form per row.
-  constexpr int NG = (64 * WPL + 3 + 127) / 128;
-  using V2 = HIP_vector_type<unsigned long long, 2>;
-  auto load = [&](const Row& r, V2 (&v)[NG]) {
-    const int64_t jend = r.si + (int64_t)((r.d + (r.G & 63) + g.cols) >> 6);
-    const int64_t e = (int64_t)((r.G >> 6) & 1);
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {
-      const int64_t j = r.si - e + 128 * k + 2 * lane;
-      int64_t jc = j > jend - 1 ? jend - 1 : j;
-      jc = jc < 0 ? 0 : jc;
-      v[k] = *reinterpret_cast<const V2*>(S + jc);
-      // words outside [0, jend] read as 0, the clamped pairs realigned (j = jend: its first word is the
-      // clamped pair's second; j = -1: its second word is the clamped pair's first)
-      const unsigned long long lo = v[k].x, hi = v[k].y;
-      v[k].x = (j >= 0 && j < jend) ? lo : (j == jend ? hi : 0ull);
-      v[k].y = (j >= 0 && j + 1 <= jend) ? (j < jend ? hi : 0ull) : (j == -1 ? lo : 0ull);
-    }
-  };
-  auto emit = [&](const Row& cur, V2 (&v)[NG]) {
-    const uint32_t gs = (uint32_t)(cur.G & 63);
-    const uint64_t w0 = cur.G >> 6;
-    const int64_t nwo = (int64_t)(((cur.G + L - 1) >> 6) - w0 + 1);
-    const int64_t eolw = (int64_t)((g.cols + gs) >> 6);
-    const uint64_t eolb = BIC_MSB >> ((g.cols + gs) & 63);
-    const int64_t e = (int64_t)(w0 & 1);
-    const bool tail_whole = ((cur.G + L) & 63) == 0;
-    auto fix = [&](uint64_t x, int64_t t) {
-      if (t == 0) x &= ~0ull >> gs;
-      if (t >= eolw) x = t == eolw ? (x & ~((eolb << 1) - 1)) | eolb : 0ull;
-      return x;
-    };
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {
-      const int64_t t0 = 128 * k + 2 * lane - e, t1 = t0 + 1;
-      uint64_t n0 = ((uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v[k].x >> 32), 0x130, 0xf, 0xf, true) << 32) |
-                    (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v[k].x, 0x130, 0xf, 0xf, true);
-      if (k + 1 < NG) {
-        const uint64_t nn = rl64(v[k + 1 < NG ? k + 1 : k].x, 0);
-        if (lane == 63) n0 = nn;
-      }
-      const uint64_t h0 = bswap64(v[k].x), h1 = bswap64(v[k].y), h2 = bswap64(n0);
-      const uint64_t x0 = fix(~(cur.d ? funnel64(h0, h1, 64 - cur.d) : h0), t0);
-      const uint64_t x1 = fix(~(cur.d ? funnel64(h1, h2, 64 - cur.d) : h1), t1);
-      const bool in0 = t0 >= 0 && t0 < nwo, in1 = t1 >= 0 && t1 < nwo;
-      const bool wh0 = in0 && (t0 != 0 || gs == 0) && (t0 != nwo - 1 || tail_whole);
-      const bool wh1 = in1 && (t1 != 0 || gs == 0) && (t1 != nwo - 1 || tail_whole);
-      if (wh0 && wh1) {
-        V2 o;
-        o.x = bswap64(x0);
-        o.y = bswap64(x1);
-        *reinterpret_cast<V2*>(a.out_g + w0 + t0) = o;
-      } else {
-        if (in0) class_store(wh0 ? a.out_g + w0 + t0 : a.gfrag + 2 * (uint64_t)cur.id + (t0 == 0 ? 0 : 1), wh0 ? bswap64(x0) : x0);
-        if (in1) class_store(wh1 ? a.out_g + w0 + t1 : a.gfrag + 2 * (uint64_t)cur.id + (t1 == 0 ? 0 : 1), wh1 ? bswap64(x1) : x1);
-      }
-    }
-  };
-#define BIC_K0_VT V2
-#define BIC_K0_VN NG
-#endif
-#if !BIC_K0_W16
-#define BIC_K0_VT uint64_t
-#define BIC_K0_VN WPL + 1
-#endif
   // rows in batches of BATCH: every row's loads issued before the first row's stores, so a wave
   // waits for its previous stores once per batch
-#if BIC_K0_PLACE_AHEAD
-  // the next batch's list entries (scalar loads) are read while this batch is emitted, so a batch's
-  // source loads never wait behind its own list entries
-  Row rn[BATCH];
-#pragma unroll
-  for (int u = 0; u < BATCH; ++u) rn[u] = place((uint32_t)u < R ? (uint32_t)u : 0u);
-  for (uint32_t k = 0; k < R; k += BATCH) {
-    Row r[BATCH];
-    BIC_K0_VT v[BATCH][BIC_K0_VN];
-#pragma unroll
-    for (int u = 0; u < BATCH; ++u) {
-      r[u] = rn[u];
-      load(r[u], v[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < BATCH; ++u) rn[u] = place(k + BATCH + u < R ? k + BATCH + u : k);
-#pragma unroll
-    for (int u = 0; u < BATCH; ++u)
-      if (k + u < R) emit(r[u], v[u]);
-  }
-#elif BIC_K0_PIPE
   // software-pipelined: batch k + 1's loads issued before batch k's stores, so the wait for a batch's
   // loads never covers the previous batch's stores (vmcnt counts both, in order)
   Row ra[BATCH], rb[BATCH];
-  BIC_K0_VT va[BATCH][BIC_K0_VN], vb[BATCH][BIC_K0_VN];
+  uint64_t va[BATCH][WPL + 1], vb[BATCH][WPL + 1];
 #pragma unroll
   for (int u = 0; u < BATCH; ++u) {
     ra[u] = place((uint32_t)u < R ? (uint32_t)u : 0u);
@@ -2590,23 +2135,7 @@ __device__ __forceinline__ void k0_rows(const FusedArgs& a, uint32_t i0, uint32_
     for (int u = 0; u < BATCH; ++u)
       if (k + BATCH + u < R) emit(rb[u], vb[u]);
   }
-#else
-  for (uint32_t k = 0; k < R; k += BATCH) {
-    Row r[BATCH];
-    BIC_K0_VT v[BATCH][BIC_K0_VN];
-#pragma unroll
-    for (int u = 0; u < BATCH; ++u) {
-      r[u] = place(k + u < R ? k + u : k);
-      load(r[u], v[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < BATCH; ++u)
-      if (k + u < R) emit(r[u], v[u]);
-  }
-#endif
 }
-#undef BIC_K0_VT
-#undef BIC_K0_VN
 
 // k = 1 rows: emit_known_row's byte-table path (encode_word_k1b into a 64-bit LDS row image, then
 // write_row64_fixed); rows whose image exceeds the window are listed for k_rows_global.
@@ -2614,12 +2143,9 @@ __device__ __forceinline__ void k0_rows(const FusedArgs& a, uint32_t i0, uint32_
 #define BIC_K1_BATCH 3
 #endif
 constexpr int kK1Batch = BIC_K1_BATCH;
-#ifndef BIC_K1_DYN
-#define BIC_K1_DYN 0  // (one ticket counter for every chunk of the ~32k k = 1 rows of C3: emission 157 -> 540 us;
-                      // device-scope atomics on one word stall every wave and the memory channel holding it)
-#endif
-constexpr bool kK1Dyn = BIC_K1_DYN != 0;  // k1_rows: chunks claimed by ticket instead of a static share
-// the k = 1 list's entries i0, i0 + nw, ... (one wave, with its LDS row image and the byte table)
+// the k = 1 list's entries i0, i0 + nw, ... (one wave, with its LDS row image and the byte table): a static
+// share (one ticket counter for every chunk of the ~32k k = 1 rows of C3: emission 157 -> 540 us; device-scope
+// atomics on one word stall every wave and the memory channel holding it)
 template <int WPL>
 __device__ __forceinline__ void k1_rows(const FusedArgs& a, uint32_t i0, uint32_t nw, uint32_t* gimg,
                                         const uint32_t* s_lut) {
@@ -2634,9 +2160,8 @@ __device__ __forceinline__ void k1_rows(const FusedArgs& a, uint32_t i0, uint32_
     uint32_t id, plane, row;
     uint64_t G, L;
   };
-  // (list entry e of the k = 1 list)
-  auto place_e = [&](uint64_t e_rel) {
-    const uint64_t e = nrows + e_rel;
+  auto place = [&](uint32_t k) {  // the wave's k-th row (entry i0 + k nw of the k = 1 list)
+    const uint64_t e = nrows + i0 + (uint64_t)k * nw;
     Row r;
     const uint64_t e0 = cls_ld(a, 2 * e);
     r.id = (uint32_t)e0;
@@ -2647,19 +2172,11 @@ __device__ __forceinline__ void k1_rows(const FusedArgs& a, uint32_t i0, uint32_
     r.G = a.off_g ? Gs - (uint64_t)r.plane * a.slot_g * 64 + a.gbase[r.plane] * 64 : Gs;
     return r;
   };
-  auto place = [&](uint32_t k) { return place_e(i0 + (uint64_t)k * nw); };  // the wave's k-th row
-#if BIC_K1_LC
+  // lane l holds the row's words l WPL .. (one wave scan per row, not per word group)
   constexpr int kV = WPL + 1;
-  auto emit = [&](const Row& cur, const uint64_t (&v)[kV], uint64_t) {
+  auto emit = [&](const Row& cur, const uint64_t (&v)[kV]) {
     if (cur.L > kCapBits) {  // (the LEN scan lists such rows as slow, never here: a length disagreement)
-      if (lane == 0) {
-        if (kSlowRest) {
-          atomicOr(&a.flags[3], 1u);
-        } else {
-          *reinterpret_cast<unsigned long long*>(a.gslow + cur.id) = a.row_o[cur.id] + cur.row + 1;
-          *reinterpret_cast<unsigned long long*>(a.slow_ids + atomicAdd(a.slow_n, 1u)) = cur.id;
-        }
-      }
+      if (lane == 0) atomicOr(&a.flags[3], 1u);
       return;
     }
     YSTAMP((1u << 18) + cur.id, 0);
@@ -2669,7 +2186,6 @@ __device__ __forceinline__ void k1_rows(const FusedArgs& a, uint32_t i0, uint32_
     eg_src_assemble_lc<WPL>(g, cur.row, v, rr);
     YSTAMP((1u << 18) + cur.id, 1);
     uint64_t* img = reinterpret_cast<uint64_t*>(gimg);
-#if BIC_K1_PI
     // the backward parity form (k1_pi): pi of each word's last column's right context (zeta) from the
     // next word holding a 1 -- in this lane, or the nearest lane to the right holding one (one ballot,
     // one bpermute); the row's first remainder bit from the first lane holding a 1
@@ -2735,141 +2251,21 @@ __device__ __forceinline__ void k1_rows(const FusedArgs& a, uint32_t i0, uint32_
     write_row64_fixed<(kCapBits / 64 + 1 + 63) / 64>(img, cur.L, cur.G, a.out_g, a.gfrag + 2 * (uint64_t)cur.id,
                                                      a.sink);
     YSTAMP((1u << 18) + cur.id, 3);
-#else
-    // the lane's words l WPL + t: their last 1s, the wave's exclusive max of the lanes' last 1
-    int lastc[WPL], mxl = -1;
-#pragma unroll
-    for (int t = 0; t < WPL; ++t) {
-      const uint32_t w = (uint32_t)lane * WPL + t;
-      lastc[t] = rr[t] ? (int)(w * 64 + 63 - __builtin_ctzll(rr[t])) : -1;
-      mxl = max(mxl, lastc[t]);
-    }
-    int jp = dpp_or<0x138>(-1, wave_incl_max(mxl));  // lane 0: -1
-    LaneEnc e[WPL];
-    int jps[WPL];
-    uint32_t lsum = 0;
-#pragma unroll
-    for (int t = 0; t < WPL; ++t) {
-      const uint32_t w = (uint32_t)lane * WPL + t;
-      jps[t] = jp;
-      e[t] = encode_word_k1b(rr[t], w, jp, w == g.used - 1, g.cols, s_lut);
-      lsum += e[t].len;
-      jp = max(jp, lastc[t]);
-    }
-    const uint32_t inc = wave_incl_sum_u32(lsum);
-    uint32_t off = inc - lsum;
-    const uint32_t loc = lane63_u32(inc);
-#pragma unroll
-    for (int t = 0; t < WPL; ++t) {
-      const uint32_t w = (uint32_t)lane * WPL + t;
-      if (!e[t].lng) {
-        if (e[t].head) lds_or64(img, off >> 6, BIC_MSB >> (off & 63));
-        place128_64(img, off + 1 + e[t].z, e[t].t0, e[t].t1, e[t].tlen);
-      } else {
-        LdsSink64 ls{img, 0, 0};
-        emit_word_k1(ls, off, rr[t], w, jps[t], w == g.used - 1, g.cols);
-        ls.flush();
-      }
-      off += e[t].len;
-    }
-    if (lane == 0 && loc != cur.L) atomicOr(&a.flags[3], 1u);  // word_len disagrees with the emission
-    write_row64_fixed<(kCapBits / 64 + 1 + 63) / 64>(img, cur.L, cur.G, a.out_g, a.gfrag + 2 * (uint64_t)cur.id,
-                                                     a.sink);
-#endif
   };
-  auto load = [&](const Row& r, uint64_t (&v)[kV], uint64_t&) {
+  auto load = [&](const Row& r, uint64_t (&v)[kV]) {
     eg_src_load_lc<WPL>(a.esrc + (uint64_t)r.plane * a.slot_e, g, r.row, v);
   };
-#else
-  auto emit = [&](const Row& cur, const uint64_t (&v)[WPL], uint64_t last) {
-    if (cur.L > kCapBits) {  // (the LEN scan lists such rows as slow, never here: a length disagreement)
-      if (lane == 0) {
-        if (kSlowRest) {
-          atomicOr(&a.flags[3], 1u);
-        } else {
-          *reinterpret_cast<unsigned long long*>(a.gslow + cur.id) = a.row_o[cur.id] + cur.row + 1;
-          *reinterpret_cast<unsigned long long*>(a.slow_ids + atomicAdd(a.slow_n, 1u)) = cur.id;
-        }
-      }
-      return;
-    }
-    // zeroed as unsigned long long, the type of the image's atomics (so ordered before them)
-    unsigned long long* z = reinterpret_cast<unsigned long long*>(gimg);
-    for (int j = lane; j < kGImg / 2; j += 64) z[j] = 0ull;
-    uint64_t rr[WPL];
-    eg_src_assemble<WPL>(g, cur.row, v, last, rr);
-    uint64_t* img = reinterpret_cast<uint64_t*>(gimg);
-    int jpc = -1;
-    uint32_t loc = 0;
-#pragma unroll
-    for (int t = 0; t < WPL; ++t) {
-      if (t * 64 >= (int)g.used) break;
-      const uint32_t w = t * 64 + lane;
-      const uint64_t x = rr[t];
-      const int jp = step_jp(x, w, jpc);
-      const bool eol = w == g.used - 1;
-      const LaneEnc e = encode_word_k1b(x, w, jp, eol, g.cols, s_lut);
-      const uint32_t inc = wave_incl_sum_u32(e.len);
-      const uint32_t off = loc + inc - e.len;
-      loc += lane63_u32(inc);
-      if (!e.lng) {
-        if (e.head) lds_or64(img, off >> 6, BIC_MSB >> (off & 63));
-        place128_64(img, off + 1 + e.z, e.t0, e.t1, e.tlen);
-      } else {
-        LdsSink64 ls{img, 0, 0};
-        emit_word_k1(ls, off, x, w, jp, eol, g.cols);
-        ls.flush();
-      }
-    }
-    if (lane == 0 && loc != cur.L) atomicOr(&a.flags[3], 1u);  // word_len disagrees with the emission
-    // (no fence: the image's zeroing, atomics and reads are one wave's 8-byte LDS operations of one type --
-    // the same width, which measured in order where a 16-byte zeroing did not (lds_image_zero32) -- and the
-    // compiler keeps same-typed accesses in their order)
-    // (rows up to kCapBits: at most (kCapBits + 63) / 64 + 1 output words)
-    write_row64_fixed<(kCapBits / 64 + 1 + 63) / 64>(img, cur.L, cur.G, a.out_g, a.gfrag + 2 * (uint64_t)cur.id,
-                                                     a.sink);
-  };
-  auto load = [&](const Row& r, uint64_t (&v)[WPL], uint64_t& last) {
-    eg_src_load<WPL>(a.esrc + (uint64_t)r.plane * a.slot_e, g, r.row, v, last);
-  };
-  constexpr int kV = WPL;
-#endif
-  if constexpr (kK1Dyn) {
-    // Chunks of kK1Batch consecutive list entries claimed by ticket (counter[10]; each wave comes here
-    // when its k = 0 share is done, so the waves that finish it early -- the older ones, which win the
-    // memory and issue arbitration -- take more of these rows). The next chunk is claimed after this
-    // chunk's loads and before its stores: the wait for the ticket never covers this chunk's stores.
-    (void)R;
-    uint32_t tv = 0;
-    if (lane == 0) tv = atomicAdd(a.counter + 10, 1u);
-    for (;;) {
-      const uint32_t c = uni_u32(tv) * (uint32_t)kK1Batch;
-      if (c >= n) break;
-      Row r[kK1Batch];
-      uint64_t v[kK1Batch][kV], l[kK1Batch];
-#pragma unroll
-      for (int u = 0; u < kK1Batch; ++u) {
-        r[u] = place_e(c + u < n ? c + u : c);
-        load(r[u], v[u], l[u]);
-      }
-      if (lane == 0) tv = atomicAdd(a.counter + 10, 1u);
-#pragma unroll
-      for (int u = 0; u < kK1Batch; ++u)
-        if (c + u < n) emit(r[u], v[u], l[u]);
-    }
-    return;
-  }
   for (uint32_t k = 0; k < R; k += kK1Batch) {  // (batches as k_emit_k0)
     Row r[kK1Batch];
-    uint64_t v[kK1Batch][kV], l[kK1Batch];
+    uint64_t v[kK1Batch][kV];
 #pragma unroll
     for (int u = 0; u < kK1Batch; ++u) {
       r[u] = place(k + u < R ? k + u : k);
-      load(r[u], v[u], l[u]);
+      load(r[u], v[u]);
     }
 #pragma unroll
     for (int u = 0; u < kK1Batch; ++u)
-      if (k + u < R) emit(r[u], v[u], l[u]);
+      if (k + u < R) emit(r[u], v[u]);
   }
 }
 
@@ -2896,7 +2292,6 @@ __device__ __forceinline__ void rest_row(const FusedArgs& a, uint64_t id, bool w
     if (walked) {  // a walked row: skip it unless mixed or the first-1 row (uniform over the workgroup)
       const uint64_t onext = row + 1 < g.rows ? a.row_o[id + 1] : a.pones[plane];
       if (!(L && !k0 && !k1) && !(DO_E && O == 0 && onext > 0)) return;
-      if (!DO_E && a.kmask && (Lf & kKMix) && L <= kCapBits) return;  // (k_emit_k01's kmix_rows writes it)
     }
     const bool gmix = DO_G && L && !k0 && !k1 && L <= kCapBits;
     uint64_t rr[1];
@@ -2970,9 +2365,6 @@ __global__ __launch_bounds__(256) void k_emit_rest(FusedArgs a) {
   __shared__ uint32_t sh[16];  // (wide_prefix: up to 8 waves)
   __shared__ int sf[4];
   const int lane = lane_id(), v = (int)wave_id(), nw = blockDim.x >> 6;
-#if BIC_REST_PRIO
-  __builtin_amdgcn_s_setprio(BIC_REST_PRIO);  // (A/B: the listed rows' waves ahead in the issue arbitration)
-#endif
   if (DO_G)
     for (uint32_t i = threadIdx.x; i < 512; i += blockDim.x) s_lut[i] = reinterpret_cast<const uint32_t*>(a.lut + 256)[i];
   __syncthreads();
@@ -2985,83 +2377,9 @@ __global__ __launch_bounds__(256) void k_emit_rest(FusedArgs a) {
                                   sh, sf);
   // the class kernels' path (a.cls): the LEN scan listed every row too long for an LDS image, so the
   // slow rows are written here, one wave per row, overlapping the class kernels (no k_rows_global)
-  if (DO_G && !PREDICT && kSlowRest && a.cls) {
+  if (DO_G && !PREDICT && a.cls) {
     const uint32_t nslow = __hip_atomic_load(a.slow_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (uint32_t li = blockIdx.x * nw + v; li < nslow; li += gridDim.x * nw) row_global<false>(a, a.slow_ids[li], lane);
-  }
-}
-
-// the class entries' third list (BIC_KMIX: k_emit_k01's rest role), residual rows from the EG stream
-template <int WPL>
-__device__ __forceinline__ void kmix_row(const FusedArgs& a, uint32_t i, uint32_t* gimg, const uint32_t* s_lut) {
-  const Geom& g = a.g;
-  const int lane = lane_id();
-  constexpr uint32_t kCapBits = (kGImg - kPad) * 32;
-  const uint64_t nrows = (uint64_t)g.rows * g.nplanes;
-  const uint64_t e = 2 * nrows + i;
-  const uint64_t e0 = cls_ld(a, 2 * e);
-  const uint32_t id = (uint32_t)e0;
-  const uint64_t L = e0 >> 32;
-  const uint32_t plane = id / g.rows, row = id % g.rows;
-  const uint64_t Gs = cls_ld(a, 2 * e + 1);
-  const uint64_t G = a.off_g ? Gs - (uint64_t)plane * a.slot_g * 64 + a.gbase[plane] * 64 : Gs;
-  XSTAMP((1u << 18) + id, 0);
-  const uint32_t keol = (a.glen[id] & kKEol1) ? 1u : 0u;
-  uint64_t rr[WPL], ktw[WPL];
-  eg_src_row<WPL>(a.esrc + (uint64_t)plane * a.slot_e, g, row, rr);
-  kmix_masks<WPL>(a, id, ktw);
-  XSTAMP((1u << 18) + id, 1);
-  if (L > kCapBits) {  // (the LEN scan lists such rows as slow, never here: a length disagreement)
-    if (lane == 0) atomicOr(&a.flags[3], 1u);
-    return;
-  }
-  kmix_encode<WPL>(a, rr, ktw, keol, id, L, G, gimg, s_lut);
-  XSTAMP((1u << 18) + id, 2);
-}
-
-// The class launch's rest role (the FusedArgs::rgrid leading workgroups of k_emit_k01, dispatched first,
-// one CU slot each beside the persistent class waves): the rows whose latency would otherwise be the
-// persistent waves' tail. First the rows mixing k = 0 and k = 1 (kmix_row, one wave each, claimed by
-// ticket: counter[9]); then, per workgroup, the mixed rows with a codeword of k >= 2 (rest_ids,
-// counter[6]; k_emit_rest's rows, ticket counter[7]); then the slow rows, one wave each. This is
-// k_emit_rest on a second stream without the stream: no fork / join events around the emission.
-template <int WPL>
-__device__ __forceinline__ void rest_role(const FusedArgs& a, uint32_t* lds, uint32_t* s_lut, uint32_t* s_lut2) {
-  __shared__ uint32_t sh[16];
-  __shared__ int sf[4];
-  __shared__ uint32_t tk[2];
-  for (uint32_t i = threadIdx.x; i < 512; i += blockDim.x) {
-    s_lut[i] = reinterpret_cast<const uint32_t*>(a.lut + 256)[kK1Table + i];  // (kmix_row: the k = 1 table)
-    s_lut2[i] = reinterpret_cast<const uint32_t*>(a.lut + 256)[i];            // (rest_row: encode_word's)
-  }
-  __syncthreads();
-  if (a.kmask) {
-    const uint32_t nx = __hip_atomic_load(a.counter + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t* gimg = lds + wave_id() * kGImg;
-    for (;;) {
-      uint32_t t = 0;
-      if (lane_id() == 0) t = atomicAdd(a.counter + 9, 1u);
-      t = uni_u32((uint32_t)__shfl((int)t, 0));
-      if (t >= nx) break;
-      kmix_row<WPL>(a, t, gimg, s_lut);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the next row reuses the LDS image
-      __builtin_amdgcn_wave_barrier();
-    }
-    XSTAMP((1u << 19) + 8192u + blockIdx.x * 4u + wave_id(), 1);
-    __syncthreads();  // (the images are the workgroup's again)
-  }
-  const uint32_t n = __hip_atomic_load(a.counter + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (uint32_t it = 0;; ++it) {
-    // (two ticket slots: a thread still reading the last one is never overwritten)
-    if (threadIdx.x == 0) tk[it & 1] = n ? atomicAdd(a.counter + 7, 1u) : 0u;
-    __syncthreads();
-    const uint32_t i = tk[it & 1];
-    if (i >= n) break;
-    rest_row<false, true, false>(a, a.rest_ids[i], false, lds, nullptr, s_lut2, sh, sf);
-  }
-  if (kSlowRest) {
-    const uint32_t nslow = __hip_atomic_load(a.slow_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (uint32_t li = blockIdx.x * 4 + wave_id(); li < nslow; li += a.rgrid * 4) row_global<false>(a, a.slow_ids[li], lane_id());
   }
 }
 
@@ -3080,28 +2398,13 @@ __global__ __launch_bounds__(256, BIC_K01_OCC ? BIC_K01_OCC : 1) void k_emit_k01
   const int lane = lane_id();
   [[maybe_unused]] const uint32_t gwv = (1u << 19) + 8192u + blockIdx.x * 4u + wave_id();  // (XSTAMP index)
   XSTAMP(gwv, 0);
-  // the rest role: the grid's first rgrid workgroups, or (BIC_K01_RLAST) its last ones -- dispatched after
-  // the persistent ones, so its waves are the younger ones in the SIMDs' VALU arbitration
-  const uint32_t pb = kK01RLast ? gridDim.x - a.rgrid : 0u;  // the rest role's first workgroup
-  if constexpr (kK01Rest) {
-    if (blockIdx.x >= pb && blockIdx.x < pb + a.rgrid) {  // the rest role (k_emit_rest's rows in this launch)
-      __shared__ uint32_t s_lut2[512];
-      rest_role<WPL>(a, lds, s_lut, s_lut2);
-      XSTAMP(gwv, 3);
-      return;
-    }
-  }
-  // (BIC_K01_PRIO: the persistent waves' VALU ahead of the rest role's, whose per-codeword rows would
-  // otherwise take issue slots from the copies)
-  if constexpr (kK01Prio) __builtin_amdgcn_s_setprio(2);
   uint32_t* gimg = lds + wave_id() * kGImg;
   // every wave writes the whole table itself (the same values as the others): its own reads then
   // follow its own writes, and the kernel needs no workgroup barrier
   for (uint32_t i = lane; i < 512; i += 64) s_lut[i] = reinterpret_cast<const uint32_t*>(a.lut + 256)[kK1Table + i];
-  const uint32_t nb = gridDim.x - a.rgrid, nw = nb * 4;
-  // (the wave index through readfirstlane: the compiler then knows i0, and every branch on it, is uniform;
-  // rgrid is a multiple of 8, so block b - rgrid keeps block b's XCD)
-  const uint32_t i0 = xcd_remap(blockIdx.x - (kK01RLast ? 0u : a.rgrid), nb) * 4 + wave_id();
+  const uint32_t nb = gridDim.x, nw = nb * 4;
+  // (the wave index through readfirstlane: the compiler then knows i0, and every branch on it, is uniform)
+  const uint32_t i0 = xcd_remap(blockIdx.x, nb) * 4 + wave_id();
   k0_rows<WPL>(a, i0, nw);
   XSTAMP(gwv, 1);
   k1_rows<WPL>(a, i0, nw, gimg, s_lut);
@@ -3178,28 +2481,34 @@ void launch_fixup_rows(hipStream_t s, const uint64_t* boff, const uint64_t* len,
 }
 
 // ------------------------------------------------------------------------------------
-// walked rows whose k = 1 masks the walk stores (kmix_rows; the others stay the rest role's): 4 Mi mask
-// words, 32 MiB (C3: 16,384 rows, against ~1,400 walked)
-static uint32_t kmask_rows(const Geom& g) {
-  const uint64_t n = (uint64_t)g.rows * g.nplanes;
-  return (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(64, (4ull << 20) / g.used));
-}
-
+// The scratch block. fused_scratch_bytes and carve_fused_scratch list the same terms in the same order
+// (n = rows * planes); a term added to one goes into the other at the same place.
 size_t fused_scratch_bytes(const Geom& g) {
   const size_t n = (size_t)g.rows * g.nplanes;
-  return 256 + n * 8 * 2 + n * 8 * 10 + n * kMaxStrips * (16 + 4 + 4) + n * 4 * 4 + 1024 + (size_t)g.nplanes * 8 * 4 + 64 +
-         n * 16 * 3 + 64 + 512 +  // (cls: three lists, sink)
-         n * 4 + (size_t)kmask_rows(g) * g.used * 8 + 64;  // (row_wi, kmask)
+  return 256 +                            // counter
+         n * 8 * 2 +                      // ones_rec, bits_rec
+         n * 8 * 10 +                     // gboff, glen, gfrag (2 n), gslow, eboff, elen, efrag (2 n), slow_ids
+         n * kMaxStrips * (16 + 4 + 4) +  // krec, kpos, sones
+         n * 4 * 4 +                      // row_o, walk_ids, rest_ids, walk_o
+         (size_t)g.nplanes * 8 * 4 +      // pones, gbase, ebase, efix
+         n * 16 * 2 +                     // cls: the k = 0 list and the k = 1 list, two u64 words per entry
+         512 +                            // sink
+         1024 + 64 + 64;                  // unassigned tail (covers rounding pones up to 8 bytes)
 }
 
 FusedScratch carve_fused_scratch(void* base, const Geom& g) {
   const size_t n = (size_t)g.rows * g.nplanes;
   char* p = reinterpret_cast<char*>(base);
   FusedScratch fs;
+  // counter: kZeroWords u32 words in 256 bytes. [0] the single / two-pass encoders' tile ticket, [1] slow_n,
+  // [2] the walk list's length, [3] rest_ids', [4] and [5] the k = 0 and k = 1 class lists'; the words from
+  // [6] on are unused ([6..10] served experiments whose code was removed)
   fs.counter = reinterpret_cast<uint32_t*>(p);
+  // ones_rec, bits_rec
   fs.ones_rec = reinterpret_cast<uint64_t*>(p + 256);
   fs.bits_rec = fs.ones_rec + n;
   fs.zero_bytes = 256 + n * 16;
+  // gboff, glen, gfrag, gslow, eboff, elen, efrag, slow_ids
   uint64_t* q = fs.bits_rec + n;
   fs.gboff = q; q += n;
   fs.glen = q; q += n;
@@ -3209,26 +2518,25 @@ FusedScratch carve_fused_scratch(void* base, const Geom& g) {
   fs.elen = q; q += n;
   fs.efrag = q; q += 2 * n;
   fs.slow_ids = q; q += n;
+  // krec, kpos, sones
   fs.krec = reinterpret_cast<int4*>(q);
   fs.kpos = reinterpret_cast<uint32_t*>(fs.krec + n * kMaxStrips);
   fs.sones = fs.kpos + n * kMaxStrips;
+  // row_o, walk_ids, rest_ids, walk_o
   fs.row_o = fs.sones + n * kMaxStrips;
   fs.walk_ids = fs.row_o + n;
   fs.rest_ids = fs.walk_ids + n;
   fs.walk_o = fs.rest_ids + n;
-  {
-    uintptr_t e = reinterpret_cast<uintptr_t>(fs.walk_o + n);
-    e = (e + 7) & ~(uintptr_t)7;
-    fs.pones = reinterpret_cast<uint64_t*>(e);
-    fs.gbase = fs.pones + g.nplanes;
-    fs.ebase = fs.gbase + g.nplanes;
-    fs.efix = fs.ebase + g.nplanes;
-    fs.cls = fs.efix + g.nplanes;
-    fs.sink = fs.cls + 6 * n;
-    fs.kmask = fs.sink + 64;
-    fs.kcap = kmask_rows(g);
-    fs.row_wi = reinterpret_cast<uint32_t*>(fs.kmask + (size_t)fs.kcap * g.used);
-  }
+  // pones, gbase, ebase, efix (rounded up to 8 bytes: the tail pays for it)
+  const uintptr_t e = (reinterpret_cast<uintptr_t>(fs.walk_o + n) + 7) & ~(uintptr_t)7;
+  fs.pones = reinterpret_cast<uint64_t*>(e);
+  fs.gbase = fs.pones + g.nplanes;
+  fs.ebase = fs.gbase + g.nplanes;
+  fs.efix = fs.ebase + g.nplanes;
+  // cls
+  fs.cls = fs.efix + g.nplanes;
+  // sink
+  fs.sink = fs.cls + 4 * n;
   fs.ns = 1;
   fs.counted = false;
   fs.slow_n = fs.counter + 1;  // zeroed with the counter
@@ -3272,12 +2580,6 @@ void launch_fused(hipStream_t s, const Geom& g, const uint64_t* planes, const ui
   a.efix = es ? fs.efix : nullptr;
   a.cls = es && out_g && !fs.eg_src_one ? fs.cls : nullptr;
   a.sink = fs.sink;
-  // the walk stores the k = 1 masks of mixed rows for kmix_rows (class kernels' path only)
-  // (k_emit_k01's rest role writes kKMix rows; or k_emit_known itself, planes in and Golomb alone)
-  a.kmask = (a.cls && kKMixRows && kK01Rest) || (kKnownMix && !es && out_g && !out_e && mode == kEncStaged) ? fs.kmask
-                                                                                                            : nullptr;
-  a.row_wi = fs.row_wi;
-  a.kcap = fs.kcap;
 #ifdef BIC_STAMPS
   a.known = getenv("BIC_KNOWN") && getenv("BIC_KNOWN")[0] == '1';
 #endif
@@ -3290,7 +2592,7 @@ void launch_fused(hipStream_t s, const Geom& g, const uint64_t* planes, const ui
     // a fixed small grid walks the list of LDS-overflow rows (usually empty); block 0 also clears
     // the EG source's one bit per plane (eg_fix_bit)
     // (a.cls: k_emit_rest wrote the slow rows; single pass: k_encode_rows did)
-    if ((dg && !single_pass && (!a.cls || !kSlowRest)) || (!dg && es)) {
+    if ((dg && !single_pass && !a.cls) || (!dg && es)) {
       if (predict) k_rows_global<true><<<dg ? 256 : 1, 256, 0, s>>>(a);
       else k_rows_global<false><<<dg ? 256 : 1, 256, 0, s>>>(a);
     }
@@ -3351,10 +2653,8 @@ void launch_fused(hipStream_t s, const Geom& g, const uint64_t* planes, const ui
     auto main_ev = [&](hipEvent_t e) {
       if (e && hipEventRecord(e, s) == hipSuccess && e == fs.ev_main1 && fs.ev_main_rec) *fs.ev_main_rec = true;
     };
-    // (the class kernels' path with the rest role inside k_emit_k01: one launch, no second stream)
-    const bool one_launch = es && a.cls && kK01Rest;
     hipStream_t rs = s;
-    if (!one_launch && kRestAux && fs.aux && fs.ev_fork && fs.ev_join && hipEventRecord(fs.ev_fork, s) == hipSuccess &&
+    if (fs.aux && fs.ev_fork && fs.ev_join && hipEventRecord(fs.ev_fork, s) == hipSuccess &&
         hipStreamWaitEvent(fs.aux, fs.ev_fork, 0) == hipSuccess)
       rs = fs.aux;
 #define BIC_EMIT1(W, P, DG, DE, ES)                                                                    \
@@ -3376,19 +2676,10 @@ void launch_fused(hipStream_t s, const Geom& g, const uint64_t* planes, const ui
 #define BIC_EMITC(W)                                                                                      \
   {                                                                                                    \
     static const int o_ = occ_of(reinterpret_cast<const void*>(&k_emit_k01<W>));                      \
-    if (one_launch) {                                                                                  \
-      a.rgrid = kK01Rg ? kK01Rg : std::max(8u, (uint32_t)cus / 8 * 8);                                 \
-      main_ev(fs.ev_main0);                                                                            \
-      const uint32_t pg = (uint32_t)std::min<uint64_t>((nrows + 3) / 4, kK01Rg ? (uint64_t)cus * o_ - a.rgrid   \
-                                                                                 : (uint64_t)cus * std::max(1, o_ - 1)); \
-      k_emit_k01<W><<<a.rgrid + pg, 256, 0, s>>>(a);                                                   \
-      main_ev(fs.ev_main1);                                                                            \
-    } else {                                                                                           \
-      k_emit_rest<false, true, false><<<rgrid, 64 * nwv, 0, rs>>>(a);                                  \
-      main_ev(fs.ev_main0);                                                                            \
-      k_emit_k01<W><<<egrid_of(o_), 256, 0, s>>>(a);                                                   \
-      main_ev(fs.ev_main1);                                                                            \
-    }                                                                                                  \
+    k_emit_rest<false, true, false><<<rgrid, 64 * nwv, 0, rs>>>(a);                                    \
+    main_ev(fs.ev_main0);                                                                              \
+    k_emit_k01<W><<<egrid_of(o_), 256, 0, s>>>(a);                                                     \
+    main_ev(fs.ev_main1);                                                                              \
   }
       if (wpl == 1) { BIC_EMITC(1); } else if (wpl == 2) { BIC_EMITC(2); } else { BIC_EMITC(4); }
 #undef BIC_EMITC

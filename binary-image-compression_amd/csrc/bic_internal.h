@@ -160,14 +160,9 @@ struct FusedScratch {
   // EG source: the LEN scan lists the rows whose codewords all have k = 0 (entries [0 .. counter[4]))
   // and all k = 1 (entries [n ..], counter[5]) for the two class emission kernels (n = rows * planes),
   // each entry two u64 words: the row id | its Golomb length << 32, then its slot-relative Golomb bit
-  // offset (gboff's value); a third list (entries [2n ..], counter[8]) holds the rows mixing k = 0 and
-  // k = 1 whose per-codeword k the walk stored (kmask / row_wi, kcap walked rows): kmix_rows. The other
-  // mixed rows (a codeword with k >= 2) stay the rest role's / k_emit_rest's
+  // offset (gboff's value): 2 n entries in all. The rows of mixed k stay k_emit_rest's
   uint64_t* cls = nullptr;
   uint64_t* sink = nullptr;   // 64 words the class kernels' idle lanes store to (a fixed store count)
-  uint64_t* kmask = nullptr;  // per walked row (walk list index < kcap): its words' k = 1 masks
-  uint32_t* row_wi = nullptr; // per kKMix row: its walk list index
-  uint32_t kcap = 0;
   bool eg_src_one = false;  // (A/B: the one emission kernel k_emit_known for every class instead)
 };
 size_t fused_scratch_bytes(const Geom& g);

@@ -1,7 +1,7 @@
 """Phase clocks of the class emission launch (diagnostic build lib/libbic_stamps.so, make stamps; the
-XSTAMP slots of bic_fused.hip): one C3 encode_gray (the bench's default call, twice), then per wave of
-k_emit_k01 its entry / k = 0 rows done / exit (persistent waves) or entry / kmix rows done / exit (rest
-role), and per kmix row its entry, loads done and stored times, on the shared 100 MHz clock."""
+XSTAMP / YSTAMP slots of bic_fused.hip): one C3 encode_gray (the bench's default call, twice), then per
+persistent wave of k_emit_k01 its entry / k = 0 rows done / exit, and per k = 1 row its entry, assembled,
+placed and stored times, on the shared 100 MHz clock."""
 import json
 import os
 import sys
@@ -37,22 +37,12 @@ for rep in range(2):
     t0 = W[live, 0].min()
     K = buf[(1 << 18) * 4:((1 << 18) + rows * 8) * 4].reshape(-1, 4).astype(np.int64)
     K0 = buf0[(1 << 18) * 4:((1 << 18) + rows * 8) * 4].reshape(-1, 4).astype(np.int64)
-    km = (K[:, 0] > 0) & (K[:, 0] != K0[:, 0])
-    Kk = K[km]
-    rg = int(os.environ.get("RG", "1024"))  # rest-role waves (the first rg of the launch's waves)
-    idx = np.nonzero(live)[0]
-    rest = idx[idx < rg]
-    pers = idx[idx >= rg]
+    pw = np.nonzero(live)[0]  # the persistent waves (every wave of the launch)
     out = dict(rep=rep, waves=int(live.sum()),
-               persistent_k0_done_us=d((W[pers, 1] - t0) / 100), persistent_exit_us=d((W[pers, 3] - t0) / 100),
-               rest_kmix_done_us=d((W[rest, 1] - t0) / 100), rest_exit_us=d((W[rest, 3] - t0) / 100),
-               kmix_rows=int(km.sum()), kmix_start_us=d((Kk[:, 0] - t0) / 100),
-               kmix_load_us=d((Kk[:, 1] - Kk[:, 0]) / 100), kmix_code_us=d((Kk[:, 2] - Kk[:, 1]) / 100))
+               persistent_k0_done_us=d((W[pw, 1] - t0) / 100), persistent_exit_us=d((W[pw, 3] - t0) / 100))
     print(json.dumps(out), flush=True)
     # where the spread comes from: per XCD (block % 8), per wave of the workgroup, per CU slot (block // 8 % ...)
     if rep == 1:
-        blk = (idx - 0) // 4
-        pw = idx[idx >= rg]
         b = pw // 4
         k0d = (W[pw, 1] - t0) / 100
         ex = (W[pw, 3] - t0) / 100
