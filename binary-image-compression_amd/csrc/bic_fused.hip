@@ -25,6 +25,7 @@
 #include "bic_kstat.h"
 
 #include <algorithm>
+#include <cstdio>
 
 namespace bic {
 
@@ -1510,18 +1511,22 @@ __device__ __forceinline__ void plane_bases(const FusedArgs& a, uint64_t* tmp) {
     if (a.off_e) a.off_e[g.nplanes] = ce;
   }
 }
-// Exclusive per-plane scan of per-row values. Each 1024-thread workgroup owns kScanChunk rows of a
+// Exclusive per-plane scan of per-row values. Each kScanThreads-thread workgroup owns kScanChunk rows of a
 // plane (kScanPer consecutive rows per thread) and sums the plane's earlier rows itself (coalesced,
-// at most rows / 1024 loads per thread), so no workgroup waits on another and a plane spreads over
+// at most rows / kScanThreads loads per thread), so no workgroup waits on another and a plane spreads over
 // rows / kScanChunk CUs. ONES: the strips' 1-counts (sones) -> row_o[], the ones before each row;
 // with CLASSIFY each row is also classified (row_class) and the rows to walk are appended to
 // walk_ids. Otherwise: glen[] Golomb lengths -> gboff[] absolute bit offsets in the plane's slot,
 // bits_g[] the plane's total; rows past the slot's end get glen = 0 and raise the overflow flag
 // (a later chunk may then sum a zeroed length: its offsets stay inside the slot, and the call
 // reports BIC_ENOSPC with the stream undefined).
-constexpr uint32_t kScanPer = 1, kScanChunk = 1024 * kScanPer;  // (1024-row chunks: twice the workgroups of 2048, C3 prefix 51 -> 42 us)
+constexpr uint32_t kScanThreads = 512;
+// (1024-row chunks: twice the workgroups of 2048, C3 prefix 51 -> 42 us; 512-row chunks, 256 workgroups for
+// C3's 256 CUs: the ONES scan 12.8-14.2 -> 10.4-11.7 us)
+constexpr uint32_t kScanPer = 1, kScanChunk = kScanThreads * kScanPer;
+constexpr uint32_t kScanAhead = 16;  // loads in flight per thread in the ONES scan's sum of the plane's earlier rows (C3: all of them)
 template <bool ONES, bool CLASSIFY>
-__global__ __launch_bounds__(1024) void k_scan_rows(FusedArgs a) {
+__global__ __launch_bounds__(kScanThreads) void k_scan_rows(FusedArgs a) {
   __shared__ uint64_t tmp[17];
   const Geom& g = a.g;
   const uint32_t nb = (g.rows + kScanChunk - 1) / kScanChunk;
@@ -1530,8 +1535,19 @@ __global__ __launch_bounds__(1024) void k_scan_rows(FusedArgs a) {
   const uint64_t base = (uint64_t)plane * g.rows;
   auto val = [&](uint32_t r) -> uint64_t {
     if constexpr (ONES) {
+      // a row's strip counts in one load for 1, 2 and 4 strips (4: C3; 16 bytes, aligned as sones is)
+      const uint32_t* so = a.sones + (base + r) * a.ns;
+      if (a.ns == 4) {
+        const uint4 q = *reinterpret_cast<const uint4*>(so);
+        return (uint64_t)q.x + q.y + q.z + q.w;
+      }
+      if (a.ns == 2) {
+        const uint2 q = *reinterpret_cast<const uint2*>(so);
+        return (uint64_t)q.x + q.y;
+      }
+      if (a.ns == 1) return so[0];
       uint64_t o = 0;
-      for (uint32_t q = 0; q < a.ns; ++q) o += a.sones[(base + r) * a.ns + q];
+      for (uint32_t q = 0; q < a.ns; ++q) o += so[q];
       return o;
     } else {
       return a.glen[base + r] & kLenMask;
@@ -1561,25 +1577,44 @@ __global__ __launch_bounds__(1024) void k_scan_rows(FusedArgs a) {
     const uint32_t* so = a.sones + base * a.ns;
     const uint64_t flat = (uint64_t)lim * a.ns;  // a multiple of 4 (lim is one of kScanChunk)
     if ((base * a.ns) % 4 == 0) {  // 16-byte loads
+      // kScanAhead independent loads per trip, each at a clamped index and all issued before the first
+      // is used: one wait for C3's <= 15 loads per thread
       const uint4* s4 = reinterpret_cast<const uint4*>(so);
-#pragma unroll 8
-      for (uint64_t i = threadIdx.x; i < flat / 4; i += 1024) {
-        const uint4 q = s4[i];
-        before += (uint64_t)q.x + q.y + q.z + q.w;
+      const uint64_t n4 = flat / 4;
+      for (uint64_t i0 = threadIdx.x; i0 < n4; i0 += kScanAhead * kScanThreads) {
+        uint4 q[kScanAhead];
+#pragma unroll
+        for (uint32_t k = 0; k < kScanAhead; ++k) {
+          const uint64_t i = i0 + k * kScanThreads;
+          q[k] = s4[i < n4 ? i : i0];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kScanAhead; ++k)
+          if (i0 + k * kScanThreads < n4) before += (uint64_t)q[k].x + q[k].y + q[k].z + q[k].w;
       }
     } else {
 #pragma unroll 8
-      for (uint64_t i = threadIdx.x; i < flat; i += 1024) before += so[i];
+      for (uint64_t i = threadIdx.x; i < flat; i += kScanThreads) before += so[i];
     }
   } else {
 #pragma unroll 8
-    for (uint32_t r = threadIdx.x; r < lim; r += 1024) before += val(r);
+    for (uint32_t r = threadIdx.x; r < lim; r += kScanThreads) before += val(r);
   }
   SSTAMP(2);
-  uint64_t tot, btot;
-  uint64_t pre = block_excl_scan<uint64_t>(sum, tmp, tot);
-  (void)block_excl_scan<uint64_t>(before, tmp, btot);
-  pre += btot;
+  uint64_t tot, btot, pre;
+  if constexpr (ONES) {
+    // one workgroup scan of a packed pair: a plane's 1-count fits 32 bits (fused_supported), so the low
+    // half -- the chunk's prefix -- never carries into the high half, whose total is `before`'s sum
+    uint64_t t2;
+    const uint64_t p2 = block_excl_scan<uint64_t>(sum | (before << 32), tmp, t2);
+    tot = (uint32_t)t2;
+    btot = t2 >> 32;
+    pre = (uint32_t)p2 + btot;
+  } else {  // (the lengths stay 64-bit)
+    pre = block_excl_scan<uint64_t>(sum, tmp, tot);
+    (void)block_excl_scan<uint64_t>(before, tmp, btot);
+    pre += btot;
+  }
   SSTAMP(3);
   if constexpr (ONES) {
     bool walks[kScanPer];  // classify every row of the thread first: their record loads overlap
@@ -2387,11 +2422,18 @@ __global__ __launch_bounds__(256) void k_emit_rest(FusedArgs a) {
 // The waves reach the byte-table rows at different times, so the copies (memory-bound) and the
 // byte-table rows (issue-bound) run side by side instead of one launch after the other. (Odd waves
 // starting on the k = 1 rows measured 196-198 µs against 192-193, round 4.)
-template <int WPL>
 #ifndef BIC_K01_OCC
 #define BIC_K01_OCC 4  // a minimum of workgroups (one wave per SIMD each) per CU for k_emit_k01 (0: none;
                        // the compiler then took 133 VGPRs, three per CU)
 #endif
+// At most 112 registers, one fewer than the compiler takes by itself: four workgroups then leave 64 of a
+// SIMD's 512 for one wave of k_emit_rest (59 registers, allocated as 64), whose rows otherwise wait for
+// these persistent waves to end (k_emit_rest ended 3-9 us after this kernel). The attribute counts
+// architectural registers, half of this target's unified file, hence 56; launch_fused checks what the
+// build gave (k01_regs_checked).
+constexpr int kK01Regs = 112;
+template <int WPL>
+__attribute__((amdgpu_num_vgpr(kK01Regs / 2)))
 __global__ __launch_bounds__(256, BIC_K01_OCC ? BIC_K01_OCC : 1) void k_emit_k01(FusedArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t lds[4 * kGImg];
   __shared__ uint32_t s_lut[512];
@@ -2543,7 +2585,8 @@ FusedScratch carve_fused_scratch(void* base, const Geom& g) {
   return fs;
 }
 
-bool fused_supported(const Geom& g) { return g.used <= 256; }
+// (a plane's pixels fit 32 bits: row_o, and the ONES scan's packed pair, hold a plane's 1-count in 32)
+bool fused_supported(const Geom& g) { return g.used <= 256 && (uint64_t)g.rows * g.cols <= 0xffffffffull; }
 
 #ifdef BIC_STAMPS
 int read_stamps(uint64_t* host, size_t n) {
@@ -2611,13 +2654,13 @@ void launch_fused(hipStream_t s, const Geom& g, const uint64_t* planes, const ui
     if (stage == kFusedPrefix) {
       if (!fs.counted) launch_row_ones(s, g, planes, predict, fs.sones, fs.krec, fs.kpos, fs.counter);
       const uint32_t sgrid = (g.rows + kScanChunk - 1) / kScanChunk * g.nplanes;
-      if (dg) k_scan_rows<true, true><<<sgrid, 1024, 0, s>>>(a);
-      else k_scan_rows<true, false><<<sgrid, 1024, 0, s>>>(a);
+      if (dg) k_scan_rows<true, true><<<sgrid, kScanThreads, 0, s>>>(a);
+      else k_scan_rows<true, false><<<sgrid, kScanThreads, 0, s>>>(a);
       if (dg) {
         const uint32_t wwv = (kWalkSplit * g.used + 63) / 64;  // k_row_walk: waves per row (<= 8)
         if (predict) k_row_walk<true><<<kWalkWaves / wwv, 64 * wwv, 0, s>>>(a);
         else k_row_walk<false><<<kWalkWaves / wwv, 64 * wwv, 0, s>>>(a);
-        k_scan_rows<false, false><<<sgrid, 1024, 0, s>>>(a);  // (+ the row index)
+        k_scan_rows<false, false><<<sgrid, kScanThreads, 0, s>>>(a);  // (+ the row index)
       }
       // packed output: the planes' start words (the rows' Golomb offsets stay slot-relative: gb_abs)
       // -- as the LEN scan's last workgroup instead, its device-scope release fences (an L2 write-back
@@ -2640,6 +2683,17 @@ void launch_fused(hipStream_t s, const Geom& g, const uint64_t* planes, const ui
       int occ = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64 * kEmitWaves, 0) != hipSuccess || occ < 1) occ = 4;
       return std::min(occ, 8);
+    };
+    // k_emit_k01's register bound (kK01Regs) as built: more registers, or any scratch, and k_emit_rest no
+    // longer fits beside it or its rows spill -- said once, since the streams stay right and only time is lost
+    auto k01_regs_checked = [](const void* fn) {
+      hipFuncAttributes fa{};
+      if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return false;
+      const bool ok = fa.numRegs <= kK01Regs && fa.localSizeBytes == 0;
+      if (!ok)
+        std::fprintf(stderr, "bic_fused.hip: k_emit_k01 was built with %d registers and %zu bytes of scratch (expected <= %d, 0)\n",
+                     fa.numRegs, (size_t)fa.localSizeBytes, kK01Regs);
+      return ok;
     };
     auto egrid_of = [&](int occ) {
       return (uint32_t)std::min<uint64_t>((nrows + kEmitWaves - 1) / kEmitWaves, (uint64_t)cus * (uint32_t)occ);
@@ -2676,6 +2730,8 @@ void launch_fused(hipStream_t s, const Geom& g, const uint64_t* planes, const ui
 #define BIC_EMITC(W)                                                                                      \
   {                                                                                                    \
     static const int o_ = occ_of(reinterpret_cast<const void*>(&k_emit_k01<W>));                      \
+    static const bool r_ = k01_regs_checked(reinterpret_cast<const void*>(&k_emit_k01<W>));           \
+    (void)r_;                                                                                          \
     k_emit_rest<false, true, false><<<rgrid, 64 * nwv, 0, rs>>>(a);                                    \
     main_ev(fs.ev_main0);                                                                              \
     k_emit_k01<W><<<egrid_of(o_), 256, 0, s>>>(a);                                                     \
