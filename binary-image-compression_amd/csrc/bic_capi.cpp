@@ -449,6 +449,23 @@ int bic_bitplanes_u8_range(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size
   return BIC_OK;
 }
 
+int bic_bitplanes_u16(bic_ctx* ctx, const void* gray, size_t pitch, size_t rows, size_t cols, int big_endian,
+                      int plane0, int nplanes, uint64_t* planes, size_t wpr) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (plane0 < 0 || nplanes < 1 || plane0 + nplanes > 16 || cols > SIZE_MAX / 2 || pitch < 2 * cols ||
+      (rows && (!gray || !planes)))
+    return BIC_EINVAL;
+  if (!geom_ok(rows, cols, wpr)) return BIC_EINVAL;
+  if (rows == 0) return BIC_OK;
+  timed(ctx, "bitplanes_u16", [&] {
+    bic::launch_raster_planes(ctx->cur, static_cast<const uint8_t*>(gray), 2, (uint32_t)rows, (uint32_t)cols, plane0,
+                              nplanes, planes, (uint32_t)wpr, (uint64_t)pitch, big_endian ? 1 : 0);
+  });
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
 int bic_bitplanes_u8(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size_t rows, size_t cols,
                      int nplanes, uint64_t* planes, size_t wpr) {
   return bic_bitplanes_u8_range(ctx, gray, pitch, rows, cols, 0, nplanes, planes, wpr);
@@ -617,13 +634,18 @@ int bic_encode_planes_packed(bic_ctx* ctx, const uint64_t* planes, int nplanes, 
                             off_golomb, out_eg, slot_eg, bits_eg, off_eg, row_index);
 }
 
-static int encode_gray_impl(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size_t rows, size_t cols, int plane0,
-                            int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
-                            size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
-                            size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index = nullptr) {
+// bps: bytes per sample -- 1 (bic_encode_gray*), or 2 (bic_encode_gray16*: big_endian = 1 the P5 order of
+// pnm.cpp:73, 0 the host's uint16_t). Only the count pass (and the fallback's plane extraction) knows
+// the sample size; everything after it is per (plane, row).
+static int encode_gray_impl(bic_ctx* ctx, const uint8_t* gray, int bps, int big_endian, size_t pitch, size_t rows,
+                            size_t cols, int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict,
+                            uint64_t* out_golomb, size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb,
+                            uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg,
+                            uint64_t* row_index = nullptr) {
   int rc = bind(ctx);
   if (rc) return rc;
-  if (plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 || pitch < cols || !geom_ok(rows, cols, wpr))
+  if (plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 * bps || cols > SIZE_MAX / 2 || pitch < cols * (size_t)bps ||
+      !geom_ok(rows, cols, wpr))
     return BIC_EINVAL;
   if (!out_golomb && !out_eg) return BIC_EINVAL;
   if (out_golomb && (!bits_golomb || slot_golomb == 0)) return BIC_EINVAL;
@@ -636,7 +658,7 @@ static int encode_gray_impl(bic_ctx* ctx, const uint8_t* gray, size_t pitch, siz
   const uint64_t eg_words = ((uint64_t)rows * (cols + 1) + 1 + 63) / 64;
   const bool fuse = rows && bic::fused_supported(g) && !ctx->force_multipass && !ctx->two_pass && !ctx->single_kernel &&
                     staged_pays(ctx, g) && bic::med_rows_supported(g, planes, nullptr) &&
-                    bic::gray_rows_supported(g, gray, pitch, planes);
+                    bic::gray_rows_supported(g, gray, pitch, planes, bps);
   const bool eg_src = fuse && !planes && predict && out_eg && !off_eg && bic::gray_eg_supported(g) &&
                       eg_words <= slot_eg && (out_golomb || !row_index) && !ctx->eg_src_off;
   if (!planes && rows && !eg_src) {
@@ -656,7 +678,9 @@ static int encode_gray_impl(bic_ctx* ctx, const uint8_t* gray, size_t pitch, siz
   const bool store_resid = !planes && predict;
   if (!planes && !eg_src) planes = ctx->rbuf;
   if (!fuse) {  // the same result through the two separate calls
-    if ((rc = bic_bitplanes_u8_range(ctx, gray, pitch, rows, cols, plane0, nplanes, planes, wpr))) return rc;
+    if ((rc = bps == 2 ? bic_bitplanes_u16(ctx, gray, pitch, rows, cols, big_endian, plane0, nplanes, planes, wpr)
+                       : bic_bitplanes_u8_range(ctx, gray, pitch, rows, cols, plane0, nplanes, planes, wpr)))
+      return rc;
     return encode_planes_impl(ctx, planes, nplanes, rows, cols, wpr, predict, out_golomb, slot_golomb, bits_golomb,
                               off_golomb, out_eg, slot_eg, bits_eg, off_eg, row_index);
   }
@@ -678,7 +702,7 @@ static int encode_gray_impl(bic_ctx* ctx, const uint8_t* gray, size_t pitch, siz
   stage(bic::kFusedPrep);
   timed(ctx, "bitplanes_count", [&] {
     bic::launch_gray_rows(ctx->cur, gray, pitch, g, predict ? 1 : 0, plane0, planes, fs.sones, fs.krec, fs.kpos,
-                          fs.counter, store_resid, eg_src ? out_eg : nullptr, slot_eg);
+                          fs.counter, store_resid, eg_src ? out_eg : nullptr, slot_eg, bps, big_endian);
   });
   timed(ctx, "encode_prefix", [&] { stage(bic::kFusedPrefix); });
   // (EG source: the emission is Golomb's alone, reading the residual rows from the EG stream)
@@ -695,8 +719,26 @@ int bic_encode_gray_range(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size_
                           int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
                           size_t slot_golomb, uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg,
                           uint64_t* bits_eg) {
-  return encode_gray_impl(ctx, gray, pitch, rows, cols, plane0, nplanes, planes, wpr, predict, out_golomb, slot_golomb,
-                          bits_golomb, nullptr, out_eg, slot_eg, bits_eg, nullptr);
+  return encode_gray_impl(ctx, gray, 1, 0, pitch, rows, cols, plane0, nplanes, planes, wpr, predict, out_golomb,
+                          slot_golomb, bits_golomb, nullptr, out_eg, slot_eg, bits_eg, nullptr);
+}
+
+int bic_encode_gray16(bic_ctx* ctx, const void* gray, size_t pitch, size_t rows, size_t cols, int big_endian,
+                      int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
+                      size_t slot_golomb, uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg) {
+  return encode_gray_impl(ctx, static_cast<const uint8_t*>(gray), 2, big_endian ? 1 : 0, pitch, rows, cols, plane0,
+                          nplanes, planes, wpr, predict, out_golomb, slot_golomb, bits_golomb, nullptr, out_eg, slot_eg,
+                          bits_eg, nullptr);
+}
+
+int bic_encode_gray16_packed(bic_ctx* ctx, const void* gray, size_t pitch, size_t rows, size_t cols, int big_endian,
+                             int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
+                             size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
+                             size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
+  if ((out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
+  return encode_gray_impl(ctx, static_cast<const uint8_t*>(gray), 2, big_endian ? 1 : 0, pitch, rows, cols, plane0,
+                          nplanes, planes, wpr, predict, out_golomb, slot_golomb, bits_golomb, off_golomb, out_eg,
+                          slot_eg, bits_eg, off_eg, row_index);
 }
 
 int bic_encode_gray_packed(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size_t rows, size_t cols, int plane0,
@@ -704,8 +746,8 @@ int bic_encode_gray_packed(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size
                            size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
                            size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
   if ((out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
-  return encode_gray_impl(ctx, gray, pitch, rows, cols, plane0, nplanes, planes, wpr, predict, out_golomb, slot_golomb,
-                          bits_golomb, off_golomb, out_eg, slot_eg, bits_eg, off_eg, row_index);
+  return encode_gray_impl(ctx, gray, 1, 0, pitch, rows, cols, plane0, nplanes, planes, wpr, predict, out_golomb,
+                          slot_golomb, bits_golomb, off_golomb, out_eg, slot_eg, bits_eg, off_eg, row_index);
 }
 
 int bic_row_index(bic_ctx* ctx, const uint64_t* planes, int nplanes, size_t rows, size_t cols, size_t wpr,

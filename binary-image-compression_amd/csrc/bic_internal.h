@@ -187,15 +187,17 @@ void launch_row_ones(hipStream_t s, const Geom& g, const uint64_t* planes, int p
                      int4* krec, uint32_t* kpos, uint32_t* zero);
 // bitplanes + the count pass in one read of the gray image (bic_encode_gray); gray_strips(g)
 // k statistics records per row (one per 64-word strip)
-bool gray_rows_supported(const Geom& g, const void* gray, size_t pitch, const void* planes);
+bool gray_rows_supported(const Geom& g, const void* gray, size_t pitch, const void* planes, int bps = 1);
 uint32_t gray_strips(const Geom& g);
 // store_resid: the words stored are the med residual R (planes = the caller's bitplanes are not
 // wanted; the encoder then reads R with predict off), not the bitplanes P. out_e (with predict, the
 // bitplanes not wanted): the EG stream instead of R (FusedScratch::eg_src; slots of eg_stride
-// words); planes is then unused
+// words); planes is then unused. bps = 2 (bic_encode_gray16): samples of two bytes, big-endian
+// (pnm.cpp:71-74) or the host's order, planes plane0 .. of 16 (k_gray_strips16)
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero,
-                      bool store_resid = false, uint64_t* out_e = nullptr, uint64_t eg_stride = 0);
+                      bool store_resid = false, uint64_t* out_e = nullptr, uint64_t eg_stride = 0, int bps = 1,
+                      int big_endian = 0);
 // the count pass can write the EG stream (FusedScratch::eg_src): rows of whole 64-word strips only
 bool gray_eg_supported(const Geom& g);
 
@@ -240,9 +242,10 @@ void launch_match_code(hipStream_t s, const MatchArgs& a, unsigned long long* ou
                        size_t cap_words, uint64_t* stats);
 void launch_pbm(hipStream_t s, bool pack, const uint8_t* raster_in, uint8_t* raster_out, const uint64_t* plane_in,
                 uint64_t* plane_out, uint32_t rows, uint32_t cols, uint32_t wpr);
-// P5 samples (1 or 2 bytes, any alignment) -> planes plane0.. (bic_raster.hip)
+// P5 samples (1 or 2 bytes, any alignment) -> planes plane0.. (bic_raster.hip); pitch: bytes per row
+// (0: cols * bpp, a P5 raster); big_endian: the order of two-byte samples (1: pnm.cpp:73)
 void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_t rows, uint32_t cols, int plane0,
-                          int nplanes, uint64_t* planes, uint32_t wpr);
+                          int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch = 0, int big_endian = 1);
 void launch_planes_gray(hipStream_t s, const uint64_t* planes, uint32_t rows, uint32_t cols, uint32_t wpr, int plane0,
                         int nplanes, int bps, uint8_t* gray, uint64_t pitch);
 

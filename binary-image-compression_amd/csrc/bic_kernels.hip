@@ -594,12 +594,23 @@ __device__ __forceinline__ void load64_mis(const uint8_t* src, uint4 (&v)[4]) {
 #undef BIC_MIS_CASE
 }
 
-template <bool PREDICT, bool FULL, bool STORE_R, bool NP8, bool EGS, bool MIS = false>
+// 64 two-byte samples (128 bytes) of a lane: the row's and the row above's, loaded once for both
+// byte groups (k_gray_strips16, one wave per (row, strip))
+struct Raw16 {
+  uint4 cur[8], up[8];
+};
+
+// S16 (k_gray_strips16): two-byte samples, the wave takes ONE byte of each -- byte bo (0 or 1, wave-
+// uniform) of the sample, the low or the high one by the byte order -- and from there works as on an
+// 8-bit image: a lane's 64 pixels are 128 bytes, v_perm_b32 keeps the 64 it needs.
+// (S16 = 2: the samples of rows r0 - 1 and r0 come preloaded in `pre`, one row per wave)
+template <bool PREDICT, bool FULL, bool STORE_R, bool NP8, bool EGS, bool MIS = false, int S16 = 0>
 __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray, size_t pitch, const Geom& g,
                                                 uint32_t ns, uint32_t s, uint32_t r0, uint32_t plane0,
                                                 uint64_t* __restrict__ planes, uint32_t* __restrict__ sones,
                                                 int4* __restrict__ krec, uint32_t* __restrict__ kpos, uint32_t* tw,
-                                                uint64_t* __restrict__ out_e, uint64_t eg_stride) {
+                                                uint64_t* __restrict__ out_e, uint64_t eg_stride, uint32_t bo = 0,
+                                                const Raw16* pre = nullptr) {
   const int lane = lane_id();
   const int np = NP8 ? 8 : (int)g.nplanes;
   const uint32_t w = s * 64 + lane;
@@ -607,8 +618,35 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
   const uint64_t mask = FULL ? ~0ull : in ? (w == g.used - 1 ? g.trail : ~0ull) : 0ull;
   // the word's 64 pixels, and (lane 0 of strips s > 0) the pixel before the strip
   auto load = [&](uint32_t row, uint4 (&v)[4], uint32_t& lb) {
-    const uint8_t* src = gray + (uint64_t)row * pitch + (uint64_t)w * 64;
-    if constexpr (MIS) {
+    const uint8_t* src = gray + (uint64_t)row * pitch + (uint64_t)w * (S16 ? 128 : 64);
+    if constexpr (S16) {
+      uint4 c[8];  // the 64 samples
+      if constexpr (S16 == 2) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) c[q] = row == r0 ? pre->cur[q] : pre->up[q];  // (wave-uniform)
+      } else if (in) {
+        if constexpr (MIS) {
+          uint4 a[4], b[4];
+          load64_mis(src, a);
+          load64_mis(src + 64, b);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) c[q] = a[q], c[4 + q] = b[q];
+        } else {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) c[q] = reinterpret_cast<const uint4*>(src)[q];
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) c[q] = make_uint4(0, 0, 0, 0);
+      }
+      // byte bo of four samples (two dwords) -> one dword (k_raster_planes<2>'s selectors)
+      const uint32_t sel = bo ? 0x07050301u : 0x06040200u;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        v[q] = make_uint4(__builtin_amdgcn_perm(c[2 * q].y, c[2 * q].x, sel), __builtin_amdgcn_perm(c[2 * q].w, c[2 * q].z, sel),
+                          __builtin_amdgcn_perm(c[2 * q + 1].y, c[2 * q + 1].x, sel),
+                          __builtin_amdgcn_perm(c[2 * q + 1].w, c[2 * q + 1].z, sel));
+    } else if constexpr (MIS) {
       if (in) load64_mis(src, v);
       else
 #pragma unroll
@@ -617,7 +655,8 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = in ? reinterpret_cast<const uint4*>(src)[q] : make_uint4(0, 0, 0, 0);
     }
-    lb = (lane == 0 && s > 0) ? (uint32_t)src[-1] : 0u;
+    if constexpr (S16) lb = (lane == 0 && s > 0) ? (uint32_t)src[(int)bo - 2] : 0u;  // the sample before the strip
+    else lb = (lane == 0 && s > 0) ? (uint32_t)src[-1] : 0u;
     if (plane0) {  // planes plane0.. of the range: every pixel's bits shifted down (a wave-uniform branch)
       const uint32_t m = 0x01010101u * (0xffu >> plane0);
 #pragma unroll
@@ -658,7 +697,8 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
     const uint32_t rn = lastS ? row + 1 : row;
     uint32_t gn = 0;
     if (EGS && FULL && rn < g.rows) {
-      const uint8_t* cp = gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 4096u) + lane;
+      const uint8_t* cp = S16 ? gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 8192u) + 2 * lane + bo
+                              : gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 4096u) + lane;
       uint32_t cb = cp[0], ub = rn ? cp[-(int64_t)pitch] : 0u;
       gn = (cb ^ ub) >> plane0;
     }
@@ -789,27 +829,117 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips(const ui
                                                                 kpos, tw, nullptr, 0);
 }
 
+// Two-byte samples (bic_encode_gray16; pnm.cpp:71-74 big-endian, or the host's uint16_t). The planes
+// plane0 .. of the call split into the low byte's (plane0 .. 7, the outputs' first nlo planes) and the
+// high byte's (the rest); gray_strip_rows runs once per group on that byte of every sample, its plane-
+// indexed outputs advanced by nlo for the high group. Two layouts (DESIGN.md §3, 16-bit gray):
+//  * byte-domain med on 16-byte aligned rows (BOTH): one wave per (row, strip) loads the row's and the
+//    row above's 128 bytes per lane once and runs the groups one after the other, reusing its LDS
+//    table (every row of gray_strip_rows ends with a wave fence + wave_barrier);
+//  * otherwise (planes returned, no prediction, misaligned rows): one wave per (row block, strip, byte
+//    group); the two groups of a strip are neighbouring waves of one workgroup, both load the same 128
+//    bytes per lane (the second from L1 / L2) and keep their own 64.
+#ifndef BIC_GRAY16_BOTH
+#define BIC_GRAY16_BOTH 1
+#endif
+constexpr bool kGray16Both = BIC_GRAY16_BOTH != 0 && kGrayByteMed && kGrayRowsBM == 1;
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false>
+__global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips16(const uint8_t* __restrict__ gray, size_t pitch, Geom g,
+                                                          uint32_t ns, uint32_t plane0, uint32_t be,
+                                                          uint64_t* __restrict__ planes, uint32_t* __restrict__ sones,
+                                                          int4* __restrict__ krec, uint32_t* __restrict__ kpos,
+                                                          uint32_t* __restrict__ zero, uint64_t* __restrict__ out_e,
+                                                          uint64_t eg_stride) {
+  __shared__ __attribute__((aligned(16))) uint32_t tab[kWaves][1024];  // strip_word_put tables
+  if (blockIdx.x == 0 && threadIdx.x < kZeroWords) zero[threadIdx.x] = 0;  // the encoder's counters
+  const uint32_t wv = wave_id();
+  uint32_t* tw = tab[wv];
+  const uint32_t nlo = plane0 < 8 ? min(8u, plane0 + g.nplanes) - plane0 : 0u, nhi = g.nplanes - nlo;
+  const uint32_t ngrp = nlo && nhi ? 2u : 1u;
+  constexpr bool BOTH = kGray16Both && PREDICT && STORE_R && !MIS;  // the wave runs both groups
+  constexpr int S = BOTH ? 2 : 1;
+  const uint32_t wgrp = BOTH ? 1u : ngrp;
+  const uint64_t gw = (uint64_t)xcd_remap(blockIdx.x, gridDim.x) * kWaves + wv;
+  const uint32_t hi = nlo ? (uint32_t)(gw % wgrp) : 1u;  // the wave's byte group
+  const uint64_t gs = gw / wgrp;
+  const uint32_t s = (uint32_t)(gs % ns);
+  const uint32_t r0 = (uint32_t)(gs / ns) * gray_rows_per_wave<PREDICT, STORE_R>();
+  if (r0 >= g.rows) return;  // whole wave
+  Raw16 raw;
+  if constexpr (BOTH) {
+    const uint32_t w = s * 64 + lane_id();
+    const uint8_t* src = gray + (uint64_t)r0 * pitch + (uint64_t)w * 128;
+    const bool in = w < g.used;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) raw.cur[q] = raw.up[q] = make_uint4(0, 0, 0, 0);
+    if (in) {  // (the row, then the row above: eight 16-byte loads each)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) raw.cur[q] = reinterpret_cast<const uint4*>(src)[q];
+    }
+    if (in && r0) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) raw.up[q] = reinterpret_cast<const uint4*>(src - pitch)[q];
+    }
+  }
+  auto group = [&](uint32_t h) __attribute__((always_inline)) {
+    Geom gg = g;
+    gg.nplanes = h ? nhi : nlo;
+    const uint32_t p0 = h ? max(8u, plane0) - 8u : plane0;  // the group's first plane within its byte
+    const uint32_t skip = h ? nlo : 0u;                     // output planes before the group's
+    const uint32_t bo = h ^ (be ? 1u : 0u);                 // the group's byte of a sample (big-endian: high first)
+    const uint64_t rskip = (uint64_t)skip * g.rows * ns;
+    uint64_t* pl = planes + (uint64_t)skip * g.plane_words;
+    uint64_t* oe = out_e + (uint64_t)skip * eg_stride;
+    if ((s + 1) * 64 <= g.used && g.trail == ~0ull && gg.nplanes == 8)
+      gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, S>(gray, pitch, gg, ns, s, r0, p0, pl, sones + rskip,
+                                                                 krec + rskip, kpos + rskip, tw, oe, eg_stride, bo, &raw);
+    else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
+      gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, S>(gray, pitch, gg, ns, s, r0, p0, pl, sones + rskip,
+                                                                  krec + rskip, kpos + rskip, tw, oe, eg_stride, bo, &raw);
+    else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
+      gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, S>(gray, pitch, gg, ns, s, r0, p0, pl, sones + rskip,
+                                                                     krec + rskip, kpos + rskip, tw, nullptr, 0, bo,
+                                                                     &raw);
+  };
+  if constexpr (BOTH) {  // (the LDS table reused: gray_strip_rows ends every row with a wave fence + barrier)
+    if (nlo) group(0);
+    if (nhi) group(1);
+  } else {
+    group(hi);
+  }
+}
+
 bool gray_eg_supported(const Geom& g) { return g.trail == ~0ull && g.used % 64 == 0 && g.used / 64 <= kMaxStrips; }
 
 // any gray alignment and pitch (rows not 16-byte aligned: load64_mis); every row must hold used * 64
-// readable bytes
-bool gray_rows_supported(const Geom& g, const void* gray, size_t pitch, const void* planes) {
+// readable samples (of bps bytes)
+bool gray_rows_supported(const Geom& g, const void* gray, size_t pitch, const void* planes, int bps) {
   (void)gray;
-  return g.used <= 256 && pitch >= (size_t)g.used * 64 && reinterpret_cast<uintptr_t>(planes) % 8 == 0;
+  return g.used <= 256 && pitch >= (size_t)g.used * 64 * bps && reinterpret_cast<uintptr_t>(planes) % 8 == 0;
 }
 
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero, bool store_resid,
-                      uint64_t* out_e, uint64_t eg_stride) {
+                      uint64_t* out_e, uint64_t eg_stride, int bps, int big_endian) {
   const uint32_t ns = gray_strips(g);
   const uint32_t rpw = predict && store_resid ? gray_rows_per_wave<true, true>() : gray_rows_per_wave<true, false>();
   const uint64_t units = (uint64_t)(g.rows + rpw - 1) / rpw;  // row groups per strip
-  const uint32_t grid = (uint32_t)((units * ns + kWaves - 1) / kWaves);
+  // (two-byte samples: a wave per byte group that holds planes of the range)
   const bool mis = pitch % 16 != 0 || reinterpret_cast<uintptr_t>(gray) % 16 != 0;  // e.g. a P5 raster in its file
+  const bool both = kGray16Both && predict && store_resid && !mis;  // one wave runs both groups
+  const uint32_t ngrp = bps == 2 && !both && plane0 < 8 && plane0 + (int)g.nplanes > 8 ? 2u : 1u;
+  const uint32_t grid = (uint32_t)((units * ns * ngrp + kWaves - 1) / kWaves);
   const bool egs = out_e && predict && store_resid && gray_eg_supported(g);
-#define BIC_GS(P, R, E, M) \
-  k_gray_strips<P, R, E, M><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes, sones, krec, kpos, \
-                                                    zero, out_e, eg_stride)
+#define BIC_GS(P, R, E, M)                                                                                         \
+  do {                                                                                                             \
+    if (bps == 2)                                                                                                  \
+      k_gray_strips16<P, R, E, M><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0,                    \
+                                                          big_endian ? 1u : 0u, planes, sones, krec, kpos, zero,   \
+                                                          out_e, eg_stride);                                       \
+    else                                                                                                           \
+      k_gray_strips<P, R, E, M><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes, sones, krec, \
+                                                        kpos, zero, out_e, eg_stride);                             \
+  } while (0)
 #define BIC_GS2(P, R) { if (mis) BIC_GS(P, R, false, true); else BIC_GS(P, R, false, false); }
   if (egs) { if (mis) BIC_GS(true, true, true, true); else BIC_GS(true, true, true, false); }
   else if (predict) { if (store_resid) BIC_GS2(true, true) else BIC_GS2(true, false) }

@@ -79,18 +79,21 @@ __global__ __launch_bounds__(256) void k_pbm_pack2(const uint64_t* __restrict__ 
 // P5 samples (BPP = 1 or 2 bytes) -> planes plane0 .. plane0 + nplanes - 1. Lane = output word w
 // of a row (64 samples); 16 (BPP 1) or 32 (BPP 2) aligned loads, the 8 x 8 bit transposes of
 // k_bitplanes_u8 per byte column.
+// Rows of `pitch` bytes (a P5 raster: cols * BPP); selL / selH: the v_perm_b32 selectors of a two-byte
+// sample's low and high bytes (wave-uniform: big-endian or the host's order).
 template <int BPP>
 __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict__ base, uint32_t off, uint32_t rows,
                                                        uint32_t cols, int plane0, int nplanes,
-                                                       uint64_t* __restrict__ planes, uint32_t wpr) {
+                                                       uint64_t* __restrict__ planes, uint32_t wpr, uint64_t pitch,
+                                                       uint32_t selL, uint32_t selH) {
   const uint32_t groups = (cols + 4095) / 4096;  // 64-word groups per row
   const uint64_t gw = (uint64_t)blockIdx.x * 4 + wave_id();
   if (gw >= (uint64_t)rows * groups) return;
   const uint32_t row = (uint32_t)(gw / groups), w = (uint32_t)(gw % groups) * 64 + lane_id();
   const uint32_t used = (cols + 63) / 64;
   if (w >= used) return;
-  const uint64_t end = off + (uint64_t)rows * cols * BPP;
-  const uint64_t p0 = off + ((uint64_t)row * cols + 64ull * w) * BPP;
+  const uint64_t end = off + (uint64_t)(rows - 1) * pitch + (uint64_t)cols * BPP;
+  const uint64_t p0 = off + (uint64_t)row * pitch + 64ull * w * BPP;
   uint64_t lo8[8], hi8[8];  // per group of 8 samples: the low / high bytes, little-endian
 #pragma unroll
   for (int g = 0; g < 8; ++g) {
@@ -100,10 +103,11 @@ __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict
     } else {
       const uint64_t a = bytes8(base, p0 + 16 * g, end), b = bytes8(base, p0 + 16 * g + 8, end);
       // sample = (byte 2k << 8) + byte 2k+1 (pnm.cpp:73): odd bytes are the low ones
-      lo8[g] = ((uint64_t)__builtin_amdgcn_perm((uint32_t)(b >> 32), (uint32_t)b, 0x07050301u) << 32) |
-               __builtin_amdgcn_perm((uint32_t)(a >> 32), (uint32_t)a, 0x07050301u);
-      hi8[g] = ((uint64_t)__builtin_amdgcn_perm((uint32_t)(b >> 32), (uint32_t)b, 0x06040200u) << 32) |
-               __builtin_amdgcn_perm((uint32_t)(a >> 32), (uint32_t)a, 0x06040200u);
+      // (selL = 0x07050301, selH = 0x06040200; the host's little-endian order swaps them)
+      lo8[g] = ((uint64_t)__builtin_amdgcn_perm((uint32_t)(b >> 32), (uint32_t)b, selL) << 32) |
+               __builtin_amdgcn_perm((uint32_t)(a >> 32), (uint32_t)a, selL);
+      hi8[g] = ((uint64_t)__builtin_amdgcn_perm((uint32_t)(b >> 32), (uint32_t)b, selH) << 32) |
+               __builtin_amdgcn_perm((uint32_t)(a >> 32), (uint32_t)a, selH);
     }
   }
   const uint32_t valid = min(64u, cols - 64 * w);
@@ -214,14 +218,20 @@ void launch_pbm(hipStream_t s, bool pack, const uint8_t* raster_in, uint8_t* ras
 }
 
 void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_t rows, uint32_t cols, int plane0,
-                          int nplanes, uint64_t* planes, uint32_t wpr) {
+                          int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch, int big_endian) {
   const uintptr_t r = reinterpret_cast<uintptr_t>(raster);
+  if (!pitch) pitch = (uint64_t)cols * bpp;
+  const uint32_t selL = big_endian ? 0x07050301u : 0x06040200u, selH = big_endian ? 0x06040200u : 0x07050301u;
   const uint8_t* base = reinterpret_cast<const uint8_t*>(r & ~(uintptr_t)7);
   const uint64_t waves = (uint64_t)rows * ((cols + 4095) / 4096);
   const uint32_t grid = (uint32_t)((waves + 3) / 4);
   if (!grid) return;
-  if (bpp == 1) k_raster_planes<1><<<grid, 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr);
-  else k_raster_planes<2><<<grid, 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr);
+  if (bpp == 1)
+    k_raster_planes<1><<<grid, 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr, pitch,
+                                            selL, selH);
+  else
+    k_raster_planes<2><<<grid, 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr, pitch,
+                                            selL, selH);
 }
 
 }  // namespace bic

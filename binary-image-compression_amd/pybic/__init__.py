@@ -30,6 +30,7 @@ EXPORTS = [
     "bic_bitplanes_u8_range", "bic_encode_gray_range", "bic_encode_planes_packed", "bic_encode_gray_packed",
     "bic_row_index", "bic_decode_planes", "bic_pgm_bitplanes", "bic_pnm_parse_header",
     "bic_gf2_transpose", "bic_gf2_mul", "bic_planes_to_gray", "bic_match_encode_inv", "bic_match_encode_var", "bic_egad_row_index",
+    "bic_encode_gray16", "bic_encode_gray16_packed", "bic_bitplanes_u16",
 ]
 
 # bic_gf2_mul ops (include/bic.h)
@@ -120,6 +121,10 @@ def load(path=LIB_PATH):
     sig("bic_gf2_transpose", i32, [vp, vp, sz, sz, sz, vp, sz])
     sig("bic_gf2_mul", i32, [vp, i32, vp, sz, sz, sz, vp, sz, sz, sz, vp, sz, sz, sz])
     sig("bic_planes_to_gray", i32, [vp, vp, i32, i32, sz, sz, sz, i32, vp, sz])
+    sig("bic_bitplanes_u16", i32, [vp, vp, sz, sz, sz, i32, i32, i32, vp, sz])
+    sig("bic_encode_gray16", i32, [vp, vp, sz, sz, sz, i32, i32, i32, vp, sz, i32, vp, sz, vp, vp, sz, vp])
+    sig("bic_encode_gray16_packed", i32, [vp, vp, sz, sz, sz, i32, i32, i32, vp, sz, i32, vp, sz, vp, vp, vp, sz, vp,
+                                          vp, vp])
     _lib = L
     return L
 
@@ -343,6 +348,70 @@ class Context:
         self._chk(self.lib.bic_encode_gray_packed(self.h, _p(gray), pitch, rows, cols, plane0, nplanes, _p(planes), wpr,
                                                   int(predict), _p(og), sg, _p(bg), _p(fg), _p(oe), se, _p(be),
                                                   _p(fe), _p(row_index)), "bic_encode_gray_packed")
+        return planes, ((og, bg, fg) if golomb else None), ((oe, be, fe) if eg else None)
+
+    def _gray16_args(self, gray, rows, cols, pitch):
+        """gray: 2-D uint16 / int16 tensor [rows, >= cols] (pitch = stride(0) * 2 bytes), or a uint8 tensor of
+        raster bytes starting at the first sample with rows, cols (and pitch, default 2 * cols) given"""
+        t = self.torch
+        if gray.dtype in (getattr(t, "uint16", t.int16), t.int16):
+            assert gray.dim() == 2 and gray.stride(1) == 1
+            return gray.shape[0], (gray.shape[1] if cols is None else cols), gray.stride(0) * 2
+        assert gray.dtype == t.uint8 and rows is not None and cols is not None
+        return rows, cols, (2 * cols if pitch is None else pitch)
+
+    def bitplanes_u16(self, gray, cols=None, nplanes=16, plane0=0, big_endian=False, wpr=None, out=None, rows=None,
+                      pitch=None):
+        """bic_bitplanes_u16: two-byte samples -> int64 tensor [nplanes, rows, wpr] (planes plane0 ..)"""
+        rows, cols, pitch = self._gray16_args(gray, rows, cols, pitch)
+        wpr = wpr or (cols + 63) // 64
+        out = self.empty_i64(nplanes, rows, wpr) if out is None else out
+        self._bind_stream()
+        self._chk(self.lib.bic_bitplanes_u16(self.h, _p(gray), pitch, rows, cols, int(big_endian), plane0, nplanes,
+                                             _p(out), wpr), "bic_bitplanes_u16")
+        return out
+
+    def encode_gray16(self, gray, cols=None, nplanes=16, plane0=0, big_endian=False, predict=True, planes=None,
+                      slots=(None, None), outs=(None, None), bits=(None, None), golomb=True, eg=True,
+                      store_planes=True, rows=None, pitch=None):
+        """bic_encode_gray16 -> (planes, (out_g, bits_g) or None, (out_e, bits_e) or None), as encode_gray
+        for two-byte samples (gray: see _gray16_args; big_endian: the P5 order, else the host's)."""
+        rows, cols, pitch = self._gray16_args(gray, rows, cols, pitch)
+        wpr = (cols + 63) // 64
+        if planes is None and store_planes:
+            planes = self.empty_i64(nplanes, rows, wpr)
+        wpr = planes.shape[-1] if planes is not None else wpr
+        res = []
+        for on, coder, slot, out, b in ((golomb, CODER_GOLOMB, slots[0], outs[0], bits[0]),
+                                        (eg, CODER_EG, slots[1], outs[1], bits[1])):
+            if not on:
+                res.append((None, 0, None))
+                continue
+            slot = slot or self.slot_words(rows, cols, coder)
+            out = self.empty_i64(nplanes, slot) if out is None else out
+            b = self.empty_i64(nplanes) if b is None else b
+            res.append((out, slot, b))
+        (og, sg, bg), (oe, se, be) = res
+        self._bind_stream()
+        self._chk(self.lib.bic_encode_gray16(self.h, _p(gray), pitch, rows, cols, int(big_endian), plane0, nplanes,
+                                             _p(planes), wpr, int(predict), _p(og), sg, _p(bg), _p(oe), se, _p(be)),
+                  "bic_encode_gray16")
+        return planes, ((og, bg) if golomb else None), ((oe, be) if eg else None)
+
+    def encode_gray16_packed(self, gray, cols=None, nplanes=16, plane0=0, big_endian=False, predict=True, planes=None,
+                             golomb=True, eg=True, slots=(None, None), outs=(None, None), bits=(None, None),
+                             offs=(None, None), row_index=None, store_planes=True, rows=None, pitch=None):
+        """bic_encode_gray16_packed -> (planes, (out_g, bits_g, off_g) or None, (out_e, bits_e, off_e) or None)"""
+        rows, cols, pitch = self._gray16_args(gray, rows, cols, pitch)
+        if planes is None and store_planes:
+            planes = self.empty_i64(nplanes, rows, (cols + 63) // 64)
+        wpr = planes.shape[-1] if planes is not None else (cols + 63) // 64
+        (og, sg, bg, fg), (oe, se, be, fe) = self._packed_bufs(nplanes, rows, cols, golomb, eg, slots, outs, bits, offs)
+        self._bind_stream()
+        self._chk(self.lib.bic_encode_gray16_packed(self.h, _p(gray), pitch, rows, cols, int(big_endian), plane0,
+                                                    nplanes, _p(planes), wpr, int(predict), _p(og), sg, _p(bg), _p(fg),
+                                                    _p(oe), se, _p(be), _p(fe), _p(row_index)),
+                  "bic_encode_gray16_packed")
         return planes, ((og, bg, fg) if golomb else None), ((oe, be, fe) if eg else None)
 
     def row_index(self, planes, cols, predict=True, out=None):

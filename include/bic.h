@@ -109,6 +109,13 @@ int bic_bitplanes_u8(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size_t row
  * plane-sharded encode extracts its own share of one image this way. */
 int bic_bitplanes_u8_range(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size_t rows, size_t cols, int plane0,
                            int nplanes, uint64_t* planes, size_t wpr);
+/* The same for samples of two bytes (pnm.cpp:71-74: a P5 sample with maxval >= 256 is (hi << 8) + lo,
+ * high byte first; bitplane_tool.cpp:24-30 then extracts up to 16 planes): gray = rows of cols samples
+ * with row pitch `pitch` in BYTES (>= 2 * cols), device memory of any byte alignment (pitch too).
+ * big_endian = 1: the P5 order; 0: the host's uint16_t. Output plane b is bit plane0 + b of each
+ * sample, plane0 + nplanes <= 16. bic_pgm_bitplanes with a row pitch and a choice of byte order. */
+int bic_bitplanes_u16(bic_ctx* ctx, const void* gray, size_t pitch, size_t rows, size_t cols, int big_endian,
+                      int plane0, int nplanes, uint64_t* planes, size_t wpr);
 
 /* ---- a5/a6: med residual + weight (pred.cpp:3-15, binmat.cpp:57-67) -----------------------
  * resid (nullable): the med residual of each plane (R(0,0) = 0 and pad bits 0, which is what
@@ -173,6 +180,27 @@ int bic_encode_gray_packed(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size
                            int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
                            size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
                            size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index);
+/* bic_encode_gray_range / bic_encode_gray_packed for samples of two bytes (pnm.cpp:71-74; the planes
+ * bitplane_tool.cpp:24-30 extracts from a P5 file with maxval >= 256): gray = rows of cols samples, row
+ * pitch `pitch` in BYTES (>= 2 * cols), any byte alignment of gray and pitch (odd included: a P5 raster
+ * where it lies in its file's bytes). big_endian = 1: the P5 order, high byte first; 0: the host's
+ * uint16_t. Planes plane0 .. plane0 + nplanes - 1 of the 16 (plane0 + nplanes <= 16; a range may cross
+ * the byte boundary); outputs, nullable arguments, errors and domain as for the 8-bit calls, the
+ * results bit-identical to bic_bitplanes_u16 (bic_pgm_bitplanes) followed by bic_encode_planes2 /
+ * bic_encode_planes_packed. Bitplane extraction and med are linear over XOR, so planes 0-7 are the
+ * 8-bit pipeline on the samples' low bytes and planes 8-15 the same on their high bytes: rows of up to
+ * 16384 columns whose gray rows hold ceil(cols/64)*128 readable bytes read the image once (with planes
+ * NULL, predict and the EG stream into slots the count pass writes the EG stream itself, as for
+ * bic_encode_gray); otherwise the same result through the two separate calls. The device round trip of
+ * a 16-bit image is gray -> bic_encode_gray16_packed -> bic_decode_planes -> bic_planes_to_gray
+ * (sample_bytes = 2). */
+int bic_encode_gray16(bic_ctx* ctx, const void* gray, size_t pitch, size_t rows, size_t cols, int big_endian,
+                      int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
+                      size_t slot_golomb, uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg);
+int bic_encode_gray16_packed(bic_ctx* ctx, const void* gray, size_t pitch, size_t rows, size_t cols, int big_endian,
+                             int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
+                             size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
+                             size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index);
 
 /* ---- f1: decoders on the device (GolombDecoder.cpp:15-23 read order, eg.cpp:20-37 as written) --
  * row_index (device, nplanes * rows * 2 u64; nullable in the encoders above): per row of each plane,
