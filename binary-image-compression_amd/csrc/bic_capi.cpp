@@ -11,7 +11,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <new>
 #include <string>
@@ -107,11 +106,12 @@ bool prof_wants(bic_ctx* ctx, const char* name) {
   return ctx->prof_on && (ctx->prof_only.empty() || ctx->prof_only == name);
 }
 
-// The staged encoder's emission stage: `name` times its main kernel alone (events the launch records
-// on its own stream right around that kernel, FusedScratch::ev_main*: the roofline kernel's launch
-// duration), "<name>_stage" the whole stage, the second stream's fork and join included.
+// The row encoders' emission stage: `name` times the staged encoder's main kernel alone (events the
+// launch records on its own stream right around that kernel, EmitStreams::main*: the roofline
+// kernel's launch duration), "<name>_stage" the whole stage, the second stream's fork and join included.
 template <typename F>
-void timed_rows(bic_ctx* ctx, bic::FusedScratch& fs, const char* name, F&& launch) {
+void timed_rows(bic_ctx* ctx, bic::EmitStreams& es, const char* name, F&& launch) {
+  if (!ctx->prof_on) return launch();
   const std::string stage_name = std::string(name) + "_stage";
   const bool k = prof_wants(ctx, name), st = prof_wants(ctx, stage_name.c_str());
   hipEvent_t a = nullptr, b = nullptr, sa = nullptr, sb = nullptr;
@@ -122,9 +122,9 @@ void timed_rows(bic_ctx* ctx, bic::FusedScratch& fs, const char* name, F&& launc
     // (recorded here too: a path without a separate main kernel -- the single and two-pass encoders --
     // then times the whole stage, b recorded below)
     (void)hipEventRecord(a, ctx->cur);
-    fs.ev_main0 = a;
-    fs.ev_main1 = b;
-    fs.ev_main_rec = &main_rec;
+    es.main0 = a;
+    es.main1 = b;
+    es.main_rec = &main_rec;
   }
   if (st) {
     sa = take_event(ctx);
@@ -139,11 +139,7 @@ void timed_rows(bic_ctx* ctx, bic::FusedScratch& fs, const char* name, F&& launc
     (void)hipEventRecord(sb, ctx->cur);
     ctx->recs.push_back({stage_name, sa, sb});
   }
-  if (k) {
-    fs.ev_main0 = fs.ev_main1 = nullptr;
-    fs.ev_main_rec = nullptr;
-    ctx->recs.push_back({name, a, b});
-  }
+  if (k) ctx->recs.push_back({name, a, b});
 }
 
 // Runs one launch, bracketed by events when profiling is on.
@@ -186,12 +182,8 @@ int ensure_scratch(bic_ctx* ctx, size_t bytes) {
 
 // The staged encoder's second stream and its fork / join events, made on first use; left null
 // (one stream) when HIP cannot make them. Work on it is always joined back into ctx->cur.
-void set_aux(bic_ctx* ctx, bic::FusedScratch& fs) {
-  if (ctx->one_stream) {
-    fs.aux = nullptr;
-    fs.ev_fork = fs.ev_join = nullptr;
-    return;
-  }
+void set_aux(bic_ctx* ctx, bic::EmitStreams& es) {
+  if (ctx->one_stream) return;
   if (!ctx->aux) {
     hipStream_t st = nullptr;
     hipEvent_t a = nullptr, b = nullptr;
@@ -214,9 +206,9 @@ void set_aux(bic_ctx* ctx, bic::FusedScratch& fs) {
     ctx->ev_fork = a;
     ctx->ev_join = b;
   }
-  fs.aux = ctx->aux;
-  fs.ev_fork = ctx->ev_fork;
-  fs.ev_join = ctx->ev_join;
+  es.aux = ctx->aux;
+  es.fork = ctx->ev_fork;
+  es.join = ctx->ev_join;
 }
 
 // The staged encoder's ~8 dependent launches cost more than the single kernel's look-back waits
@@ -498,169 +490,165 @@ size_t bic_encode_slot_words(size_t rows, size_t cols, int coder) {
   return (size_t)((2 * base + 63) / 64 + 64);
 }
 
+extern "C++" {
 namespace {
+// nplanes planes of rows x cols pixels, wpr words per row
+struct Shape {
+  int nplanes;
+  size_t rows, cols, wpr;
+};
+// bps: bytes per sample -- 1 (bic_encode_gray*), or 2 (bic_encode_gray16*: big_endian = 1 the P5 order of
+// pnm.cpp:73, 0 the host's uint16_t)
+struct GrayImage {
+  const uint8_t* data;
+  size_t pitch;
+  int bps, big_endian;
+};
+
 // Packed output where the encoder cannot write it in place (encoders other than the staged one, the
 // multi-pass path): ONE encode of both coders into slots in stream-ordered temporaries, then
 // bic_pack_streams' kernel once per coder.
-int pack_after(bic_ctx* ctx, int nplanes, uint64_t* out_g, size_t slot_g, uint64_t* bits_g, uint64_t* off_g,
-               uint64_t* out_e, size_t slot_e, uint64_t* bits_e, uint64_t* off_e,
-               const std::function<int(uint64_t*, uint64_t*)>& encode) {
-  uint64_t *tg = nullptr, *te = nullptr;
-  if (out_g) BIC_HIP(hipMallocAsync(reinterpret_cast<void**>(&tg), (size_t)nplanes * slot_g * 8, ctx->cur));
-  if (out_e && hipMallocAsync(reinterpret_cast<void**>(&te), (size_t)nplanes * slot_e * 8, ctx->cur) != hipSuccess) {
-    if (tg) (void)hipFreeAsync(tg, ctx->cur);
+template <typename Encode>
+int pack_after(bic_ctx* ctx, int nplanes, const bic::CoderOut& g, const bic::CoderOut& e, Encode&& encode) {
+  bic::CoderOut tg{nullptr, g.slot, g.bits, nullptr}, te{nullptr, e.slot, e.bits, nullptr};
+  if (g.out) BIC_HIP(hipMallocAsync(reinterpret_cast<void**>(&tg.out), (size_t)nplanes * g.slot * 8, ctx->cur));
+  if (e.out && hipMallocAsync(reinterpret_cast<void**>(&te.out), (size_t)nplanes * e.slot * 8, ctx->cur) != hipSuccess) {
+    if (tg.out) (void)hipFreeAsync(tg.out, ctx->cur);
     return BIC_EDEVICE;
   }
   const int rc = encode(tg, te);
-  if (rc == BIC_OK && tg)
-    timed(ctx, "pack", [&] { bic::launch_pack(ctx->cur, tg, nplanes, slot_g, bits_g, out_g, off_g); });
-  if (rc == BIC_OK && te)
-    timed(ctx, "pack", [&] { bic::launch_pack(ctx->cur, te, nplanes, slot_e, bits_e, out_e, off_e); });
-  if (tg) (void)hipFreeAsync(tg, ctx->cur);
-  if (te) (void)hipFreeAsync(te, ctx->cur);
+  if (rc == BIC_OK && tg.out)
+    timed(ctx, "pack", [&] { bic::launch_pack(ctx->cur, tg.out, nplanes, g.slot, g.bits, g.out, g.off); });
+  if (rc == BIC_OK && te.out)
+    timed(ctx, "pack", [&] { bic::launch_pack(ctx->cur, te.out, nplanes, e.slot, e.bits, e.out, e.off); });
+  if (tg.out) (void)hipFreeAsync(tg.out, ctx->cur);
+  if (te.out) (void)hipFreeAsync(te.out, ctx->cur);
   BIC_HIP(hipGetLastError());
   return rc;
 }
-}  // namespace
 
-static int encode_planes_impl(bic_ctx* ctx, const uint64_t* planes, int nplanes, size_t rows, size_t cols,
-                              size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
-                              uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg, size_t slot_eg,
-                              uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index = nullptr) {
+bool outs_ok(const bic::CoderOut& g, const bic::CoderOut& e) {
+  return (g.out || e.out) && (!g.out || (g.bits && g.slot)) && (!e.out || (e.bits && e.slot));
+}
+
+// One call of the row encoders (bic_fused*.hip) on ctx->cur: the scratch arena, then clear -> count
+// pass -> prefix -> rows -> finish. c comes as {g, planes, predict, mode, rq}.
+// count: the caller's count pass (bic_encode_gray*'s bitplane kernel, rq.counted), given the arena;
+// without one the staged prefix counts for itself. prefix_only (bic_row_index): the staged prefix
+// alone, recorded as "row_index".
+template <typename Count>
+int run_fused(bic_ctx* ctx, bic::FusedCall& c, Count&& count, bool prefix_only = false) {
+  int rc = ensure_scratch(ctx, bic::fused_scratch_bytes(c.g));
+  if (rc) return rc;
+  c.ar = bic::carve_fused_arena(ctx->scratch, c.g);
+  c.lut = ctx->lut;
+  c.flags = ctx->flags;
+  const bool staged = c.mode == bic::kEncStaged;
+  // (look-back encoders: no memset when the previous call's k_fixup left the counters and records
+  // zero: C2 0.036 -> 0.032 ms. A call on another stream without synchronisation would share the arena
+  // anyway: calls on one context are ordered by the caller)
+  hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(ctx->cur, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone) ctx->captured = true;
+  c.rq.zero_ready = !staged && !ctx->captured && ctx->scratch_zero_prev >= c.ar.zero_bytes;
+  if (!staged) bic::launch_lookback_clear(ctx->cur, c);
+  if (c.rq.counted) timed(ctx, "bitplanes_count", [&] { count(c.ar); });
+  // staged encoder: per-row counts, scans and Golomb lengths (every row's offsets known up front)
+  if (staged)
+    timed(ctx, prefix_only ? "row_index" : "encode_prefix",
+          [&] { bic::launch_staged_prefix(ctx->cur, c, c.rq.g.out || c.rq.index); });
+  if (!prefix_only) {
+    // the row kernel alone is timed under the encoder's name (bench.py's roofline kernel)
+    bic::EmitStreams es;
+    if (staged) set_aux(ctx, es);
+    const char* name = c.rq.eg_src ? "encode_rows_golomb_egsrc"
+                       : c.rq.g.out ? (c.rq.e.out ? "encode_rows_golomb_eg" : "encode_rows_golomb") : "encode_rows_eg";
+    timed_rows(ctx, es, name, [&] {
+      if (staged) bic::launch_staged_emit(ctx->cur, c, es);
+      else bic::launch_lookback_rows(ctx->cur, c);
+    });
+    timed(ctx, "encode_finish", [&] { bic::launch_fused_finish(ctx->cur, c); });
+  }
+  BIC_HIP(hipGetLastError());
+  if (!staged && !ctx->captured) ctx->scratch_zero = c.ar.zero_bytes;  // (k_fixup cleared them)
+  return BIC_OK;
+}
+
+int encode_planes_impl(bic_ctx* ctx, const uint64_t* planes, const Shape& sh, int predict, const bic::CoderOut& og,
+                       const bic::CoderOut& oe, uint64_t* row_index = nullptr) {
+  const int nplanes = sh.nplanes;
   int rc = bind(ctx);
   if (rc) return rc;
-  if (nplanes < 1 || !geom_ok(rows, cols, wpr)) return BIC_EINVAL;
-  if (!out_golomb && !out_eg) return BIC_EINVAL;
-  if (out_golomb && (!bits_golomb || slot_golomb == 0)) return BIC_EINVAL;
-  if (out_eg && (!bits_eg || slot_eg == 0)) return BIC_EINVAL;
-  if (rows && !planes) return BIC_EINVAL;
-  if (rows == 0) {
-    if (out_golomb) BIC_HIP((bic::launch_fill(ctx->cur, bits_golomb, 0, sizeof(uint64_t) * nplanes), hipGetLastError()));
-    if (out_eg) BIC_HIP((bic::launch_fill(ctx->cur, bits_eg, 0, sizeof(uint64_t) * nplanes), hipGetLastError()));
-    if (off_golomb) BIC_HIP((bic::launch_fill(ctx->cur, off_golomb, 0, sizeof(uint64_t) * (nplanes + 1)), hipGetLastError()));
-    if (off_eg) BIC_HIP((bic::launch_fill(ctx->cur, off_eg, 0, sizeof(uint64_t) * (nplanes + 1)), hipGetLastError()));
+  if (nplanes < 1 || !geom_ok(sh.rows, sh.cols, sh.wpr) || !outs_ok(og, oe) || (sh.rows && !planes)) return BIC_EINVAL;
+  if (sh.rows == 0) {
+    if (og.out) BIC_HIP((bic::launch_fill(ctx->cur, og.bits, 0, sizeof(uint64_t) * nplanes), hipGetLastError()));
+    if (oe.out) BIC_HIP((bic::launch_fill(ctx->cur, oe.bits, 0, sizeof(uint64_t) * nplanes), hipGetLastError()));
+    if (og.off) BIC_HIP((bic::launch_fill(ctx->cur, og.off, 0, sizeof(uint64_t) * (nplanes + 1)), hipGetLastError()));
+    if (oe.off) BIC_HIP((bic::launch_fill(ctx->cur, oe.off, 0, sizeof(uint64_t) * (nplanes + 1)), hipGetLastError()));
     return BIC_OK;
   }
   const int pr = predict ? 1 : 0;
-  const bic::Geom g = bic::make_geom(rows, cols, wpr, nplanes);
+  const bic::Geom g = bic::make_geom(sh.rows, sh.cols, sh.wpr, nplanes);
+  // packed output via slots + pack
+  auto packed_after = [&] {
+    return pack_after(ctx, nplanes, og, oe, [&](const bic::CoderOut& tg, const bic::CoderOut& te) {
+      return encode_planes_impl(ctx, planes, sh, predict, tg, te);
+    });
+  };
   if (bic::fused_supported(g) && !ctx->force_multipass) {
-    // one pass: residual -> runs -> both streams (bic_fused.hip)
-    if ((rc = ensure_scratch(ctx, bic::fused_scratch_bytes(g)))) return rc;
-    bic::FusedScratch fs = bic::carve_fused_scratch(ctx->scratch, g);
-    set_aux(ctx, fs);
+    // one pass: residual -> runs -> both streams (bic_fused.hip, bic_fused_lookback.hip)
     const int mode = ctx->two_pass ? bic::kEncTwoPass
                      : (ctx->single_kernel || !staged_pays(ctx, g) || !bic::med_rows_supported(g, planes, nullptr))
                          ? bic::kEncSingle
-                                                                                            : bic::kEncStaged;
-    if (row_index && (mode != bic::kEncStaged || !out_golomb)) {  // the index from the staged prefix kernels
-      if ((rc = encode_planes_impl(ctx, planes, nplanes, rows, cols, wpr, predict, out_golomb, slot_golomb,
-                                   bits_golomb, off_golomb, out_eg, slot_eg, bits_eg, off_eg)))
-        return rc;
-      return bic_row_index(ctx, planes, nplanes, rows, cols, wpr, predict, row_index);
+                         : bic::kEncStaged;
+    if (row_index && (mode != bic::kEncStaged || !og.out)) {  // the index from the staged prefix kernels
+      if ((rc = encode_planes_impl(ctx, planes, sh, predict, og, oe))) return rc;
+      return bic_row_index(ctx, planes, nplanes, sh.rows, sh.cols, sh.wpr, predict, row_index);
     }
-    if ((off_golomb || off_eg) && mode != bic::kEncStaged)  // packed output via slots + pack
-      return pack_after(ctx, nplanes, out_golomb, slot_golomb, bits_golomb, off_golomb, out_eg, slot_eg, bits_eg,
-                        off_eg, [&](uint64_t* tg, uint64_t* te) {
-                          return encode_planes_impl(ctx, planes, nplanes, rows, cols, wpr, predict, tg, slot_golomb,
-                                                    bits_golomb, nullptr, te, slot_eg, bits_eg, nullptr);
-                        });
-    fs.off_g = off_golomb;
-    fs.off_e = off_eg;
-    fs.index = row_index;
-    // (no memset when the previous call's k_fixup left the counters and records zero: C2 0.036 ->
-    // 0.032 ms. A call on another stream without synchronisation would share the arena anyway: calls
-    // on one context are ordered by the caller)
-    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(ctx->cur, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone) ctx->captured = true;
-    fs.zero_ready = mode != bic::kEncStaged && !ctx->captured && ctx->scratch_zero_prev >= fs.zero_bytes;
-    auto stage = [&](int st) {
-      bic::launch_fused(ctx->cur, g, planes, ctx->lut, pr, fs, out_golomb, slot_golomb, bits_golomb, out_eg, slot_eg,
-                        bits_eg, ctx->flags, mode, st);
-    };
-    stage(bic::kFusedPrep);
-    // staged encoder: per-row counts, scans and Golomb lengths (every row's offsets known up front)
-    if (mode == bic::kEncStaged) timed(ctx, "encode_prefix", [&] { stage(bic::kFusedPrefix); });
-    // the row kernel alone is timed under the encoder's name (bench.py's roofline kernel)
-    timed_rows(ctx, fs, out_golomb ? (out_eg ? "encode_rows_golomb_eg" : "encode_rows_golomb") : "encode_rows_eg",
-               [&] { stage(bic::kFusedRows); });
-    timed(ctx, "encode_finish", [&] { stage(bic::kFusedFinish); });
-    BIC_HIP(hipGetLastError());
-    if (mode != bic::kEncStaged && !ctx->captured) ctx->scratch_zero = fs.zero_bytes;  // (k_fixup cleared them)
-    return BIC_OK;
+    if ((og.off || oe.off) && mode != bic::kEncStaged) return packed_after();
+    bic::FusedCall c{g, planes, pr, mode, {og, oe, row_index}};
+    return run_fused(ctx, c, [](const bic::FusedArena&) {});
   }
   // rows wider than 16384 columns: multi-pass chunk kernels (bic_kernels.hip)
   if (row_index) return BIC_EINVAL;  // (the decoders take rows of up to 16384 columns)
-  if (off_golomb || off_eg)  // packed output via slots + pack
-    return pack_after(ctx, nplanes, out_golomb, slot_golomb, bits_golomb, off_golomb, out_eg, slot_eg, bits_eg, off_eg,
-                      [&](uint64_t* tg, uint64_t* te) {
-                        return encode_planes_impl(ctx, planes, nplanes, rows, cols, wpr, predict, tg, slot_golomb,
-                                                  bits_golomb, nullptr, te, slot_eg, bits_eg, nullptr);
-                      });
+  if (og.off || oe.off) return packed_after();
   if ((rc = ensure_scratch(ctx, bic::chunk_scratch_bytes(g)))) return rc;
   const bic::ChunkScratch cs = bic::carve_chunk_scratch(ctx->scratch, g);
   timed(ctx, "med_count", [&] { bic::launch_count(ctx->cur, g, planes, pr, cs, nullptr, nullptr); });
   timed(ctx, "scan_rows", [&] { bic::launch_scan_rows(ctx->cur, g, cs); });
-  if (out_golomb) {
+  if (og.out) {
     timed(ctx, "golomb_bits", [&] { bic::launch_golomb_bits(ctx->cur, g, planes, pr, cs); });
     timed(ctx, "golomb_offsets", [&] {
-      bic::launch_golomb_offsets(ctx->cur, g, cs, out_golomb, slot_golomb, bits_golomb, ctx->flags);
+      bic::launch_golomb_offsets(ctx->cur, g, cs, og.out, og.slot, og.bits, ctx->flags);
     });
-    timed(ctx, "golomb_emit", [&] {
-      bic::launch_golomb_emit(ctx->cur, g, planes, pr, cs, out_golomb, slot_golomb);
-    });
+    timed(ctx, "golomb_emit", [&] { bic::launch_golomb_emit(ctx->cur, g, planes, pr, cs, og.out, og.slot); });
   }
-  if (out_eg) {
-    timed(ctx, "eg_emit", [&] {
-      bic::launch_eg_emit(ctx->cur, g, planes, pr, cs, out_eg, slot_eg, bits_eg, ctx->flags);
-    });
-  }
+  if (oe.out)
+    timed(ctx, "eg_emit", [&] { bic::launch_eg_emit(ctx->cur, g, planes, pr, cs, oe.out, oe.slot, oe.bits, ctx->flags); });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
 }
 
-int bic_encode_planes2(bic_ctx* ctx, const uint64_t* planes, int nplanes, size_t rows, size_t cols,
-                       size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
-                       uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg) {
-  return encode_planes_impl(ctx, planes, nplanes, rows, cols, wpr, predict, out_golomb, slot_golomb, bits_golomb,
-                            nullptr, out_eg, slot_eg, bits_eg, nullptr);
-}
-
-int bic_encode_planes_packed(bic_ctx* ctx, const uint64_t* planes, int nplanes, size_t rows, size_t cols,
-                             size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
-                             uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg, size_t slot_eg,
-                             uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
-  if ((out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
-  return encode_planes_impl(ctx, planes, nplanes, rows, cols, wpr, predict, out_golomb, slot_golomb, bits_golomb,
-                            off_golomb, out_eg, slot_eg, bits_eg, off_eg, row_index);
-}
-
-// bps: bytes per sample -- 1 (bic_encode_gray*), or 2 (bic_encode_gray16*: big_endian = 1 the P5 order of
-// pnm.cpp:73, 0 the host's uint16_t). Only the count pass (and the fallback's plane extraction) knows
-// the sample size; everything after it is per (plane, row).
-static int encode_gray_impl(bic_ctx* ctx, const uint8_t* gray, int bps, int big_endian, size_t pitch, size_t rows,
-                            size_t cols, int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict,
-                            uint64_t* out_golomb, size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb,
-                            uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg,
-                            uint64_t* row_index = nullptr) {
+// Only the count pass (and the fallback's plane extraction) knows the sample size; everything after
+// it is per (plane, row).
+int encode_gray_impl(bic_ctx* ctx, const GrayImage& img, int plane0, uint64_t* planes, const Shape& sh, int predict,
+                     const bic::CoderOut& og, const bic::CoderOut& oe, uint64_t* row_index = nullptr) {
+  const int nplanes = sh.nplanes, bps = img.bps;
+  const size_t rows = sh.rows, cols = sh.cols, wpr = sh.wpr;
   int rc = bind(ctx);
   if (rc) return rc;
-  if (plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 * bps || cols > SIZE_MAX / 2 || pitch < cols * (size_t)bps ||
-      !geom_ok(rows, cols, wpr))
+  if (plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 * bps || cols > SIZE_MAX / 2 ||
+      img.pitch < cols * (size_t)bps || !geom_ok(rows, cols, wpr) || !outs_ok(og, oe) || (rows && !img.data))
     return BIC_EINVAL;
-  if (!out_golomb && !out_eg) return BIC_EINVAL;
-  if (out_golomb && (!bits_golomb || slot_golomb == 0)) return BIC_EINVAL;
-  if (out_eg && (!bits_eg || slot_eg == 0)) return BIC_EINVAL;
-  if (rows && !gray) return BIC_EINVAL;
   const bic::Geom g = bic::make_geom(rows, cols, wpr, nplanes);
   // EG source: no bitplanes wanted and the EG stream into slots -- the count pass writes the EG
   // stream (its uniform layout) instead of the residual planes, and the Golomb kernels read the
-  // residual rows back from it (bic_internal.h FusedScratch::eg_src): no residual buffer at all
+  // residual rows back from it (bic_internal.h FusedRequest::eg_src): no residual buffer at all
   const uint64_t eg_words = ((uint64_t)rows * (cols + 1) + 1 + 63) / 64;
   const bool fuse = rows && bic::fused_supported(g) && !ctx->force_multipass && !ctx->two_pass && !ctx->single_kernel &&
                     staged_pays(ctx, g) && bic::med_rows_supported(g, planes, nullptr) &&
-                    bic::gray_rows_supported(g, gray, pitch, planes, bps);
-  const bool eg_src = fuse && !planes && predict && out_eg && !off_eg && bic::gray_eg_supported(g) &&
-                      eg_words <= slot_eg && (out_golomb || !row_index) && !ctx->eg_src_off;
+                    bic::gray_rows_supported(g, img.data, img.pitch, planes, bps);
+  const bool eg_src = fuse && !planes && predict && oe.out && !oe.off && bic::gray_eg_supported(g) &&
+                      eg_words <= oe.slot && (og.out || !row_index) && !ctx->eg_src_off;
   if (!planes && rows && !eg_src) {
     // no bitplanes wanted: the count pass stores the med residual planes into the context's buffer
     // (the same bytes the bitplanes would take) and the encoder reads them with prediction off --
@@ -678,57 +666,61 @@ static int encode_gray_impl(bic_ctx* ctx, const uint8_t* gray, int bps, int big_
   const bool store_resid = !planes && predict;
   if (!planes && !eg_src) planes = ctx->rbuf;
   if (!fuse) {  // the same result through the two separate calls
-    if ((rc = bps == 2 ? bic_bitplanes_u16(ctx, gray, pitch, rows, cols, big_endian, plane0, nplanes, planes, wpr)
-                       : bic_bitplanes_u8_range(ctx, gray, pitch, rows, cols, plane0, nplanes, planes, wpr)))
+    if ((rc = bps == 2 ? bic_bitplanes_u16(ctx, img.data, img.pitch, rows, cols, img.big_endian, plane0, nplanes, planes, wpr)
+                       : bic_bitplanes_u8_range(ctx, img.data, img.pitch, rows, cols, plane0, nplanes, planes, wpr)))
       return rc;
-    return encode_planes_impl(ctx, planes, nplanes, rows, cols, wpr, predict, out_golomb, slot_golomb, bits_golomb,
-                              off_golomb, out_eg, slot_eg, bits_eg, off_eg, row_index);
+    return encode_planes_impl(ctx, planes, sh, predict, og, oe, row_index);
   }
   const int pr = predict && !store_resid ? 1 : 0;  // R stored: the encoder codes it as given
-  if ((rc = ensure_scratch(ctx, bic::fused_scratch_bytes(g)))) return rc;
-  bic::FusedScratch fs = bic::carve_fused_scratch(ctx->scratch, g);
-  fs.counted = true;
-  fs.ns = bic::gray_strips(g);
-  fs.off_g = off_golomb;
-  fs.off_e = off_eg;
-  fs.index = out_golomb ? row_index : nullptr;
-  fs.eg_src = eg_src;
-  fs.eg_src_one = ctx->eg_src_one;
-  set_aux(ctx, fs);
-  auto stage = [&](int st) {
-    bic::launch_fused(ctx->cur, g, planes, ctx->lut, pr, fs, out_golomb, slot_golomb, bits_golomb, out_eg, slot_eg,
-                      bits_eg, ctx->flags, bic::kEncStaged, st);
-  };
-  stage(bic::kFusedPrep);
-  timed(ctx, "bitplanes_count", [&] {
-    bic::launch_gray_rows(ctx->cur, gray, pitch, g, predict ? 1 : 0, plane0, planes, fs.sones, fs.krec, fs.kpos,
-                          fs.counter, store_resid, eg_src ? out_eg : nullptr, slot_eg, bps, big_endian);
-  });
-  timed(ctx, "encode_prefix", [&] { stage(bic::kFusedPrefix); });
+  bic::FusedCall c{g, planes, pr, bic::kEncStaged, {og, oe, og.out ? row_index : nullptr}};
+  c.rq.eg_src = eg_src;
+  c.rq.eg_src_one = ctx->eg_src_one;
+  c.rq.counted = true;
+  c.rq.ns = bic::gray_strips(g);
   // (EG source: the emission is Golomb's alone, reading the residual rows from the EG stream)
-  timed_rows(ctx, fs, eg_src ? "encode_rows_golomb_egsrc"
-                             : out_golomb ? (out_eg ? "encode_rows_golomb_eg" : "encode_rows_golomb") : "encode_rows_eg",
-             [&] { stage(bic::kFusedRows); });
-  timed(ctx, "encode_finish", [&] { stage(bic::kFusedFinish); });
-  BIC_HIP(hipGetLastError());
-  if (row_index && !out_golomb) return bic_row_index(ctx, planes, nplanes, rows, cols, wpr, pr, row_index);
+  if ((rc = run_fused(ctx, c, [&](const bic::FusedArena& ar) {
+         bic::launch_gray_rows(ctx->cur, img.data, img.pitch, g, predict ? 1 : 0, plane0, planes, ar.sones, ar.krec,
+                               ar.kpos, ar.counter, store_resid, eg_src ? oe.out : nullptr, oe.slot, bps,
+                               img.big_endian);
+       })))
+    return rc;
+  if (row_index && !og.out) return bic_row_index(ctx, planes, nplanes, rows, cols, wpr, pr, row_index);
   return BIC_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int bic_encode_planes2(bic_ctx* ctx, const uint64_t* planes, int nplanes, size_t rows, size_t cols,
+                       size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
+                       uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg) {
+  return encode_planes_impl(ctx, planes, {nplanes, rows, cols, wpr}, predict, {out_golomb, slot_golomb, bits_golomb},
+                            {out_eg, slot_eg, bits_eg});
+}
+
+int bic_encode_planes_packed(bic_ctx* ctx, const uint64_t* planes, int nplanes, size_t rows, size_t cols,
+                             size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
+                             uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg, size_t slot_eg,
+                             uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
+  if ((out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
+  return encode_planes_impl(ctx, planes, {nplanes, rows, cols, wpr}, predict,
+                            {out_golomb, slot_golomb, bits_golomb, off_golomb}, {out_eg, slot_eg, bits_eg, off_eg},
+                            row_index);
 }
 
 int bic_encode_gray_range(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size_t rows, size_t cols, int plane0,
                           int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
                           size_t slot_golomb, uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg,
                           uint64_t* bits_eg) {
-  return encode_gray_impl(ctx, gray, 1, 0, pitch, rows, cols, plane0, nplanes, planes, wpr, predict, out_golomb,
-                          slot_golomb, bits_golomb, nullptr, out_eg, slot_eg, bits_eg, nullptr);
+  return encode_gray_impl(ctx, {gray, pitch, 1, 0}, plane0, planes, {nplanes, rows, cols, wpr}, predict,
+                          {out_golomb, slot_golomb, bits_golomb}, {out_eg, slot_eg, bits_eg});
 }
 
 int bic_encode_gray16(bic_ctx* ctx, const void* gray, size_t pitch, size_t rows, size_t cols, int big_endian,
                       int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
                       size_t slot_golomb, uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg) {
-  return encode_gray_impl(ctx, static_cast<const uint8_t*>(gray), 2, big_endian ? 1 : 0, pitch, rows, cols, plane0,
-                          nplanes, planes, wpr, predict, out_golomb, slot_golomb, bits_golomb, nullptr, out_eg, slot_eg,
-                          bits_eg, nullptr);
+  return encode_gray_impl(ctx, {static_cast<const uint8_t*>(gray), pitch, 2, big_endian ? 1 : 0}, plane0, planes,
+                          {nplanes, rows, cols, wpr}, predict, {out_golomb, slot_golomb, bits_golomb},
+                          {out_eg, slot_eg, bits_eg});
 }
 
 int bic_encode_gray16_packed(bic_ctx* ctx, const void* gray, size_t pitch, size_t rows, size_t cols, int big_endian,
@@ -736,9 +728,9 @@ int bic_encode_gray16_packed(bic_ctx* ctx, const void* gray, size_t pitch, size_
                              size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
                              size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
   if ((out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
-  return encode_gray_impl(ctx, static_cast<const uint8_t*>(gray), 2, big_endian ? 1 : 0, pitch, rows, cols, plane0,
-                          nplanes, planes, wpr, predict, out_golomb, slot_golomb, bits_golomb, off_golomb, out_eg,
-                          slot_eg, bits_eg, off_eg, row_index);
+  return encode_gray_impl(ctx, {static_cast<const uint8_t*>(gray), pitch, 2, big_endian ? 1 : 0}, plane0, planes,
+                          {nplanes, rows, cols, wpr}, predict, {out_golomb, slot_golomb, bits_golomb, off_golomb},
+                          {out_eg, slot_eg, bits_eg, off_eg}, row_index);
 }
 
 int bic_encode_gray_packed(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size_t rows, size_t cols, int plane0,
@@ -746,8 +738,9 @@ int bic_encode_gray_packed(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size
                            size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
                            size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
   if ((out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
-  return encode_gray_impl(ctx, gray, 1, 0, pitch, rows, cols, plane0, nplanes, planes, wpr, predict, out_golomb,
-                          slot_golomb, bits_golomb, off_golomb, out_eg, slot_eg, bits_eg, off_eg, row_index);
+  return encode_gray_impl(ctx, {gray, pitch, 1, 0}, plane0, planes, {nplanes, rows, cols, wpr}, predict,
+                          {out_golomb, slot_golomb, bits_golomb, off_golomb}, {out_eg, slot_eg, bits_eg, off_eg},
+                          row_index);
 }
 
 int bic_row_index(bic_ctx* ctx, const uint64_t* planes, int nplanes, size_t rows, size_t cols, size_t wpr,
@@ -771,19 +764,11 @@ int bic_row_index(bic_ctx* ctx, const uint64_t* planes, int nplanes, size_t rows
     (void)hipFreeAsync(tmp, ctx->cur);
     return rc;
   }
-  if ((rc = ensure_scratch(ctx, bic::fused_scratch_bytes(g)))) return rc;
-  bic::FusedScratch fs = bic::carve_fused_scratch(ctx->scratch, g);
-  fs.index = index;
-  const size_t slot = bic_encode_slot_words(rows, cols, BIC_CODER_GOLOMB);
   // the staged encoder's prefix kernels alone (counts, scans, the walk of mixed-k rows, the
-  // length scan): they touch no output words, only the scratch, the per-plane totals (gbase) and
-  // the index; `index` stands in for the Golomb output, which they never write
-  timed(ctx, "row_index", [&] {
-    bic::launch_fused(ctx->cur, g, planes, ctx->lut, predict ? 1 : 0, fs, index, slot, fs.gbase, nullptr, 0, nullptr,
-                      ctx->flags, bic::kEncStaged, bic::kFusedPrefix);
-  });
-  BIC_HIP(hipGetLastError());
-  return BIC_OK;
+  // length scan): they touch no output words, only the scratch and the index
+  const bic::CoderOut slot_only{nullptr, bic_encode_slot_words(rows, cols, BIC_CODER_GOLOMB)};
+  bic::FusedCall c{g, planes, predict ? 1 : 0, bic::kEncStaged, {slot_only, {}, index}};
+  return run_fused(ctx, c, [](const bic::FusedArena&) {}, /*prefix_only=*/true);
 }
 
 int bic_decode_planes(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,

@@ -593,7 +593,7 @@ __device__ __forceinline__ void lds_image_zero32(uint32_t* img, uint32_t n16) {
 __device__ __forceinline__ void lds_or64(uint64_t* img, uint32_t i, uint64_t v) {
   if (v) atomicOr(reinterpret_cast<unsigned long long*>(img + i), (unsigned long long)v);
 }
-// write_row for a 64-bit LDS image (bic_fused.hip place128_64, bic_egad.hip): output word t of the row holds image bits
+// write_row for a 64-bit LDS image (bic_fused.h place128_64, bic_egad.hip): output word t of the row holds image bits
 // [64 t - G % 64, 64 t - G % 64 + 64): two LDS words and a funnel shift.
 __device__ __forceinline__ void write_row64(const uint64_t* img, uint64_t L, uint64_t G, uint64_t* out,
                                             uint64_t* frag) {

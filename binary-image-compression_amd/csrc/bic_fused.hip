@@ -1,931 +1,16 @@
-// bic_fused.hip -- row encoders for rows of up to 256 words (16384 columns): med residual ->
-// per-row runs -> Golomb stream and/or EG stream, one wavefront per row, 16-row tiles.
-//
-// Semantics are those of bic_kernels.hip (GolombCoder.cpp:13-34, eg.cpp:20-37, pred.cpp:3-15);
-// the difference is the schedule. The default single kernel (k_encode_rows):
-//  * tiles are claimed in order through an atomic ticket, so every tile a workgroup looks back
-//    at was claimed earlier and is running or finished (no deadlock, whatever the dispatch order);
-//  * the tile's 1-count is published at once and a decoupled look-back over the earlier tiles
-//    of the plane yields the number of samples before each row (the Golomb coder state);
-//  * every codeword is computed ONCE: each lane turns its word into a register string
-//    (first codeword's binary part, its unary zeros, then <= 128 bits), or -- when the k
-//    bounds prove k = 0 for every codeword of the word -- copies the word's bits (a k = 0
-//    codeword is exactly the run's zeros and its 1); constant k = 1..3 words go byte by byte
-//    through precomputed tables;
-//  * lane strings are OR'd into an LDS row image; the tile's bit length is published and a
-//    second look-back gives its offset; whole 64-bit words go to HBM with plain stores and
-//    the (at most two) words shared with neighbouring rows go to a fragment table that the
-//    fixup kernel combines (no atomics on the output, no pre-zeroing of the output).
-// The two-pass option (k_len_rows, k_emit_rows) computes lengths and offsets first and then
-// writes every row independently; same output, slower.
-// Inter-workgroup records are 8-byte {flag, value} granules written and polled with
-// agent-scope atomics (cdna_hip_programming.md §6 Guideline 16, R2), spins bounded.
-#include "bic_device.h"
-#include "bic_k1pi.h"  // the k = 1 rows' backward-parity encoder (host-compilable: tests/cpp/k1pi_check.cpp)
-#include "bic_kstat.h"
+// bic_fused.hip -- the staged row encoder for rows of up to 256 words (16384 columns), the default:
+// count pass -> ONES scan -> walk of the mixed-k rows -> LEN scan -> emission (k_emit_known, or
+// k_emit_k01 per row class when the rows come back from the EG stream, with k_emit_rest beside it
+// for the listed rows); then the finish kernels every row encoder shares (k_rows_global, k_fixup)
+// and the scratch arena's layout. The lanes' codewords, the row images and the kernels' argument
+// block are bic_fused.h's; the look-back encoders (small batches, cross-checks) are
+// bic_fused_lookback.hip's.
+#include "bic_fused.h"
 
 #include <algorithm>
 #include <cstdio>
 
 namespace bic {
-
-#ifdef BIC_STAMPS  // diagnostic build only (make stamps): per-wave phase clocks, never in the product
-__device__ unsigned long long g_stamps[1 << 22];
-// BIC_KNOWN=1 (diagnostic): replay the tile prefixes recorded by the previous normal launch
-// instead of looking them back, to measure what the look-back waits cost
-__device__ unsigned long long g_known[2][1 << 17];
-#define STAMP(slot)                                                                        \
-  do {                                                                                     \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();                            \
-    if (lane == 0 && (uint64_t)id * 8 + (slot) < (1u << 21)) g_stamps[(uint64_t)id * 8 + (slot)] = t_; \
-  } while (0)
-// k_row_walk's phases (slots 4-7 of the row: entry, residual word loaded, length walked, stored), on
-// the 100 MHz clock every XCD shares (s_memrealtime), waiting for the phase's loads first
-#define WSTAMP(slot)                                                                               \
-  do {                                                                                             \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                    \
-    const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();                                \
-    if (threadIdx.x == 0 && (uint64_t)id * 8 + (slot) < (1u << 21)) g_stamps[(uint64_t)id * 8 + (slot)] = t_; \
-  } while (0)
-// k_scan_rows' phases per workgroup (slots of g_stamps from 1 << 21: ONES scan, then LEN scan)
-#define SSTAMP(slot)                                                                              \
-  do {                                                                                            \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                   \
-    const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();                               \
-    if (threadIdx.x == 0) g_stamps[(1u << 21) + (ONES ? 0u : 8192u) + blockIdx.x * 8u + (slot)] = t_; \
-  } while (0)
-// the class launch's phases (tools/k01_stamps.py), 4 slots per index: per k = 1 row (YSTAMP, index
-// 1 << 18 + its row id; slots 0-3: entry, words assembled, image built, stored), per wave of k_emit_k01
-// (index 1 << 19 + 8192 + its wave; slots 0-3: entry, k = 0 rows done, -, exit)
-#define XSTAMP(idx, slot)                                                                          \
-  do {                                                                                             \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                    \
-    const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();                                \
-    if (lane_id() == 0 && (uint64_t)(idx) * 4 + (slot) < (1u << 22)) g_stamps[(uint64_t)(idx) * 4 + (slot)] = t_; \
-  } while (0)
-// (the same without draining the memory counters first: the instruction's issue time)
-#define YSTAMP(idx, slot)                                                                          \
-  do {                                                                                             \
-    const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();                                \
-    if (lane_id() == 0 && (uint64_t)(idx) * 4 + (slot) < (1u << 22)) g_stamps[(uint64_t)(idx) * 4 + (slot)] = t_; \
-  } while (0)
-#else
-#define XSTAMP(idx, slot) \
-  do {                    \
-  } while (0)
-#define YSTAMP(idx, slot) \
-  do {                    \
-  } while (0)
-#define STAMP(slot) \
-  do {              \
-  } while (0)
-#define WSTAMP(slot) \
-  do {               \
-  } while (0)
-#define SSTAMP(slot) \
-  do {               \
-  } while (0)
-#endif
-
-constexpr int kTileRows = 16;  // rows (= waves) per workgroup tile (C3: 666 us vs 677 at 8 rows)
-constexpr int kGImg = 684;    // u32 words of Golomb row image per wave (21760 bits; with the EG image and
-                              // the k = 1, 2 byte tables 4 workgroups (32 waves) fit one CU's LDS)
-constexpr int kEImg = 520;    // u32 words of EG row image per wave (cols <= 16384)
-constexpr int kPad = 4;       // zeroed words after an image's end (get64 reads ahead)
-constexpr uint32_t kK1Table = 512u;  // the k = 1 rows' table in the u32 byte tables (k1_pi, the [pi][byte] table)
-// k_emit_known's k = 1 rows (C4, C2, predict) go by encode_word_k1b, table 0 (C4 0.268 ms against 0.283
-// with the backward parity's strided lanes)
-constexpr uint32_t kKnownTable = 0u;
-
-// One lane's codewords for one residual word.
-struct LaneEnc {
-  uint32_t head, k0, z;  // first codeword: k0-bit binary part, then z unary zeros
-  uint64_t t0, t1;       // the rest (starting with the first codeword's '1'), MSB-first
-  uint32_t tlen;
-  uint32_t len;          // total bits
-  bool lng;              // rest longer than 128 bits: placed by re-iteration
-#ifdef BIC_STAMPS
-  uint32_t path;         // diagnostic: 1 copy mode, 2 byte table, 3 per-codeword loop
-#endif
-};
-
-__device__ __forceinline__ void tail_put(LaneEnc& e, uint64_t cw, uint32_t nb) {  // nb 1..64
-  const uint32_t pos = e.tlen;
-  e.tlen = pos + nb;
-  if (pos + nb > 128) { e.lng = true; return; }
-  const uint32_t sh = 128 - pos - nb;
-  if (sh >= 64) {
-    e.t0 |= cw << (sh - 64);
-  } else {
-    e.t1 |= cw << sh;
-    if (sh + nb > 64) e.t0 |= cw >> (64 - sh);
-  }
-}
-
-// Byte tables for words whose codewords all share one k in 1..3 (built on the host,
-// bic_kernels.hip build_byte_lut): for a byte v != 0, the codewords that lie wholly inside the
-// byte (after its first 1) as one right-aligned pattern R of lr bits, plus the byte's leading (t)
-// and trailing (tz) zeros. k = 1, 2: packed u32 R | lr << 21 | t << 26 | tz << 29, staged in LDS
-// by the encoder; k = 3: u64 R | lr << 32 | t << 40 | tz << 44 from global memory.
-struct ByteTables {
-  const uint32_t* t12;  // [2][256]
-  const uint64_t* t3;   // [256]
-};
-__device__ __forceinline__ void tail_put_n(LaneEnc& e, uint64_t cw, uint32_t nb) {
-  if (nb) tail_put(e, cw, nb);
-}
-
-// STR = false computes only e.len (the length pass of the two-pass encoder).
-template <bool STR = true>
-__device__ __forceinline__ LaneEnc encode_word(uint64_t x, uint32_t w, uint32_t n, int jp, uint32_t arow,
-                                               bool eol, uint32_t cols, ByteTables lut) {
-  LaneEnc e{};
-  if (!x && !eol) return e;
-  if (x && n) {
-    // A never decreases and n only grows along the word, so every codeword's k lies between
-    // k(n_last, A_first) and k(n_first, A_last); when the two agree, k is the same throughout.
-    const uint32_t m = (uint32_t)__popcll(x);
-    const uint32_t plast = w * 64 + 63 - (uint32_t)__builtin_ctzll(x);
-    const uint32_t aup = arow + plast - (n + m - 1);  // >= A of the last codeword (and = A of the EOL's)
-    const uint32_t afirst = arow + (uint32_t)(jp + 1) - n;
-    const uint32_t khi = golomb_k(n, aup);
-    const uint32_t klo = golomb_k(n + m - 1 + (eol ? 1u : 0u), afirst);
-    if (khi == klo && khi == 0) {
-      // k = 0: a codeword is its run's zeros and the 1 -- the word's bits verbatim
-      e.z = w * 64 - (uint32_t)(jp + 1);
-      e.t0 = x;
-      if (!eol) {
-        e.tlen = plast - w * 64 + 1;
-      } else {
-        const uint32_t p = cols - w * 64;  // the EOL codeword's '1'
-        if (p < 64) e.t0 |= BIC_MSB >> p; else e.t1 = BIC_MSB;
-        e.tlen = p + 1;
-      }
-      e.len = e.z + e.tlen;
-#ifdef BIC_STAMPS
-      e.path = 1;
-#endif
-      return e;
-    }
-    if (khi == klo && khi <= 3) {
-#ifdef BIC_STAMPS
-      e.path = 2;
-#endif
-      const uint32_t k = khi, kmask = (1u << k) - 1u;
-      uint32_t c = w * 64 - (uint32_t)(jp + 1);  // zeros of the open run
-      bool first = true;
-      const uint32_t* T = lut.t12 + (k - 1) * 256;
-#pragma unroll
-      for (int b = 0; b < 8; ++b) {
-        const uint32_t v = (uint32_t)(x >> (56 - 8 * b)) & 0xffu;
-        if (v) {
-          uint32_t R, lr, t, tz;
-          if (k <= 2) {
-            const uint32_t en = T[v];
-            R = en & 0x1fffffu;
-            lr = (en >> 21) & 31u;
-            t = (en >> 26) & 7u;
-            tz = en >> 29;
-          } else {
-            const uint64_t en = lut.t3[v];
-            R = (uint32_t)en;
-            lr = (uint32_t)(en >> 32) & 63u;
-            t = (uint32_t)(en >> 40) & 15u;
-            tz = (uint32_t)(en >> 44) & 15u;
-          }
-          const uint32_t sr = c + t, q = sr >> k, bin = sr & kmask;
-          if constexpr (STR) {
-            if (first) {
-              e.head = bin;
-              e.k0 = k;
-              e.z = q;
-              tail_put(e, (1ull << lr) | R, 1 + lr);
-              first = false;
-            } else {
-              const uint32_t nb = k + q + 1;  // sr <= 63 here
-              if (nb + lr <= 64) {
-                tail_put(e, ((((uint64_t)bin << (q + 1)) | 1ull) << lr) | R, nb + lr);
-              } else {
-                tail_put(e, ((uint64_t)bin << (q + 1)) | 1ull, nb);
-                tail_put_n(e, R, lr);
-              }
-            }
-          }
-          e.len += k + q + 1 + lr;
-          c = tz;
-        } else {
-          c += 8;
-        }
-      }
-      if (eol) {  // the row's trailing zeros (pad columns excluded)
-        const uint32_t sr = c - (w * 64 + 64 - cols), q = sr >> k;
-        if constexpr (STR) tail_put(e, ((uint64_t)(sr & kmask) << (q + 1)) | 1ull, k + q + 1);
-        e.len += k + q + 1;
-      }
-      return e;
-    }
-  }
-  // k changes inside the word (or n = 0, the plane's first sample): one codeword at a time, the
-  // word's first one (binary part and unary zeros cut off: head, z) peeled off the loop, and
-  // A = arow + jp + 1 - n carried (A' = A + s as n' = n + 1). (Byte by byte with per-byte k bounds
-  // measured slower.)
-#ifdef BIC_STAMPS
-  e.path = 3;
-#endif
-  uint32_t A = arow + (uint32_t)(jp + 1) - n;
-  {
-    uint32_t s;
-    int j;
-    if (x) {
-      const int cz = __builtin_clzll(x);
-      x ^= BIC_MSB >> cz;
-      j = (int)(w * 64) + cz;
-      s = (uint32_t)(j - jp - 1);
-    } else {  // (eol: the row's end-of-row codeword alone)
-      j = (int)cols;
-      s = cols - 1 - (uint32_t)jp;
-      eol = false;
-    }
-    const uint32_t k = golomb_k_state(n, A);
-    const uint32_t q = s >> k;
-    if constexpr (STR) {
-      e.head = s & ((1u << k) - 1u);
-      e.k0 = k;
-      e.z = q;
-      tail_put(e, 1, 1);
-    }
-    e.len += k + q + 1;
-    A += s;
-    ++n;
-    jp = j;
-  }
-  while (x) {  // (n >= 1 from here; s <= 62: k + q + 1 <= 64)
-    const int cz = __builtin_clzll(x);
-    x ^= BIC_MSB >> cz;
-    const int j = (int)(w * 64) + cz;
-    const uint32_t s = (uint32_t)(j - jp - 1);
-    const uint32_t k = golomb_k(n, A), q = s >> k;
-    if constexpr (STR) tail_put(e, ((uint64_t)(s & ((1u << k) - 1u)) << (q + 1)) | 1ull, k + q + 1);
-    e.len += k + q + 1;
-    A += s;
-    ++n;
-    jp = j;
-  }
-  if (eol) {
-    const uint32_t s = cols - 1 - (uint32_t)jp;
-    const uint32_t k = golomb_k(n, A), q = s >> k;
-    if constexpr (STR) tail_put(e, ((uint64_t)(s & ((1u << k) - 1u)) << (q + 1)) | 1ull, k + q + 1);
-    e.len += k + q + 1;
-  }
-  return e;
-}
-
-// OR the nb (1..64) low bits of v into the 128-bit MSB-first string (t0, t1) at bit pos
-// (pos + nb <= 128 whenever v != 0), branch-free.
-__device__ __forceinline__ void or128(uint64_t& t0, uint64_t& t1, uint64_t v, uint32_t pos, uint32_t nb) {
-  const uint32_t end = pos + nb;
-  const uint64_t p0 = end <= 64 ? v << ((64 - end) & 63) : v >> ((end - 64) & 63);
-  t0 |= pos < 64 ? p0 : 0ull;
-  t1 |= end > 64 ? v << ((128 - end) & 63) : 0ull;
-}
-
-// encode_word for a row whose codewords all have k = 1 (kK1Row): no k bounds, no sample count, no
-// divergent paths. The first codeword (binary part in head, its q zeros in z) is cut off as in
-// encode_word; the rest goes byte by byte through the k = 1 table: byte i's first 1 closes the open
-// run (c zeros before the byte + t): its binary bit, q zeros, then the table's '1' + R -- one
-// pattern appended to a right-aligned 128-bit accumulator (two 64-bit shifts and an or); the word's
-// first byte appends '1' + R only. <= 128 bits except through long runs (then lng: placed by
-// emit_word_k1).
-__device__ __forceinline__ void acc_put(uint64_t& hi, uint64_t& lo, uint64_t pat, uint32_t nb) {  // nb 1..63
-  hi = (hi << nb) | (lo >> (64 - nb));
-  lo = (lo << nb) | pat;
-}
-__device__ __forceinline__ void acc_zeros(uint64_t& hi, uint64_t& lo, uint32_t nb) {  // nb <= 128
-  if (nb >= 64) {
-    hi = lo;
-    lo = 0;
-    nb -= 64;
-  }
-  if (nb) {
-    hi = (hi << nb) | (lo >> (64 - nb));
-    lo <<= nb;
-  }
-}
-// append bin, q zeros, then pat (np bits, 1..63): total 1 + q + np bits
-__device__ __forceinline__ void acc_codeword(uint64_t& hi, uint64_t& lo, uint32_t& p, uint32_t bin, uint32_t q,
-                                             uint64_t pat, uint32_t np) {
-  const uint32_t nb = 1 + q + np;
-  if (p + nb <= 128) {
-    if (nb <= 63) {
-      acc_put(hi, lo, ((uint64_t)bin << (nb - 1)) | pat, nb);
-    } else {
-      acc_put(hi, lo, bin, 1);
-      acc_zeros(hi, lo, q);
-      acc_put(hi, lo, pat, np);
-    }
-  }
-  p += nb;
-}
-
-__device__ __forceinline__ LaneEnc encode_word_k1(uint64_t x, uint32_t w, int jp, bool eol, uint32_t cols,
-                                                  const uint32_t* T1) {
-  LaneEnc e{};
-  e.k0 = 1;
-  uint32_t c = w * 64 - (uint32_t)(jp + 1);  // zeros of the open run
-  if (!x) {
-    if (eol) {
-      const uint32_t s = cols - 1 - (uint32_t)jp;
-      e.head = s & 1u;
-      e.z = s >> 1;
-      e.t0 = BIC_MSB;
-      e.tlen = 1;
-      e.len = 2 + e.z;
-    }
-    return e;
-  }
-  const uint32_t bf = (uint32_t)__builtin_clzll(x);
-  const uint32_t s1 = c + bf, fb = bf >> 3;
-  e.head = s1 & 1u;
-  e.z = s1 >> 1;
-  uint64_t hi = 0, lo = 0;
-  uint32_t p = 0;
-#pragma unroll
-  for (uint32_t i = 0; i < 8; ++i) {
-    const uint32_t v = (uint32_t)(x >> (56 - 8 * i)) & 0xffu;
-    if (v) {
-      const uint32_t en = T1[v];
-      const uint32_t R = en & 0x1fffffu, lr = (en >> 21) & 31u, t = (en >> 26) & 7u, tz = en >> 29;
-      const uint64_t pat = (1ull << lr) | R;
-      if (i == fb) {
-        acc_put(hi, lo, pat, lr + 1);
-        p += lr + 1;
-      } else {
-        const uint32_t s = c + t;
-        acc_codeword(hi, lo, p, s & 1u, s >> 1, pat, lr + 1);
-      }
-      c = tz;
-    } else {
-      c += 8;
-    }
-  }
-  if (eol) {  // the row's trailing zeros (pad columns excluded)
-    const uint32_t s = c - (w * 64 + 64 - cols);
-    acc_codeword(hi, lo, p, s & 1u, s >> 1, 1ull, 1);
-  }
-  e.tlen = p;
-  e.len = 1 + e.z + p;
-  e.lng = p > 128;
-  if (!e.lng) {  // left-align the p-bit string
-    const uint32_t sh = 128 - p;
-    if (sh >= 64) {
-      e.t0 = lo << (sh - 64);
-      e.t1 = 0;
-    } else if (sh) {
-      e.t0 = (hi << sh) | (lo >> (64 - sh));
-      e.t1 = lo << sh;
-    } else {
-      e.t0 = hi;
-      e.t1 = lo;
-    }
-  }
-  return e;
-}
-
-// encode_word_k1 without branches: every byte runs the same instructions (its codeword from the k = 1
-// table whether or not it holds a 1, selected in or out), so a wave never executes divergent paths.
-// Inside a word a run's zeros are < 64 + 7, so a byte's pattern (bin, q zeros, '1', R) is < 64 bits;
-// out-of-range shift amounts of unselected bytes are clamped.
-__device__ __forceinline__ LaneEnc encode_word_k1b(uint64_t x, uint32_t w, int jp, bool eol, uint32_t cols,
-                                                   const uint32_t* T1) {
-  LaneEnc e{};
-  e.k0 = 1;
-  uint32_t c = w * 64 - (uint32_t)(jp + 1);  // zeros of the open run
-  if (!x) {
-    if (eol) {
-      const uint32_t s = cols - 1 - (uint32_t)jp;
-      e.head = s & 1u;
-      e.z = s >> 1;
-      e.t0 = BIC_MSB;
-      e.tlen = 1;
-      e.len = 2 + e.z;
-    }
-    return e;
-  }
-  const uint32_t bf = (uint32_t)__builtin_clzll(x), fb = bf >> 3;
-  const uint32_t s1 = c + bf;
-  e.head = s1 & 1u;
-  e.z = s1 >> 1;
-  uint64_t hi = 0, lo = 0;
-  uint32_t p = 0;
-#pragma unroll
-  for (uint32_t i = 0; i < 8; ++i) {
-    const uint32_t v = (uint32_t)(x >> (56 - 8 * i)) & 0xffu;
-    const uint32_t en = T1[v];
-    const uint32_t R = en & 0x1fffffu, lr = (en >> 21) & 31u, t = (en >> 26) & 7u, tz = en >> 29;
-    const uint32_t sr = c + t;
-    const uint32_t q1 = min((sr >> 1) + 1u, 62u - lr);  // the '1' after q zeros, then R
-    const uint64_t tail = (1ull << lr) | R;
-    const bool first = i == fb;
-    const uint64_t pat = first ? tail : ((uint64_t)(sr & 1u) << (q1 + lr)) | tail;
-    const uint32_t nb = first ? lr + 1 : q1 + 1 + lr;  // 1..63
-    const bool act = v != 0;
-    const uint64_t nhi = (hi << nb) | (lo >> (64 - nb));
-    const uint64_t nlo = (lo << nb) | pat;
-    hi = act ? nhi : hi;
-    lo = act ? nlo : lo;
-    p += act ? nb : 0u;
-    c = act ? tz : c + 8;
-  }
-  if (eol) {  // the row's trailing zeros (pad columns excluded): bin, q zeros, '1' (< 64 bits)
-    const uint32_t sr = c - (w * 64 + 64 - cols), q1 = (sr >> 1) + 1;
-    const uint32_t nb = q1 + 1;
-    const uint64_t pat = ((uint64_t)(sr & 1u) << q1) | 1ull;
-    hi = (hi << nb) | (lo >> (64 - nb));
-    lo = (lo << nb) | pat;
-    p += nb;
-  }
-  e.tlen = p;
-  e.len = 1 + e.z + p;
-  e.lng = p > 128;
-  if (!e.lng) {  // left-align the p-bit string
-    const uint32_t sh = 128 - p;
-    if (sh >= 64) {
-      e.t0 = lo << (sh - 64);
-      e.t1 = 0;
-    } else if (sh) {
-      e.t0 = (hi << sh) | (lo >> (64 - sh));
-      e.t1 = lo << sh;
-    } else {
-      e.t0 = hi;
-      e.t1 = lo;
-    }
-  }
-  return e;
-}
-
-__device__ __forceinline__ void place128_64(uint64_t* img, uint32_t off, uint64_t A, uint64_t B, uint32_t tlen) {
-  if (!tlen) return;
-  const uint32_t i = off >> 6, sh = off & 63;
-  uint64_t D0 = A, D1 = B, D2 = 0;
-  if (sh) {
-    D0 = A >> sh;
-    D1 = (A << (64 - sh)) | (B >> sh);
-    D2 = B << (64 - sh);
-  }
-  const uint32_t nw = (sh + tlen + 63) >> 6;
-  lds_or64(img, i, D0);
-  if (nw > 1) lds_or64(img, i + 1, D1);
-  if (nw > 2) lds_or64(img, i + 2, D2);
-}
-struct LdsSink64 {
-  uint64_t* buf;
-  uint32_t idx;
-  uint64_t cur;
-  __device__ __forceinline__ void flush() {
-    if (cur) atomicOr(reinterpret_cast<unsigned long long*>(buf + idx), (unsigned long long)cur);
-    cur = 0;
-  }
-  __device__ __forceinline__ void orw(uint32_t i, uint64_t v) {
-    if (i != idx) {
-      flush();
-      idx = i;
-    }
-    cur |= v;
-  }
-  __device__ __forceinline__ void put(uint32_t off, uint32_t v, uint32_t nb) {  // nb <= 32
-    const uint32_t i = off >> 6, sh = off & 63;
-    if (sh + nb <= 64) {
-      orw(i, (uint64_t)v << (64 - sh - nb));
-    } else {
-      orw(i, (uint64_t)v >> (sh + nb - 64));
-      orw(i + 1, (uint64_t)v << (128 - sh - nb));
-    }
-  }
-  __device__ __forceinline__ void bit(uint32_t off) { orw(off >> 6, BIC_MSB >> (off & 63)); }
-};
-
-// emit_word for k = 1 rows (the lng fallback of encode_word_k1).
-template <typename Sink, typename Off>
-__device__ __forceinline__ void emit_word_k1(Sink& sk, Off off, uint64_t x, uint32_t w, int jp, bool eol, uint32_t cols) {
-  for (;;) {
-    int j;
-    uint32_t s;
-    if (x) {
-      const int cz = __builtin_clzll(x);
-      x ^= BIC_MSB >> cz;
-      j = (int)(w * 64) + cz;
-      s = (uint32_t)(j - jp - 1);
-    } else if (eol) {
-      j = (int)cols;
-      s = cols - 1 - (uint32_t)jp;
-      eol = false;
-    } else {
-      break;
-    }
-    if (s & 1u) sk.put(off, 1u, 1);
-    sk.bit(off + 1 + (s >> 1));
-    off += 2 + (s >> 1);
-    jp = j;
-  }
-}
-
-// Emit one word's codewords through a sink at bit offset `off` (fallback paths).
-template <typename Sink, typename Off>
-__device__ __forceinline__ void emit_word(Sink& sk, Off off, uint64_t x, uint32_t w, uint32_t n, int jp,
-                                          uint32_t arow, bool eol, uint32_t cols) {
-  for (;;) {
-    int j;
-    uint32_t s;
-    if (x) {
-      const int cz = __builtin_clzll(x);
-      x ^= BIC_MSB >> cz;
-      j = (int)(w * 64) + cz;
-      s = (uint32_t)(j - jp - 1);
-    } else if (eol) {
-      j = (int)cols;
-      s = cols - 1 - (uint32_t)jp;
-      eol = false;
-    } else {
-      break;
-    }
-    const uint32_t k = golomb_k_state(n, arow + (uint32_t)(jp + 1) - n);
-    if (k) {
-      const uint32_t bin = s & ((1u << k) - 1u);
-      if (bin) sk.put(off, bin, k);
-    }
-    sk.bit(off + k + (s >> k));
-    off += k + (s >> k) + 1;
-    ++n;
-    jp = j;
-  }
-}
-
-__device__ __forceinline__ void lds_or(uint32_t* img, uint32_t i, uint32_t v) {
-  if (v) atomicOr(&img[i], v);
-}
-
-// OR tlen (<= 128) bits (A:B, MSB-first) into the image at bit `off`.
-__device__ __forceinline__ void place128(uint32_t* img, uint32_t off, uint64_t A, uint64_t B, uint32_t tlen) {
-  if (!tlen) return;
-  const uint32_t i = off >> 5, sh = off & 31;
-  uint64_t D0 = A, D1 = B, D2 = 0;
-  if (sh) {
-    D0 = A >> sh;
-    D1 = (A << (64 - sh)) | (B >> sh);
-    D2 = B << (64 - sh);
-  }
-  const uint32_t nw = (sh + tlen + 31) >> 5;
-  lds_or(img, i, (uint32_t)(D0 >> 32));
-  if (nw > 1) lds_or(img, i + 1, (uint32_t)D0);
-  if (nw > 2) lds_or(img, i + 2, (uint32_t)(D1 >> 32));
-  if (nw > 3) lds_or(img, i + 3, (uint32_t)D1);
-  if (nw > 4) lds_or(img, i + 4, (uint32_t)(D2 >> 32));
-}
-
-__device__ __forceinline__ void place_small(uint32_t* img, uint32_t off, uint32_t v, uint32_t nb) {
-  if (!nb || !v) return;
-  const uint32_t i = off >> 5, sh = off & 31;
-  if (sh + nb <= 32) {
-    lds_or(img, i, v << (32 - sh - nb));
-  } else {
-    lds_or(img, i, v >> (sh + nb - 32));
-    lds_or(img, i + 1, v << (64 - sh - nb));
-  }
-}
-
-// 64 image bits starting at bit a (a may be negative: leading zeros).
-__device__ __forceinline__ uint64_t raw64(const uint32_t* img, int64_t a) {
-  if (a <= -64) return 0;
-  const int64_t b = a < 0 ? 0 : a;
-  const uint32_t i = (uint32_t)(b >> 5), sh = (uint32_t)(b & 31);
-  const uint64_t hi = ((uint64_t)img[i] << 32) | img[i + 1];
-  const uint64_t v = sh ? (hi << sh) | (img[i + 2] >> (32 - sh)) : hi;
-  return a < 0 ? v >> (-a) : v;
-}
-
-// Same, of the image with a '0' inserted at position ins (ins < 0: no insertion).
-__device__ __forceinline__ uint64_t img64(const uint32_t* img, int64_t a, int64_t ins) {
-  if (ins < 0 || ins >= a + 64) return raw64(img, a);
-  const uint64_t Y = raw64(img, a - 1);
-  if (ins < a) return Y;
-  const uint32_t q = (uint32_t)(ins - a);
-  const uint64_t X = raw64(img, a);
-  const uint64_t hi = q ? ~(~0ull >> q) : 0ull;
-  const uint64_t lo = q == 63 ? 0ull : (~0ull >> (q + 1));
-  return (X & hi) | (Y & lo);
-}
-
-// Is output word w entirely inside the row's bit range [G, G+L)?
-__device__ __forceinline__ bool word_complete(uint64_t w, uint64_t G, uint64_t L) {
-  return w * 64 >= G && w * 64 + 64 <= G + L;
-}
-
-// A word the row shares with a neighbouring row: into the fragment table (k_fixup combines them).
-__device__ __forceinline__ void put_shared(uint64_t* out, uint64_t wi, uint64_t* frag, int which, uint64_t v) {
-  (void)out;
-  (void)wi;
-  frag[which] = v;
-}
-
-// Write a row image of L bits to absolute bit G of out (threads tid of nt: a wave's lanes by
-// default): whole words with plain stores, the
-// first/last word (when shared with another row) into frag[0]/frag[1]. Output word t of the row
-// holds image bits [64t - G%64, 64t - G%64 + 64): the bit shift inside the image's u32 words is
-// the same for every t, so the common case (no inserted bit) is three LDS reads and a funnel
-// shift per word, branch-free and independent across iterations.
-__device__ __forceinline__ void write_row(const uint32_t* img, uint64_t L, uint64_t G, int64_t ins,
-                                          uint64_t* out, uint64_t* frag, uint32_t tid = lane_id(), uint32_t nt = 64) {
-  const uint64_t w0 = G >> 6, w1 = (G + L - 1) >> 6, nw = w1 - w0 + 1;
-  if (ins >= 0) {
-    for (uint64_t t = tid; t < nw; t += nt) {
-      const uint64_t wb = (w0 + t) * 64;
-      const uint64_t v = img64(img, (int64_t)wb - (int64_t)G, ins);
-      if (word_complete(w0 + t, G, L)) out[w0 + t] = bswap64(v);
-      else put_shared(out, w0 + t, frag, t == 0 ? 0 : 1, v);
-    }
-    return;
-  }
-  const uint32_t g = (uint32_t)(G & 63);
-  for (uint32_t t = tid; t < (uint32_t)nw; t += nt) {
-    const int32_t a = (int32_t)(64 * t) - (int32_t)g;  // first image bit of output word t
-    const uint32_t b = a < 0 ? 0u : (uint32_t)a;
-    const uint32_t i = b >> 5, sh = b & 31;
-    const uint64_t hi = ((uint64_t)img[i] << 32) | img[i + 1];
-    uint64_t v = (hi << sh) | ((uint64_t)img[i + 2] >> (32 - sh));
-    if (a < 0) v >>= -a;
-    if (t != 0 && t != (uint32_t)nw - 1) out[w0 + t] = bswap64(v);
-    else if (word_complete(w0 + t, G, L)) out[w0 + t] = bswap64(v);
-    else put_shared(out, w0 + t, frag, t == 0 ? 0 : 1, v);
-  }
-}
-
-// glen[] flags of the staged encoder (set by the prefix kernels, read-only afterwards: every
-// consumer masks them off, so the two emission launches never write glen)
-constexpr uint64_t kK0Row = 1ull << 63;  // every codeword of the row has k = 0
-constexpr uint64_t kK1Row = 1ull << 62;  // every codeword of the row has k = 1
-constexpr uint64_t kLenMask = (1ull << 60) - 1;
-
-struct FusedArgs {
-  Geom g;
-  const uint64_t* planes;
-  const uint64_t* lut;  // byte tables (see ByteTables): [256] u64 for k = 3, then [2][256] u32
-  uint32_t* counter;   // zeroed per launch
-  uint64_t* ones_rec;  // zeroed per launch
-  uint64_t* bits_rec;  // zeroed per launch
-  uint64_t *gboff, *glen, *gfrag, *gslow;
-  uint64_t *eboff, *elen, *efrag;
-  uint32_t* row_o;     // two-pass / staged encoders: ones of the plane before each row
-  uint32_t* sones;     // staged encoder: per (plane, row, strip) 1-counts and k statistics
-  int4* krec;
-  uint32_t* kpos;
-  uint32_t ns;         // strips per row
-  uint32_t* walk_ids;  // staged encoder: rows k_row_walk walks (count in counter[2])
-  uint32_t* rest_ids;  // staged encoder: rows the REST emit launch writes (count in counter[3])
-  uint32_t* slow_n;    // number of rows k_rows_global must write (zeroed per launch)
-  uint64_t* slow_ids;  // their row ids
-  uint64_t* out_g;
-  uint64_t slot_g;
-  uint64_t* bits_g;
-  uint64_t* out_e;
-  uint64_t slot_e;
-  uint64_t* bits_e;
-  uint32_t* flags;
-  // packed output (FusedScratch::off_g / off_e): per-plane totals of residual 1s (ONES scan), the
-  // planes' packed start words (k_plane_bases) and EG start bits; ebase null: slot mode
-  uint64_t* pones;
-  uint64_t* gbase;
-  uint64_t* ebase;
-  uint64_t* off_g;
-  uint64_t* off_e;
-  uint64_t* index;  // FusedScratch::index
-  // bic_encode_gray without planes (FusedScratch::eg_src): the count pass wrote the EG stream in its
-  // uniform layout and the residual rows are read back from it (null: residual from planes)
-  const uint64_t* esrc;
-  uint64_t* efix;
-  uint64_t* cls;  // FusedScratch::cls (EG source: the class emission kernels' row lists, (id, offset)
-                  // pairs; the class kernels store as unsigned long long, a type apart, so the compiler
-                  // keeps these loads on the scalar cache: no wait on the vector memory counter)
-  uint64_t* sink;     // FusedScratch::sink
-  uint32_t* walk_o;   // FusedScratch::walk_o (the walked rows' row_o)
-#ifdef BIC_STAMPS
-  int known;
-#endif
-};
-
-// A row's absolute Golomb bit offset: gboff holds it relative to the plane's slot start (LEN scan);
-// packed output moves the plane to its packed start word gbase[plane]
-__device__ __forceinline__ uint64_t gb_abs(const FusedArgs& a, uint64_t id, uint32_t plane) {
-  const uint64_t G = a.gboff[id];
-  return a.off_g ? G - (uint64_t)plane * a.slot_g * 64 + a.gbase[plane] * 64 : G;
-}
-
-// ---- residual rows read back from the EG stream (FusedArgs::esrc) ------------------------------
-// bic_encode_gray without planes: the count pass (k_gray_strips, EGS) writes each plane's EG stream
-// (eg.cpp:20-37 with the block size fixed at 1: per row ~R, then the end-of-row '1') in its uniform
-// layout -- bit 0 a '1', row r at bit r (cols + 1) + 1 -- instead of storing R: that layout is the
-// stream itself but for ONE bit, cleared after the emission (eg_fix_bit). Every reader of R takes
-// the row from there: ~(64 stream bits at the row's offset + 64 w), a wave-uniform funnel shift.
-__device__ __forceinline__ uint64_t eg_src_bit0(const Geom& g, uint32_t row) {
-  return (uint64_t)row * (g.cols + 1) + 1;
-}
-// residual word w of a row (any lane pattern; two loads, the second one usually a cache hit)
-__device__ __forceinline__ uint64_t eg_src_word(const uint64_t* eplane, const Geom& g, uint32_t row, uint32_t w) {
-  if (w >= g.used) return 0;
-  const uint64_t b = eg_src_bit0(g, row) + (uint64_t)w * 64;
-  const uint64_t* p = eplane + (b >> 6);
-  const uint32_t sh = (uint32_t)(b & 63);
-  const uint64_t hi = bswap64(p[0]);
-  const uint64_t x = sh ? funnel64(hi, bswap64(p[1]), 64 - sh) : hi;
-  return ~x & (w == g.used - 1 ? g.trail : ~0ull);
-}
-// the row's words t * 64 + lane (t < WPL) as resid_row gives them: one load per word, lane l + 1's word
-// through DPP (wave_shl:1), lane 63's from lane 0 of the next word group (the last: one uniform load)
-// (as two halves, so that a wave can issue a row's loads one row ahead: eg_src_load, then
-// eg_src_assemble when the words are needed)
-template <int WPL>
-__device__ __forceinline__ void eg_src_load(const uint64_t* eplane, const Geom& g, uint32_t row, uint64_t (&v)[WPL],
-                                            uint64_t& last) {
-  const int lane = lane_id();
-  const uint64_t b = eg_src_bit0(g, row);
-  const uint64_t* p = eplane + (b >> 6);
-  const uint32_t nw = g.used;  // stream words used: nw (+ 1 when the row is not word-aligned)
-#pragma unroll
-  for (int t = 0; t < WPL; ++t) {  // (every lane loads, at a clamped index: eg_src_assemble masks)
-    const uint32_t j = t * 64 + lane;
-    v[t] = p[j < nw ? j : nw - 1];
-  }
-  last = p[(b & 63) ? nw : nw - 1];  // (uniform address; unused when the row is word-aligned)
-}
-template <int WPL>
-__device__ __forceinline__ void eg_src_assemble(const Geom& g, uint32_t row, const uint64_t (&v)[WPL], uint64_t last,
-                                                uint64_t (&r)[WPL]) {
-  const int lane = lane_id();
-  const uint32_t sh = (uint32_t)(eg_src_bit0(g, row) & 63);
-  const uint32_t nw = g.used;
-#pragma unroll
-  for (int t = 0; t < WPL; ++t) {
-    const uint32_t j = t * 64 + lane;
-    const uint64_t hi = bswap64(v[t]);
-    uint64_t nx = ((uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v[t] >> 32), 0x130, 0xf, 0xf, true) << 32) |
-                  (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v[t], 0x130, 0xf, 0xf, true);
-    if (lane == 63) {
-      if (t + 1 < WPL && (t + 1) * 64 < (int)nw)
-        nx = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v[t + 1 < WPL ? t + 1 : t] >> 32), 0) << 32) |
-             (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v[t + 1 < WPL ? t + 1 : t], 0);
-      else
-        nx = last;
-    }
-    // (lane j + 1's word is its clamped load when j + 1 >= nw: only its bits past the row are used)
-    const uint64_t x = sh ? funnel64(hi, bswap64(nx), 64 - sh) : hi;
-    r[t] = j < nw ? ~x & (j == nw - 1 ? g.trail : ~0ull) : 0;
-  }
-}
-// the row's words t * 64 + lane (t < WPL) as resid_row gives them: one load per word, lane l + 1's word
-// through DPP (wave_shl:1), lane 63's from lane 0 of the next word group (the last: one uniform load)
-template <int WPL>
-__device__ __forceinline__ void eg_src_row(const uint64_t* eplane, const Geom& g, uint32_t row, uint64_t (&r)[WPL]) {
-  uint64_t v[WPL], last;
-  eg_src_load<WPL>(eplane, g, row, v, last);
-  eg_src_assemble<WPL>(g, row, v, last, r);
-}
-
-// The row's words with lane l holding words l WPL .. l WPL + WPL - 1 (consecutive: one prefix per
-// lane over its own words, one wave scan per row instead of one per word group): WPL + 1 loads
-// per lane, the last one lane l + 1's first (clamped: masked in the assembly)
-template <int WPL>
-__device__ __forceinline__ void eg_src_load_lc(const uint64_t* eplane, const Geom& g, uint32_t row,
-                                               uint64_t (&v)[WPL + 1]) {
-  const uint64_t b = eg_src_bit0(g, row);
-  const uint64_t* p = eplane + (b >> 6);
-  const uint32_t jmax = (b & 63) ? g.used : g.used - 1;
-#pragma unroll
-  for (int t = 0; t <= WPL; ++t) {
-    const uint32_t j = (uint32_t)lane_id() * WPL + t;
-    v[t] = p[j < jmax ? j : jmax];
-  }
-}
-template <int WPL>
-__device__ __forceinline__ void eg_src_assemble_lc(const Geom& g, uint32_t row, const uint64_t (&v)[WPL + 1],
-                                                   uint64_t (&r)[WPL]) {
-  const uint32_t sh = (uint32_t)(eg_src_bit0(g, row) & 63);
-#pragma unroll
-  for (int t = 0; t < WPL; ++t) {
-    const uint32_t w = (uint32_t)lane_id() * WPL + t;
-    const uint64_t hi = bswap64(v[t]);
-    const uint64_t x = sh ? funnel64(hi, bswap64(v[t + 1]), 64 - sh) : hi;
-    r[t] = w < g.used ? ~x & (w == g.used - 1 ? g.trail : ~0ull) : 0;
-  }
-}
-
-// Global-memory emission for a row whose Golomb image does not fit the LDS window: codeword
-// bits landing in the row's first/last output word are kept for the fragment table, the rest
-// is OR'd into words this wave zeroed first.
-struct FragSink {
-  unsigned long long* out;
-  uint64_t wh, wt;
-  bool hpart, tpart;
-  uint64_t acc_h, acc_t;
-  uint64_t idx, cur;
-  __device__ __forceinline__ void flush() {
-    if (!cur) return;
-    if (idx == wh && hpart) acc_h |= cur;
-    else if (idx == wt && tpart) acc_t |= cur;
-    else atomicOr(&out[idx], (unsigned long long)bswap64(cur));
-    cur = 0;
-  }
-  __device__ __forceinline__ void orw(uint64_t i, uint64_t v) {
-    if (i != idx) { flush(); idx = i; }
-    cur |= v;
-  }
-  __device__ __forceinline__ void put(uint64_t off, uint32_t v, uint32_t nb) {
-    const uint64_t i = off >> 6;
-    const uint32_t sh = (uint32_t)(off & 63);
-    if (sh + nb <= 64) {
-      orw(i, (uint64_t)v << (64 - sh - nb));
-    } else {
-      orw(i, (uint64_t)v >> (sh + nb - 64));
-      orw(i + 1, (uint64_t)v << (128 - sh - nb));
-    }
-  }
-  __device__ __forceinline__ void bit(uint64_t off) { orw(off >> 6, BIC_MSB >> (off & 63)); }
-};
-
-// The residual word w of the row, read back from the EG image (~R, pad-masked): the image is
-// written for every row, so the Golomb steps need no registers for the row.
-__device__ __forceinline__ uint64_t img_resid(const uint32_t* eimg, const Geom& g, uint32_t w) {
-  if (w >= g.used) return 0;
-  const uint64_t v = ((uint64_t)eimg[2 * w] << 32) | eimg[2 * w + 1];
-  return ~v & (w == g.used - 1 ? g.trail : ~0ull);
-}
-
-// Rows whose Golomb output exceeds the LDS window (a long dense stretch at large k): the main
-// kernel records their offset and sample base and appends them to a list; k_rows_global (a small
-// grid walking that list, one wave per row) recomputes each and writes it straight to global
-// memory -- its inner words are zeroed and OR'd, the bits landing in its first/last (shared) word
-// go to the fragment table.
-// (row_global_at: the row's absolute offset G, length L and slow = its samples before + 1 given)
-template <bool PREDICT>
-__device__ __forceinline__ void row_global_at(const FusedArgs& a, uint64_t id, uint32_t plane, uint32_t row,
-                                              uint64_t G, uint64_t L, uint64_t slow, int lane) {
-  const Geom& g = a.g;
-  uint64_t* frag = a.gfrag + 2 * id;
-  const uint64_t wh = G >> 6, wt = (G + L - 1) >> 6;
-  const bool hpart = !word_complete(wh, G, L);
-  const bool tpart = !word_complete(wt, G, L);
-  for (uint64_t i = wh + lane; i <= wt; i += 64)
-    if (!((i == wh && hpart) || (i == wt && tpart))) a.out_g[i] = 0;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  FragSink fs{reinterpret_cast<unsigned long long*>(a.out_g), wh, wt, hpart, tpart, 0, 0, 0, 0};
-  StepState st{(uint32_t)(slow - 1), -1};
-  const uint32_t arow = row * (g.cols + 1);
-  RowCtx rc = row_ctx(a.planes, g, plane, row, 0);
-  uint64_t carry = G;
-  for (uint32_t w0 = 0; w0 < g.used; w0 += 64) {
-    const uint32_t w = w0 + lane;
-    const uint64_t x = (!PREDICT && a.esrc) ? eg_src_word(a.esrc + (uint64_t)plane * a.slot_e, g, row, w)
-                                            : resid_word<PREDICT>(rc, g, row, w);
-    uint32_t n;
-    int jp;
-    step_prefix(x, w, st, n, jp);
-    const bool eol = w == g.used - 1;
-    const LaneEnc e = encode_word<false>(x, w, n, jp, arow, eol, g.cols,
-                                         ByteTables{reinterpret_cast<const uint32_t*>(a.lut + 256), a.lut});
-    const uint32_t inc = wave_incl_sum_u32(e.len);
-    const uint64_t off = carry + inc - e.len;
-    carry += lane63_u32(inc);
-    emit_word(fs, off, x, w, n, jp, arow, eol, g.cols);
-  }
-  fs.flush();
-  uint64_t h = fs.acc_h, tl = fs.acc_t;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    h |= shfl_u64(h, lane ^ d);
-    tl |= shfl_u64(tl, lane ^ d);
-  }
-  if (lane == 0) {
-    if (hpart) put_shared(a.out_g, wh, frag, 0, h | (wh == wt ? tl : 0));
-    if (tpart && wt != wh) put_shared(a.out_g, wt, frag, 1, tl);
-  }
-}
-template <bool PREDICT>
-__device__ __forceinline__ void row_global(const FusedArgs& a, uint64_t id, int lane) {
-  const Geom& g = a.g;
-  const uint32_t plane = (uint32_t)(id / g.rows), row = (uint32_t)(id % g.rows);
-  row_global_at<PREDICT>(a, id, plane, row, gb_abs(a, id, plane), a.glen[id] & kLenMask, a.gslow[id], lane);
-}
-
-// EG source: after every reader of the residual rows, the one bit per plane in which the uniform
-// layout differs from the EG stream (eg_src_junctions' ONES scan found it: the first 1's bit, or the
-// layout's bit past the end of a plane without 1s) is cleared. The readers are the Golomb emission
-// (k_emit_k01 / k_emit_known, k_emit_rest) and the slow rows (k_rows_global, or k_emit_rest's own
-// loop on the class kernels' path), so with the Golomb stream requested the clear is k_fixup's (block
-// 0, launched after both); without it nothing reads the rows and k_rows_global's one block does it.
-__device__ __forceinline__ void eg_fix_bit(const uint64_t* efix, uint64_t* out_e, uint64_t slot_e, uint32_t nplanes) {
-  if (!efix || blockIdx.x != 0 || threadIdx.x >= nplanes) return;
-  const uint64_t P = efix[threadIdx.x];
-  uint64_t* w = out_e + (uint64_t)threadIdx.x * slot_e + (P >> 6);
-  *w &= ~bswap64(BIC_MSB >> (P & 63));
-}
 
 template <bool PREDICT>
 __global__ __launch_bounds__(256) void k_rows_global(FusedArgs a) {
@@ -934,520 +19,6 @@ __global__ __launch_bounds__(256) void k_rows_global(FusedArgs a) {
   const uint32_t nslow = *a.slow_n;
   for (uint32_t li = blockIdx.x * 4 + wave_id(); li < nslow; li += gridDim.x * 4)
     row_global<PREDICT>(a, a.slow_ids[li], lane);
-}
-
-// One workgroup = one TILE of kTileRows consecutive rows of one plane (one wave per row). Tiles
-// are claimed in order through one atomic ticket counter with the planes interleaved (tile t ->
-// plane t % nplanes), so the planes' look-back chains advance side by side and any idle CU takes
-// the oldest pending tile of any plane; one look-back per tile (by wave 0) serves its rows, which
-// combine their counts through LDS. (Per-plane counters bound to blockIdx were measured slower:
-// 793-918 us vs 682 us for C3, the claims themselves are not the limit.)
-template <int WPL, bool PREDICT, bool DO_G, bool DO_E>
-__global__ __launch_bounds__(64 * kTileRows, 8) void k_encode_rows(FusedArgs a) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[kTileRows * (kGImg + kEImg)];
-  __shared__ uint64_t sh_cnt[kTileRows], sh_len[kTileRows], sh_pre[2];
-  __shared__ uint32_t sh_tile;
-  __shared__ uint32_t s_lut[512];  // k = 1, 2 byte tables
-  const Geom& g = a.g;
-  // (the wave index left divergent here: as a scalar the compiler re-schedules this kernel's row loop
-  // and C2 measured 0.032 -> 0.033-0.035 ms)
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  uint32_t* gimg = lds + wave * (kGImg + kEImg);
-  uint32_t* eimg = gimg + kGImg;
-  const uint32_t tpp = (g.rows + kTileRows - 1) / kTileRows;  // tiles per plane
-  if (threadIdx.x == 0) sh_tile = atomicAdd(a.counter, 1u);
-  if (threadIdx.x < 512) s_lut[threadIdx.x] = reinterpret_cast<const uint32_t*>(a.lut + 256)[threadIdx.x];
-  __syncthreads();
-  const uint64_t tile = sh_tile;
-  if (tile >= (uint64_t)tpp * g.nplanes) return;  // uniform over the workgroup
-  const uint32_t plane = (uint32_t)(tile % g.nplanes), trow = (uint32_t)(tile / g.nplanes);
-  const uint64_t rbase = (uint64_t)plane * tpp;  // this plane's first tile record
-  const uint64_t rid = rbase + trow;             // this tile's record
-  const uint32_t row = trow * kTileRows + wave;
-  const bool valid = row < g.rows;
-  const uint64_t id = (uint64_t)plane * g.rows + row;  // per-row output records
-  STAMP(0);
-
-  // ---- residual row -> EG image (~R, pad-masked, EOL '1'); 1-count; first 1 ----------------
-  uint32_t ones = 0;
-  int fcol = INT_MAX;
-  if (valid) {
-    if constexpr (DO_G) lds_image_zero32(gimg, kGImg / 4);  // the Golomb image (row loads in flight)
-    uint64_t rr[WPL];
-    resid_row<WPL, PREDICT>(a.planes, g, plane, row, rr);
-#pragma unroll
-    for (int t = 0; t < WPL; ++t) {
-      const uint32_t w = t * 64 + lane;
-      const uint64_t r = rr[t];
-      ones += (uint32_t)__popcll(r);
-      if (r && fcol == INT_MAX) fcol = (int)(w * 64 + __builtin_clzll(r));
-      if (w < g.used) {
-        const uint64_t v = ~r & (w == g.used - 1 ? g.trail : ~0ull);
-        eimg[2 * w] = (uint32_t)(v >> 32);
-        eimg[2 * w + 1] = (uint32_t)v;
-      }
-    }
-    if (lane < kPad + 1) eimg[2 * g.used + lane] = 0;
-    ones = wave_sum_u32(ones);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) eimg[g.cols >> 5] |= 0x80000000u >> (g.cols & 31);  // EOL '1'
-  }
-  STAMP(1);
-  if (lane == 0) sh_cnt[wave] = ones;
-  __syncthreads();
-
-  // ---- samples before this row: ones of earlier rows (+ one EOL sample per row) ----
-#ifdef BIC_STAMPS
-  if (a.known) {
-    if (threadIdx.x == 0) sh_pre[0] = g_known[0][rid];
-  } else
-#endif
-  if (wave == 0) {
-    uint64_t tile_ones = 0;
-    for (int q = 0; q < kTileRows; ++q) tile_ones += sh_cnt[q];
-    uint64_t O = 0;
-    if (trow == 0) {
-      if (lane == 0) rec_store(&a.ones_rec[rid], kInc | tile_ones);
-    } else {
-      if (lane == 0) rec_store(&a.ones_rec[rid], kAgg | tile_ones);
-      O = lookback(a.ones_rec, rbase, rid, a.flags);
-      if (lane == 0) rec_store(&a.ones_rec[rid], kInc | (O + tile_ones));
-    }
-    if (lane == 0) sh_pre[0] = O;
-#ifdef BIC_STAMPS
-    if (lane == 0 && rid < (1u << 17)) g_known[0][rid] = O;
-#endif
-  }
-  __syncthreads();
-  STAMP(2);
-  uint64_t O = sh_pre[0];
-  for (int q = 0; q < wave; ++q) O += sh_cnt[q];
-
-  // ---- Golomb length of the row (word_len: no codewords formed), published for the tile at once:
-  // the tiles after this one find its bit count before its codewords exist, so the bit-offset
-  // look-back does not wait on any tile's emission. Wave 0 looks back while the others emit. ----
-  uint64_t L = 0;
-  if constexpr (DO_G) {
-    if (valid) {
-      StepState st{(uint32_t)(O + row), -1};
-      const uint32_t arow = row * (g.cols + 1);
-      uint32_t ll = 0;
-      for (uint32_t w0 = 0; w0 < g.used; w0 += 64) {
-        const uint32_t w = w0 + lane;
-        const uint64_t x = img_resid(eimg, g, w);
-        uint32_t n;
-        int jp;
-        step_prefix(x, w, st, n, jp);
-        uint32_t kor = 0;
-        ll += word_len(x, w, n, jp, arow, w == g.used - 1, g.cols, kor);
-      }
-      L = wave_sum_u32(ll);
-    }
-    if (lane == 0) sh_len[wave] = L;
-    __syncthreads();
-#ifdef BIC_STAMPS
-    if (a.known) {
-      if (threadIdx.x == 0) sh_pre[1] = g_known[1][rid];
-    } else
-#endif
-    if (wave == 0) {
-      uint64_t tile_bits = 0;
-      for (int q = 0; q < kTileRows; ++q) tile_bits += sh_len[q];
-      uint64_t Gt = 0;
-      if (trow == 0) {
-        if (lane == 0) rec_store(&a.bits_rec[rid], kInc | tile_bits);
-      } else {
-        if (lane == 0) rec_store(&a.bits_rec[rid], kAgg | tile_bits);
-        Gt = lookback(a.bits_rec, rbase, rid, a.flags);
-        if (lane == 0) rec_store(&a.bits_rec[rid], kInc | (Gt + tile_bits));
-      }
-      if (lane == 0) sh_pre[1] = Gt;
-#ifdef BIC_STAMPS
-      if (lane == 0 && rid < (1u << 17)) g_known[1][rid] = Gt;
-#endif
-    }
-  }
-
-  // ---- EG as written (eg.cpp:20-37): per row ~R then '1'; a '0' after the plane's first 1 ----
-  if (DO_E && valid) {
-    const bool f_here = O == 0 && ones > 0;
-    fcol = wave_min(fcol);
-    const uint64_t Le = (uint64_t)g.cols + 1 + (f_here ? 1 : 0);
-    const uint64_t Ge_rel = (uint64_t)row * (g.cols + 1) + (O > 0 ? 1 : 0);
-    const uint64_t cap = a.slot_e * 64;
-    const uint64_t Ge = (uint64_t)plane * cap + Ge_rel;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (Ge_rel + Le <= cap) {
-      write_row(eimg, Le, Ge, f_here ? (int64_t)fcol + 1 : -1, a.out_e, a.efrag + 2 * id);
-      if (lane == 0) { a.eboff[id] = Ge; a.elen[id] = Le; }
-    } else if (lane == 0) {
-      a.eboff[id] = Ge;
-      a.elen[id] = 0;  // overflowed: nothing written, fixup skips
-      atomicOr(&a.flags[0], 1u);
-    }
-    if (lane == 0 && row == g.rows - 1) a.bits_e[plane] = Ge_rel + Le;
-  }
-
-  STAMP(3);
-  // ---- Golomb codewords into the row image (rows longer than the LDS window: row_global_at below) ----
-  if constexpr (DO_G) {
-    constexpr uint32_t kCapBits = (kGImg - kPad) * 32;
-    const bool fits = L <= kCapBits;
-#ifdef BIC_STAMPS
-    uint32_t dbg_slow = 0;
-#endif
-    if (valid && fits) {
-      StepState st{(uint32_t)(O + row), -1};
-      const uint32_t arow = row * (g.cols + 1);
-      uint64_t loc = 0;
-      for (uint32_t w0 = 0; w0 < g.used; w0 += 64) {
-        const uint32_t w = w0 + lane;
-        const uint64_t x = img_resid(eimg, g, w);
-        uint32_t n;
-        int jp;
-        step_prefix(x, w, st, n, jp);
-        const bool eol = w == g.used - 1;
-        const LaneEnc e = encode_word(x, w, n, jp, arow, eol, g.cols, ByteTables{s_lut, a.lut});
-#ifdef BIC_STAMPS
-        dbg_slow += (e.path == 3 ? 1u : 0u) + (e.lng ? 1000u : 0u) + (e.path == 1 ? 1000000u : 0u);
-#endif
-        const uint32_t inc = wave_incl_sum_u32(e.len);
-        const uint64_t off = loc + inc - e.len;
-        loc += lane63_u32(inc);
-        if (!e.lng) {
-          place_small(gimg, (uint32_t)off, e.head, e.k0);
-          place128(gimg, (uint32_t)(off + e.k0 + e.z), e.t0, e.t1, e.tlen);
-        } else {
-          LdsSink ls{gimg, 0, 0};
-          emit_word(ls, (uint32_t)off, x, w, n, jp, arow, eol, g.cols);
-          ls.flush();
-        }
-      }
-      if (lane == 0 && loc != L) atomicOr(&a.flags[3], 1u);  // word_len disagrees with the emission
-    }
-    STAMP(4);
-#ifdef BIC_STAMPS
-    {
-      const uint32_t tot = wave_sum_u32(dbg_slow);
-      if (lane == 0 && (uint64_t)id * 8 + 7 < (1u << 21)) g_stamps[(uint64_t)id * 8 + 7] = tot;
-    }
-#endif
-    __syncthreads();
-    STAMP(5);
-    if (valid) {
-      uint64_t Grel = sh_pre[1];
-      for (int q = 0; q < wave; ++q) Grel += sh_len[q];
-      const uint64_t cap = a.slot_g * 64;
-      const uint64_t G = (uint64_t)plane * cap + Grel;
-      if (lane == 0 && row == g.rows - 1) a.bits_g[plane] = Grel + L;
-      if (Grel + L <= cap) {
-        if (fits) {
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          write_row(gimg, L, G, -1, a.out_g, a.gfrag + 2 * id);
-        }
-        if (lane == 0) {
-          a.gboff[id] = G;
-          a.glen[id] = L;
-          a.gslow[id] = 0;
-        }
-        // a row longer than the LDS window: written here, straight to global memory (no list, no
-        // k_rows_global launch)
-        if (!fits) row_global_at<PREDICT>(a, id, plane, row, G, L, O + row + 1, lane);
-      } else if (lane == 0) {
-        a.gboff[id] = G;
-        a.glen[id] = 0;
-        a.gslow[id] = 0;
-        atomicOr(&a.flags[0], 1u);
-      }
-    }
-    STAMP(6);
-  }
-}
-
-// ==========================================================================================
-// Two-pass encoder. Pass 1 (k_len_rows) runs the look-back chains with nothing but lengths:
-// per 8-row tile the ones count, the ones prefix, each row's Golomb length (byte tables, no
-// codeword strings) and the bits prefix; it stores, per row, the ones before it and both
-// streams' bit offsets. Pass 2 (k_emit_rows) then writes every row independently -- no
-// look-back, no workgroup barrier -- streaming each row's codewords through a small LDS window
-// whose complete words go straight to HBM. A row's first and last word (shared with the
-// neighbouring rows) go to the fragment table, as in the single-pass kernel.
-// ==========================================================================================
-constexpr int kWin = 1024;                      // u32 words of one wave's output window (also holds
-                                                // the EG image of a plane's first-1 row)
-constexpr uint32_t kIterCap = (kWin - 8) * 32 - 128;  // bits one 64-word step may emit
-
-template <int WPL, bool PREDICT, bool DO_G, bool DO_E>
-__global__ __launch_bounds__(64 * kTileRows, 8) void k_len_rows(FusedArgs a) {
-  // (sh_len apart from sh_cnt: a wave that finishes its length early must not overwrite the 1-counts
-  // a slower wave is still summing for its O -- one array for both raced: a wrong O, a wrong length,
-  // about 1 in 15 two-pass calls, tools/dbg_twopass.py)
-  __shared__ uint64_t sh_cnt[kTileRows], sh_len[kTileRows], sh_pre[2];
-  __shared__ uint32_t sh_tile;
-  __shared__ uint32_t s_lut[512];
-  const Geom& g = a.g;
-  const int lane = lane_id(), wave = (int)wave_id();
-  const uint32_t tpp = (g.rows + kTileRows - 1) / kTileRows;
-  if (threadIdx.x == 0) sh_tile = atomicAdd(a.counter, 1u);
-  if (DO_G && threadIdx.x < 512) s_lut[threadIdx.x] = reinterpret_cast<const uint32_t*>(a.lut + 256)[threadIdx.x];
-  __syncthreads();
-  const uint64_t tile = sh_tile;
-  if (tile >= (uint64_t)tpp * g.nplanes) return;  // uniform over the workgroup
-  const uint32_t plane = (uint32_t)(tile % g.nplanes), trow = (uint32_t)(tile / g.nplanes);
-  const uint64_t rbase = (uint64_t)plane * tpp, rid = rbase + trow;
-  const uint32_t row = trow * kTileRows + wave;
-  const bool valid = row < g.rows;
-  const uint64_t id = (uint64_t)plane * g.rows + row;
-
-  uint64_t rr[WPL];
-  uint32_t ones = 0;
-  if (valid) {
-    resid_row<WPL, PREDICT>(a.planes, g, plane, row, rr);
-#pragma unroll
-    for (int t = 0; t < WPL; ++t) ones += (uint32_t)__popcll(rr[t]);
-    ones = wave_sum_u32(ones);
-  }
-  if (lane == 0) sh_cnt[wave] = ones;
-  __syncthreads();
-  if (wave == 0) {
-    uint64_t tile_ones = 0;
-    for (int q = 0; q < kTileRows; ++q) tile_ones += sh_cnt[q];
-    uint64_t O = 0;
-    if (trow == 0) {
-      if (lane == 0) rec_store(&a.ones_rec[rid], kInc | tile_ones);
-    } else {
-      if (lane == 0) rec_store(&a.ones_rec[rid], kAgg | tile_ones);
-      O = lookback(a.ones_rec, rbase, rid, a.flags);
-      if (lane == 0) rec_store(&a.ones_rec[rid], kInc | (O + tile_ones));
-    }
-    if (lane == 0) sh_pre[0] = O;
-  }
-  __syncthreads();
-  uint64_t O = sh_pre[0];
-  for (int q = 0; q < wave; ++q) O += sh_cnt[q];
-
-  if (DO_E && valid && lane == 0) {  // EG as written: ~R then '1' per row; a '0' after the plane's first 1
-    const uint64_t Le = (uint64_t)g.cols + 1 + ((O == 0 && ones > 0) ? 1 : 0);
-    const uint64_t Ge_rel = (uint64_t)row * (g.cols + 1) + (O > 0 ? 1 : 0);
-    const uint64_t cap = a.slot_e * 64;
-    a.eboff[id] = (uint64_t)plane * cap + Ge_rel;
-    if (Ge_rel + Le <= cap) {
-      a.elen[id] = Le;
-    } else {
-      a.elen[id] = 0;
-      atomicOr(&a.flags[0], 1u);
-    }
-    if (row == g.rows - 1) a.bits_e[plane] = Ge_rel + Le;
-  }
-  if (valid && lane == 0) a.row_o[id] = (uint32_t)O;
-
-  if constexpr (DO_G) {
-    uint64_t L = 0;
-    uint32_t step_max = 0;
-    if (valid) {
-      StepState st{(uint32_t)(O + row), -1};
-      const uint32_t arow = row * (g.cols + 1);
-#pragma unroll
-      for (int t = 0; t < WPL; ++t) {
-        const uint32_t w = t * 64 + lane;
-        if (t * 64 >= (int)g.used) break;
-        uint32_t n;
-        int jp;
-        step_prefix(rr[t], w, st, n, jp);
-        uint32_t kor = 0;
-        const uint32_t tot = wave_sum_u32(word_len(rr[t], w, n, jp, arow, w == g.used - 1, g.cols, kor));
-        L += tot;
-        step_max = max(step_max, tot);
-      }
-    }
-    if (lane == 0) sh_len[wave] = L;
-    __syncthreads();
-    if (wave == 0) {
-      uint64_t tile_bits = 0;
-      for (int q = 0; q < kTileRows; ++q) tile_bits += sh_len[q];
-      uint64_t Gt = 0;
-      if (trow == 0) {
-        if (lane == 0) rec_store(&a.bits_rec[rid], kInc | tile_bits);
-      } else {
-        if (lane == 0) rec_store(&a.bits_rec[rid], kAgg | tile_bits);
-        Gt = lookback(a.bits_rec, rbase, rid, a.flags);
-        if (lane == 0) rec_store(&a.bits_rec[rid], kInc | (Gt + tile_bits));
-      }
-      if (lane == 0) sh_pre[1] = Gt;
-    }
-    __syncthreads();
-    if (valid && lane == 0) {
-      uint64_t Grel = sh_pre[1];
-      for (int q = 0; q < wave; ++q) Grel += sh_len[q];
-      const uint64_t cap = a.slot_g * 64;
-      a.gboff[id] = (uint64_t)plane * cap + Grel;
-      if (row == g.rows - 1) a.bits_g[plane] = Grel + L;
-      if (Grel + L <= cap) {
-        a.glen[id] = L;
-        a.gslow[id] = step_max > kIterCap ? O + row + 1 : 0;  // k_rows_global writes such rows
-        if (step_max > kIterCap) a.slow_ids[atomicAdd(a.slow_n, 1u)] = id;
-      } else {
-        a.glen[id] = 0;
-        a.gslow[id] = 0;
-        atomicOr(&a.flags[0], 1u);
-      }
-    }
-  }
-}
-
-// EG row from registers: row bit b (b < cols) is ~R, bit cols is the end-of-row '1'; output word
-// j of the row holds row bits [64j - g, 64j - g + 64) with g = Ge % 64. Lane l forms words
-// j = 64t + l from its own row word and its left neighbour's (one shuffle per step).
-// INV = false: the row bits are R itself (a Golomb row whose codewords all have k = 0).
-template <int WPL, bool INV = true>
-__device__ __forceinline__ void eg_row_regs(const uint64_t (&rr)[WPL], const Geom& g, uint64_t Ge, uint64_t Le,
-                                            uint64_t* out, uint64_t* frag) {
-  const int lane = lane_id();
-  const uint32_t sh = (uint32_t)(Ge & 63);
-  const uint64_t w0 = Ge >> 6, nw = ((Ge + Le - 1) >> 6) - w0 + 1;
-  const uint32_t eolw = g.cols >> 6;
-  const uint64_t eolbit = BIC_MSB >> (g.cols & 63);
-  const bool head_whole = sh == 0, tail_whole = ((Ge + Le) & 63) == 0;  // (only the first / last word can be shared)
-  uint64_t carry = 0;
-#pragma unroll
-  for (int t = 0; t <= WPL; ++t) {
-    const uint32_t j = t * 64 + lane;
-    if (t * 64 >= (int)nw) break;
-    uint64_t X = 0;
-    if (t < WPL && j < g.used) X = INV ? ~rr[t] & (j == g.used - 1 ? g.trail : ~0ull) : rr[t];
-    if (j == eolw) X |= eolbit;
-    uint64_t Xl = shfl_up_u64(X, 1);
-    if (lane == 0) Xl = carry;
-    carry = lane63_u64(X);
-    const uint64_t v = funnel64(Xl, X, sh);
-    if (j < nw) {
-      const uint64_t wi = w0 + j;
-      if ((j != 0 || head_whole) && (j != nw - 1 || tail_whole)) out[wi] = bswap64(v);
-      else put_shared(out, wi, frag, j == 0 ? 0 : 1, v);
-    }
-  }
-}
-
-template <int WPL, bool PREDICT, bool DO_G, bool DO_E>
-__global__ __launch_bounds__(64 * kTileRows, 8) void k_emit_rows(FusedArgs a) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[kTileRows * kWin];
-  __shared__ uint32_t s_lut[512];
-  const Geom& g = a.g;
-  const int lane = lane_id(), wave = (int)wave_id();
-  uint32_t* win = lds + wave * kWin;
-  if (DO_G && threadIdx.x < 512) s_lut[threadIdx.x] = reinterpret_cast<const uint32_t*>(a.lut + 256)[threadIdx.x];
-  __syncthreads();  // the only workgroup barrier
-  const uint64_t id = (uint64_t)blockIdx.x * kTileRows + wave;
-  if (id >= (uint64_t)g.rows * g.nplanes) return;
-  const uint32_t plane = (uint32_t)(id / g.rows), row = (uint32_t)(id % g.rows);
-  const bool do_g = DO_G && a.glen[id] != 0 && a.gslow[id] == 0;
-  const bool do_e = DO_E && a.elen[id] != 0;
-  if (!do_g && !do_e) return;
-  if (do_g) lds_image_zero32(win, kWin / 4);
-  uint64_t rr[WPL];
-  resid_row<WPL, PREDICT>(a.planes, g, plane, row, rr);
-  const uint32_t O = a.row_o[id];
-
-  if (do_e) {
-    const uint64_t Ge = a.eboff[id], Le = a.elen[id];
-    if (Le == (uint64_t)g.cols + 1) {
-      eg_row_regs<WPL>(rr, g, Ge, Le, a.out_e, a.efrag + 2 * id);
-    } else {
-      // the plane's first 1 is in this row: EG image with the inserted '0' (once per plane)
-      uint32_t* eimg = win;  // reused before the Golomb window is live
-      int fcol = INT_MAX;
-#pragma unroll
-      for (int t = 0; t < WPL; ++t) {
-        const uint32_t w = t * 64 + lane;
-        if (rr[t] && fcol == INT_MAX) fcol = (int)(w * 64 + __builtin_clzll(rr[t]));
-        if (w < g.used) {
-          const uint64_t v = ~rr[t] & (w == g.used - 1 ? g.trail : ~0ull);
-          eimg[2 * w] = (uint32_t)(v >> 32);
-          eimg[2 * w + 1] = (uint32_t)v;
-        }
-      }
-      if (lane < kPad + 1) eimg[2 * g.used + lane] = 0;
-      fcol = wave_min(fcol);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      if (lane == 0) eimg[g.cols >> 5] |= 0x80000000u >> (g.cols & 31);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      write_row(eimg, Le, Ge, (int64_t)fcol + 1, a.out_e, a.efrag + 2 * id);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      if (do_g) {
-        lds_image_zero32(win, kWin / 4);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
-    }
-  }
-
-  if constexpr (DO_G) {
-    if (!do_g) return;
-    const uint64_t G = a.gboff[id], L = a.glen[id];
-    uint64_t* out = a.out_g;
-    uint64_t* frag = a.gfrag + 2 * id;
-    uint64_t wbase = G & ~63ull;  // absolute bit of win[0]
-    const uint64_t first_word = G >> 6;
-    StepState st{O + row, -1};
-    const uint32_t arow = row * (g.cols + 1);
-    uint64_t loc = 0;  // row bits placed so far
-#pragma unroll
-    for (int t = 0; t < WPL; ++t) {
-      const uint32_t w = t * 64 + lane;
-      if (t * 64 >= (int)g.used) break;
-      const uint64_t x = rr[t];
-      uint32_t n;
-      int jp;
-      step_prefix(x, w, st, n, jp);
-      const bool eol = w == g.used - 1;
-      const LaneEnc e = encode_word<true>(x, w, n, jp, arow, eol, g.cols, ByteTables{s_lut, a.lut});
-      const uint32_t inc = wave_incl_sum_u32(e.len);
-      const uint32_t p = (uint32_t)(G + loc - wbase) + inc - e.len;  // window bit of this lane's string
-      if (!e.lng) {
-        place_small(win, p, e.head, e.k0);
-        place128(win, p + e.k0 + e.z, e.t0, e.t1, e.tlen);
-      } else {
-        LdsSink ls{win, 0, 0};
-        emit_word(ls, p, x, w, n, jp, arow, eol, g.cols);
-        ls.flush();
-      }
-      loc += lane63_u32(inc);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      // flush the complete 64-bit words; the row's first word, if shared, is a fragment
-      const uint32_t nfull = (uint32_t)((G + loc - wbase) >> 6);
-      for (uint32_t q = lane; q < nfull; q += 64) {
-        const uint64_t v = ((uint64_t)win[2 * q] << 32) | win[2 * q + 1];
-        const uint64_t wi = (wbase >> 6) + q;
-        if (wi == first_word && (G & 63)) frag[0] = v;
-        else out[wi] = bswap64(v);
-      }
-      if (nfull) {  // carry the partial word to the front, clear the rest
-        const uint32_t c0 = win[2 * nfull], c1 = win[2 * nfull + 1];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t q = 2 + lane; q < 2 * nfull + 2; q += 64) win[q] = 0;
-        if (lane == 0) { win[0] = c0; win[1] = c1; }
-        wbase += 64ull * nfull;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
-    }
-    // the row's last word, if it ends inside one
-    if ((G + L) & 63) {
-      if (lane == 0) {
-        const uint64_t v = ((uint64_t)win[0] << 32) | win[1];
-        if ((wbase >> 6) == first_word) frag[0] = v;
-        else frag[1] = v;
-      }
-    }
-  }
 }
 
 // ==========================================================================================
@@ -2429,7 +1000,7 @@ __global__ __launch_bounds__(256) void k_emit_rest(FusedArgs a) {
 // At most 112 registers, one fewer than the compiler takes by itself: four workgroups then leave 64 of a
 // SIMD's 512 for one wave of k_emit_rest (59 registers, allocated as 64), whose rows otherwise wait for
 // these persistent waves to end (k_emit_rest ended 3-9 us after this kernel). The attribute counts
-// architectural registers, half of this target's unified file, hence 56; launch_fused checks what the
+// architectural registers, half of this target's unified file, hence 56; launch_staged_emit checks what the
 // build gave (k01_regs_checked).
 constexpr int kK01Regs = 112;
 template <int WPL>
@@ -2523,66 +1094,40 @@ void launch_fixup_rows(hipStream_t s, const uint64_t* boff, const uint64_t* len,
 }
 
 // ------------------------------------------------------------------------------------
-// The scratch block. fused_scratch_bytes and carve_fused_scratch list the same terms in the same order
-// (n = rows * planes); a term added to one goes into the other at the same place.
-size_t fused_scratch_bytes(const Geom& g) {
-  const size_t n = (size_t)g.rows * g.nplanes;
-  return 256 +                            // counter
-         n * 8 * 2 +                      // ones_rec, bits_rec
-         n * 8 * 10 +                     // gboff, glen, gfrag (2 n), gslow, eboff, elen, efrag (2 n), slow_ids
-         n * kMaxStrips * (16 + 4 + 4) +  // krec, kpos, sones
-         n * 4 * 4 +                      // row_o, walk_ids, rest_ids, walk_o
-         (size_t)g.nplanes * 8 * 4 +      // pones, gbase, ebase, efix
-         n * 16 * 2 +                     // cls: the k = 0 list and the k = 1 list, two u64 words per entry
-         512 +                            // sink
-         1024 + 64 + 64;                  // unassigned tail (covers rounding pones up to 8 bytes)
+// The scratch arena's layout, stated once: every block in order with its size in bytes (n = rows *
+// planes; every size a multiple of 8). Points a's fields into the arena at base and returns its size.
+static size_t fused_layout(const Geom& g, FusedArena& a, void* base) {
+  const size_t n = (size_t)g.rows * g.nplanes, np = g.nplanes;
+  uintptr_t p = reinterpret_cast<uintptr_t>(base);
+  auto take = [&](auto*& field, size_t bytes) {
+    field = reinterpret_cast<std::remove_reference_t<decltype(field)>>(p);
+    p += bytes;
+  };
+  take(a.counter, 256);
+  take(a.ones_rec, n * 8), take(a.bits_rec, n * 8);
+  take(a.gboff, n * 8), take(a.glen, n * 8), take(a.gfrag, 2 * n * 8), take(a.gslow, n * 8);
+  take(a.eboff, n * 8), take(a.elen, n * 8), take(a.efrag, 2 * n * 8), take(a.slow_ids, n * 8);
+  take(a.krec, n * kMaxStrips * 16), take(a.kpos, n * kMaxStrips * 4), take(a.sones, n * kMaxStrips * 4);
+  take(a.row_o, n * 4), take(a.walk_ids, n * 4), take(a.rest_ids, n * 4), take(a.walk_o, n * 4);
+  take(a.pones, np * 8), take(a.gbase, np * 8), take(a.ebase, np * 8), take(a.efix, np * 8);
+  take(a.cls, 2 * n * 16);  // the k = 0 list and the k = 1 list, two u64 words per entry
+  take(a.sink, 512);
+  char* unassigned;  // (kept: the arena's size stays what it was)
+  take(unassigned, 1024 + 64 + 64);
+  a.slow_n = a.counter + 1;
+  a.zero_bytes = 256 + n * 16;  // counter, ones_rec, bits_rec
+  return p - reinterpret_cast<uintptr_t>(base);
 }
 
-FusedScratch carve_fused_scratch(void* base, const Geom& g) {
-  const size_t n = (size_t)g.rows * g.nplanes;
-  char* p = reinterpret_cast<char*>(base);
-  FusedScratch fs;
-  // counter: kZeroWords u32 words in 256 bytes. [0] the single / two-pass encoders' tile ticket, [1] slow_n,
-  // [2] the walk list's length, [3] rest_ids', [4] and [5] the k = 0 and k = 1 class lists'; the words from
-  // [6] on are unused ([6..10] served experiments whose code was removed)
-  fs.counter = reinterpret_cast<uint32_t*>(p);
-  // ones_rec, bits_rec
-  fs.ones_rec = reinterpret_cast<uint64_t*>(p + 256);
-  fs.bits_rec = fs.ones_rec + n;
-  fs.zero_bytes = 256 + n * 16;
-  // gboff, glen, gfrag, gslow, eboff, elen, efrag, slow_ids
-  uint64_t* q = fs.bits_rec + n;
-  fs.gboff = q; q += n;
-  fs.glen = q; q += n;
-  fs.gfrag = q; q += 2 * n;
-  fs.gslow = q; q += n;
-  fs.eboff = q; q += n;
-  fs.elen = q; q += n;
-  fs.efrag = q; q += 2 * n;
-  fs.slow_ids = q; q += n;
-  // krec, kpos, sones
-  fs.krec = reinterpret_cast<int4*>(q);
-  fs.kpos = reinterpret_cast<uint32_t*>(fs.krec + n * kMaxStrips);
-  fs.sones = fs.kpos + n * kMaxStrips;
-  // row_o, walk_ids, rest_ids, walk_o
-  fs.row_o = fs.sones + n * kMaxStrips;
-  fs.walk_ids = fs.row_o + n;
-  fs.rest_ids = fs.walk_ids + n;
-  fs.walk_o = fs.rest_ids + n;
-  // pones, gbase, ebase, efix (rounded up to 8 bytes: the tail pays for it)
-  const uintptr_t e = (reinterpret_cast<uintptr_t>(fs.walk_o + n) + 7) & ~(uintptr_t)7;
-  fs.pones = reinterpret_cast<uint64_t*>(e);
-  fs.gbase = fs.pones + g.nplanes;
-  fs.ebase = fs.gbase + g.nplanes;
-  fs.efix = fs.ebase + g.nplanes;
-  // cls
-  fs.cls = fs.efix + g.nplanes;
-  // sink
-  fs.sink = fs.cls + 4 * n;
-  fs.ns = 1;
-  fs.counted = false;
-  fs.slow_n = fs.counter + 1;  // zeroed with the counter
-  return fs;
+size_t fused_scratch_bytes(const Geom& g) {
+  FusedArena a;
+  return fused_layout(g, a, nullptr);
+}
+
+FusedArena carve_fused_arena(void* base, const Geom& g) {
+  FusedArena a;
+  fused_layout(g, a, base);
+  return a;
 }
 
 // (a plane's pixels fit 32 bits: row_o, and the ONES scan's packed pair, hold a plane's 1-count in 32)
@@ -2594,180 +1139,130 @@ int read_stamps(uint64_t* host, size_t n) {
 }
 #endif
 
-void launch_fused(hipStream_t s, const Geom& g, const uint64_t* planes, const uint64_t* lut, int predict,
-                  const FusedScratch& fs,
-                  uint64_t* out_g, uint64_t slot_g, uint64_t* bits_g, uint64_t* out_e, uint64_t slot_e,
-                  uint64_t* bits_e, uint32_t* flags, int mode, int stage) {
-  if (stage == kFusedPrep) {
-    // the staged encoder's count pass zeroes its counters itself (kZeroWords, launch_row_ones /
-    // launch_gray_rows)
-    // (single / two-pass: not when the previous call's k_fixup left them zero)
-    if (mode != kEncStaged && !fs.zero_ready) (void)launch_fill(s, fs.counter, 0, fs.zero_bytes);
-    return;
+// Staged encoder: per-row counts, scans and Golomb lengths -- every row's offsets known up front.
+void launch_staged_prefix(hipStream_t s, const FusedCall& c, bool golomb_lengths) {
+  const FusedArgs a = make_fused_args(c);
+  const Geom& g = c.g;
+  if (!c.rq.counted) launch_row_ones(s, g, c.planes, c.predict, c.ar.sones, c.ar.krec, c.ar.kpos, c.ar.counter);
+  const uint32_t sgrid = (g.rows + kScanChunk - 1) / kScanChunk * g.nplanes;
+  if (golomb_lengths) k_scan_rows<true, true><<<sgrid, kScanThreads, 0, s>>>(a);
+  else k_scan_rows<true, false><<<sgrid, kScanThreads, 0, s>>>(a);
+  if (golomb_lengths) {
+    const uint32_t wwv = (kWalkSplit * g.used + 63) / 64;  // k_row_walk: waves per row (<= 8)
+    if (c.predict) k_row_walk<true><<<kWalkWaves / wwv, 64 * wwv, 0, s>>>(a);
+    else k_row_walk<false><<<kWalkWaves / wwv, 64 * wwv, 0, s>>>(a);
+    k_scan_rows<false, false><<<sgrid, kScanThreads, 0, s>>>(a);  // (+ the row index)
   }
-  const bool single_pass = mode == kEncSingle;
-  FusedArgs a{g, planes, lut, fs.counter, fs.ones_rec, fs.bits_rec, fs.gboff, fs.glen, fs.gfrag, fs.gslow,
-              fs.eboff, fs.elen, fs.efrag, fs.row_o, fs.sones, fs.krec, fs.kpos, fs.counted ? fs.ns : 1u, fs.walk_ids, fs.rest_ids, fs.slow_n, fs.slow_ids, out_g, slot_g, bits_g, out_e, slot_e,
-              bits_e, flags};
-  a.pones = fs.pones;
-  a.walk_o = fs.walk_o;
-  a.gbase = fs.gbase;
-  a.off_g = out_g ? fs.off_g : nullptr;
-  a.off_e = out_e ? fs.off_e : nullptr;
-  a.ebase = a.off_e ? fs.ebase : nullptr;
-  a.index = out_g ? fs.index : nullptr;
-  // EG source (bic_encode_gray without planes): the count pass wrote the EG stream, the emission is
-  // Golomb's alone and reads the residual rows from it
-  const bool es = mode == kEncStaged && fs.eg_src && out_e && !a.off_e && !predict;
-  a.esrc = es ? out_e : nullptr;
-  a.efix = es ? fs.efix : nullptr;
-  a.cls = es && out_g && !fs.eg_src_one ? fs.cls : nullptr;
-  a.sink = fs.sink;
-#ifdef BIC_STAMPS
-  a.known = getenv("BIC_KNOWN") && getenv("BIC_KNOWN")[0] == '1';
-#endif
+  // packed output: the planes' start words (the rows' Golomb offsets stay slot-relative: gb_abs)
+  // -- as the LEN scan's last workgroup instead, its device-scope release fences (an L2 write-back
+  // per workgroup) made C4's prefix 99 -> 153 us
+  if (a.off_g || a.off_e) k_plane_bases<<<1, 1024, 0, s>>>(a);
+}
+
+// one resident wave set: as many workgroups per CU as the instance's registers and LDS allow
+// (WPL = 4: <= 128 VGPRs, 4; WPL = 1: 7), queried once per instance
+static int emit_occupancy(const void* fn) {
+  int occ = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64 * kEmitWaves, 0) != hipSuccess || occ < 1) occ = 4;
+  return std::min(occ, 8);
+}
+// k_emit_k01's register bound (kK01Regs) as built: more registers, or any scratch, and k_emit_rest no
+// longer fits beside it or its rows spill -- said once, since the streams stay right and only time is lost
+static bool k01_regs_checked(const void* fn) {
+  hipFuncAttributes fa{};
+  if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return false;
+  const bool ok = fa.numRegs <= kK01Regs && fa.localSizeBytes == 0;
+  if (!ok)
+    std::fprintf(stderr, "bic_fused.hip: k_emit_k01 was built with %d registers and %zu bytes of scratch (expected <= %d, 0)\n",
+                 fa.numRegs, (size_t)fa.localSizeBytes, kK01Regs);
+  return ok;
+}
+
+// Staged encoder: every row written independently, persistent grids (more rows per wave when the
+// image is larger).
+void launch_staged_emit(hipStream_t s, const FusedCall& c, const EmitStreams& es) {
+  const FusedArgs a = make_fused_args(c);
+  const Geom& g = c.g;
+  const bool dg = a.out_g != nullptr, de = a.out_e != nullptr && !a.esrc;  // de: the emission writes EG
+  if (!dg && !de) return;  // EG source without Golomb: the count pass and the ONES scan wrote it all
   const uint64_t nrows = (uint64_t)g.rows * g.nplanes;
-  const uint32_t grid = (uint32_t)((g.rows + kTileRows - 1) / kTileRows * (uint64_t)g.nplanes);  // one per tile
-  const uint32_t egrid = (uint32_t)((nrows + kTileRows - 1) / kTileRows);                       // one per 8 rows
-  const bool dg = out_g != nullptr, de = out_e != nullptr && !es;  // de: the emission writes EG
-  const uint32_t fgrid = (uint32_t)((nrows + 255) / 256);
-  if (stage == kFusedFinish) {
-    // a fixed small grid walks the list of LDS-overflow rows (usually empty); block 0 also clears
-    // the EG source's one bit per plane (eg_fix_bit)
-    // (a.cls: k_emit_rest wrote the slow rows; single pass: k_encode_rows did)
-    if ((dg && !single_pass && !a.cls) || (!dg && es)) {
-      if (predict) k_rows_global<true><<<dg ? 256 : 1, 256, 0, s>>>(a);
-      else k_rows_global<false><<<dg ? 256 : 1, 256, 0, s>>>(a);
-    }
-    if (!dg && !de) return;
-    k_fixup<<<dg && de ? 2 * fgrid : fgrid, 256, 0, s>>>(dg ? fs.gboff : fs.eboff, dg ? fs.glen : fs.elen,
-                                                        dg ? fs.gfrag : fs.efrag, dg ? out_g : out_e,
-                                                        fs.eboff, fs.elen, fs.efrag, out_e, g.rows, nrows,
-                                                        dg && de ? fgrid : 0xffffffffu,
-                                                        dg && mode == kEncStaged ? a.off_g ? fs.gbase : nullptr : nullptr,
-                                                        slot_g * 64, dg ? a.efix : nullptr, out_e, slot_e, g.nplanes,
-                                                        fs.counter, mode != kEncStaged ? fs.ones_rec : nullptr, nrows);
-    return;
+  static thread_local int cus = 0;  // the device's CU count, asked once
+  if (!cus) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (cus <= 0) cus = 256;
   }
-  const int wpl = g.used <= 64 ? 1 : (g.used <= 128 ? 2 : 4);
-  if (mode == kEncStaged) {
-    if (stage == kFusedPrefix) {
-      if (!fs.counted) launch_row_ones(s, g, planes, predict, fs.sones, fs.krec, fs.kpos, fs.counter);
-      const uint32_t sgrid = (g.rows + kScanChunk - 1) / kScanChunk * g.nplanes;
-      if (dg) k_scan_rows<true, true><<<sgrid, kScanThreads, 0, s>>>(a);
-      else k_scan_rows<true, false><<<sgrid, kScanThreads, 0, s>>>(a);
-      if (dg) {
-        const uint32_t wwv = (kWalkSplit * g.used + 63) / 64;  // k_row_walk: waves per row (<= 8)
-        if (predict) k_row_walk<true><<<kWalkWaves / wwv, 64 * wwv, 0, s>>>(a);
-        else k_row_walk<false><<<kWalkWaves / wwv, 64 * wwv, 0, s>>>(a);
-        k_scan_rows<false, false><<<sgrid, kScanThreads, 0, s>>>(a);  // (+ the row index)
+  // k_emit_rest (listed rows, latency bound: few workgroups) first, on the aux stream when there
+  // is one, so that it can overlap the main launch, which skips the listed rows' parts
+  const uint32_t nwv = (g.used + 63) / 64;  // waves per row in k_emit_rest
+  const uint32_t rgrid = (uint32_t)std::min<uint64_t>(nrows, (uint64_t)cus * 32 / nwv);  // 32 waves per CU (16: C4 +6 us; 4: C3 +30 us -- the listed rows are latency-bound)
+  hipStream_t rs = s;
+  if (es.aux && es.fork && es.join && hipEventRecord(es.fork, s) == hipSuccess &&
+      hipStreamWaitEvent(es.aux, es.fork, 0) == hipSuccess)
+    rs = es.aux;
+  // (bic_prof_*: events around the main emission kernel alone, on its stream s -- the roofline kernel's
+  // launch, without the fork / join of the second stream; null: not timed)
+  auto main_ev = [&](hipEvent_t e) {
+    if (e && hipEventRecord(e, s) == hipSuccess && e == es.main1 && es.main_rec) *es.main_rec = true;
+  };
+  using Kernel = void (*)(FusedArgs);
+  auto emit = [&](Kernel rest, Kernel main, int occ) {  // (main: workgroups of kEmitWaves waves)
+    rest<<<rgrid, 64 * nwv, 0, rs>>>(a);
+    main_ev(es.main0);
+    const uint64_t egrid = std::min<uint64_t>((nrows + kEmitWaves - 1) / kEmitWaves, (uint64_t)cus * (uint32_t)occ);
+    main<<<(uint32_t)egrid, 64 * kEmitWaves, 0, s>>>(a);
+    main_ev(es.main1);
+  };
+  if (a.esrc) {  // Golomb alone, the residual rows from the EG stream
+    with_wpl(g, [&](auto w) {
+      if (a.cls) {  // one kernel for the two row classes
+        static const int occ = emit_occupancy(reinterpret_cast<const void*>(&k_emit_k01<w()>));
+        [[maybe_unused]] static const bool regs = k01_regs_checked(reinterpret_cast<const void*>(&k_emit_k01<w()>));
+        emit(k_emit_rest<false, true, false>, k_emit_k01<w()>, occ);
+      } else {
+        static const int occ = emit_occupancy(reinterpret_cast<const void*>(&k_emit_known<w(), false, true, false, true>));
+        emit(k_emit_rest<false, true, false>, k_emit_known<w(), false, true, false, true>, occ);
       }
-      // packed output: the planes' start words (the rows' Golomb offsets stay slot-relative: gb_abs)
-      // -- as the LEN scan's last workgroup instead, its device-scope release fences (an L2 write-back
-      // per workgroup) made C4's prefix 99 -> 153 us
-      if (a.off_g || a.off_e) k_plane_bases<<<1, 1024, 0, s>>>(a);
-      return;
-    }
-    if (!dg && !de) return;  // EG source without Golomb: the count pass and the ONES scan wrote it all
-    // persistent grids (more rows per wave when the image is larger)
-    static thread_local int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      if (cus <= 0) cus = 256;
-    }
-    // one resident wave set: as many workgroups per CU as the instance's registers and LDS allow
-    // (WPL = 4: <= 128 VGPRs, 4; WPL = 1: 7), queried once per instance
-    auto occ_of = [](const void* fn) {
-      int occ = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64 * kEmitWaves, 0) != hipSuccess || occ < 1) occ = 4;
-      return std::min(occ, 8);
-    };
-    // k_emit_k01's register bound (kK01Regs) as built: more registers, or any scratch, and k_emit_rest no
-    // longer fits beside it or its rows spill -- said once, since the streams stay right and only time is lost
-    auto k01_regs_checked = [](const void* fn) {
-      hipFuncAttributes fa{};
-      if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return false;
-      const bool ok = fa.numRegs <= kK01Regs && fa.localSizeBytes == 0;
-      if (!ok)
-        std::fprintf(stderr, "bic_fused.hip: k_emit_k01 was built with %d registers and %zu bytes of scratch (expected <= %d, 0)\n",
-                     fa.numRegs, (size_t)fa.localSizeBytes, kK01Regs);
-      return ok;
-    };
-    auto egrid_of = [&](int occ) {
-      return (uint32_t)std::min<uint64_t>((nrows + kEmitWaves - 1) / kEmitWaves, (uint64_t)cus * (uint32_t)occ);
-    };
-    // k_emit_rest (listed rows, latency bound: few workgroups) first, on the aux stream when there
-    // is one, so that it can overlap the main launch, which skips the listed rows' parts
-    const uint32_t nwv = (g.used + 63) / 64;  // waves per row in k_emit_rest
-    const uint32_t rgrid = (uint32_t)std::min<uint64_t>(nrows, (uint64_t)cus * 32 / nwv);  // 32 waves per CU (16: C4 +6 us; 4: C3 +30 us -- the listed rows are latency-bound)
-    // (bic_prof_*: events around the main emission kernel alone, on its stream s -- the roofline kernel's
-    // launch, without the fork / join of the second stream; null: not timed)
-    auto main_ev = [&](hipEvent_t e) {
-      if (e && hipEventRecord(e, s) == hipSuccess && e == fs.ev_main1 && fs.ev_main_rec) *fs.ev_main_rec = true;
-    };
-    hipStream_t rs = s;
-    if (fs.aux && fs.ev_fork && fs.ev_join && hipEventRecord(fs.ev_fork, s) == hipSuccess &&
-        hipStreamWaitEvent(fs.aux, fs.ev_fork, 0) == hipSuccess)
-      rs = fs.aux;
-#define BIC_EMIT1(W, P, DG, DE, ES)                                                                    \
-  {                                                                                                  \
-    k_emit_rest<P, DG, DE><<<rgrid, 64 * nwv, 0, rs>>>(a);                                           \
-    static const int occ_ = occ_of(reinterpret_cast<const void*>(&k_emit_known<W, P, DG, DE, ES>));  \
-    main_ev(fs.ev_main0);                                                                            \
-    k_emit_known<W, P, DG, DE, ES><<<egrid_of(occ_), 64 * kEmitWaves, 0, s>>>(a);                    \
-    main_ev(fs.ev_main1);                                                                            \
-  }
-#define BIC_EMIT(W, P)                                                                                \
-  if (dg && de) BIC_EMIT1(W, P, true, true, false) else if (dg) BIC_EMIT1(W, P, true, false, false) else BIC_EMIT1(W, P, false, true, false)
-    if (predict) {
-      if (wpl == 1) { BIC_EMIT(1, true); } else if (wpl == 2) { BIC_EMIT(2, true); } else { BIC_EMIT(4, true); }
-    } else if (es && !a.cls) {  // Golomb alone, the residual rows from the EG stream, one kernel
-      if (wpl == 1) { BIC_EMIT1(1, false, true, false, true); } else if (wpl == 2) { BIC_EMIT1(2, false, true, false, true); }
-      else { BIC_EMIT1(4, false, true, false, true); }
-    } else if (es) {  // Golomb alone, the residual rows from the EG stream: one kernel per row class
-#define BIC_EMITC(W)                                                                                      \
-  {                                                                                                    \
-    static const int o_ = occ_of(reinterpret_cast<const void*>(&k_emit_k01<W>));                      \
-    static const bool r_ = k01_regs_checked(reinterpret_cast<const void*>(&k_emit_k01<W>));           \
-    (void)r_;                                                                                          \
-    k_emit_rest<false, true, false><<<rgrid, 64 * nwv, 0, rs>>>(a);                                    \
-    main_ev(fs.ev_main0);                                                                              \
-    k_emit_k01<W><<<egrid_of(o_), 256, 0, s>>>(a);                                                     \
-    main_ev(fs.ev_main1);                                                                              \
-  }
-      if (wpl == 1) { BIC_EMITC(1); } else if (wpl == 2) { BIC_EMITC(2); } else { BIC_EMITC(4); }
-#undef BIC_EMITC
-    } else {
-      if (wpl == 1) { BIC_EMIT(1, false); } else if (wpl == 2) { BIC_EMIT(2, false); } else { BIC_EMIT(4, false); }
-    }
-#undef BIC_EMIT
-#undef BIC_EMIT1
-    if (rs != s && (hipEventRecord(fs.ev_join, rs) != hipSuccess || hipStreamWaitEvent(s, fs.ev_join, 0) != hipSuccess))
-      (void)hipStreamSynchronize(rs);  // no join event: wait on the host rather than race
-    return;
-  }
-  if (stage == kFusedPrefix) return;
-  const dim3 blk(64 * kTileRows);
-#define BIC_PASSES(W, P, DG, DE)                                                        \
-  if (single_pass) {                                                                    \
-    k_encode_rows<W, P, DG, DE><<<grid, blk, 0, s>>>(a);                                \
-  } else {                                                                              \
-    k_len_rows<W, P, DG, DE><<<grid, blk, 0, s>>>(a);                                   \
-    k_emit_rows<W, P, DG, DE><<<egrid, blk, 0, s>>>(a);                                 \
-  }
-#define BIC_CODERS(W, P)                                                                \
-  if (dg && de) { BIC_PASSES(W, P, true, true) }                                        \
-  else if (dg) { BIC_PASSES(W, P, true, false) }                                        \
-  else { BIC_PASSES(W, P, false, true) }
-  if (predict) {
-    if (wpl == 1) { BIC_CODERS(1, true) } else if (wpl == 2) { BIC_CODERS(2, true) } else { BIC_CODERS(4, true) }
+    });
   } else {
-    if (wpl == 1) { BIC_CODERS(1, false) } else if (wpl == 2) { BIC_CODERS(2, false) } else { BIC_CODERS(4, false) }
+    with_row_kernel(g, c.predict != 0, dg, de, [&](auto w, auto p, auto cg, auto ce) {
+      static const int occ = emit_occupancy(reinterpret_cast<const void*>(&k_emit_known<w(), p(), cg(), ce()>));
+      emit(k_emit_rest<p(), cg(), ce()>, k_emit_known<w(), p(), cg(), ce()>, occ);
+    });
   }
-#undef BIC_CODERS
-#undef BIC_PASSES
+  if (rs != s && (hipEventRecord(es.join, rs) != hipSuccess || hipStreamWaitEvent(s, es.join, 0) != hipSuccess))
+    (void)hipStreamSynchronize(rs);  // no join event: wait on the host rather than race
+}
+
+// The LDS-overflow rows and the words adjacent rows share.
+void launch_fused_finish(hipStream_t s, const FusedCall& c) {
+  const FusedArgs a = make_fused_args(c);
+  const Geom& g = c.g;
+  const FusedArena& ar = c.ar;
+  const bool staged = c.mode == kEncStaged;
+  const bool dg = a.out_g != nullptr, de = a.out_e != nullptr && !a.esrc;
+  const uint64_t nrows = (uint64_t)g.rows * g.nplanes;
+  const uint32_t fgrid = (uint32_t)((nrows + 255) / 256);
+  // a fixed small grid walks the list of LDS-overflow rows (usually empty); block 0 also clears
+  // the EG source's one bit per plane (eg_fix_bit)
+  // (a.cls: k_emit_rest wrote the slow rows; single kernel: k_encode_rows did)
+  if ((dg && c.mode != kEncSingle && !a.cls) || (!dg && a.esrc)) {
+    if (c.predict) k_rows_global<true><<<dg ? 256 : 1, 256, 0, s>>>(a);
+    else k_rows_global<false><<<dg ? 256 : 1, 256, 0, s>>>(a);
+  }
+  if (!dg && !de) return;
+  k_fixup<<<dg && de ? 2 * fgrid : fgrid, 256, 0, s>>>(dg ? ar.gboff : ar.eboff, dg ? ar.glen : ar.elen,
+                                                      dg ? ar.gfrag : ar.efrag, dg ? a.out_g : a.out_e,
+                                                      ar.eboff, ar.elen, ar.efrag, a.out_e, g.rows, nrows,
+                                                      dg && de ? fgrid : 0xffffffffu,
+                                                      dg && staged && a.off_g ? ar.gbase : nullptr,
+                                                      a.slot_g * 64, dg ? a.efix : nullptr, a.out_e, a.slot_e, g.nplanes,
+                                                      ar.counter, !staged ? ar.ones_rec : nullptr, nrows);
 }
 
 }  // namespace bic
+
+#ifdef BIC_STAMPS  // the stamps build is one unit: the look-back kernels write the same g_stamps
+#include "bic_fused_lookback.hip"
+#endif

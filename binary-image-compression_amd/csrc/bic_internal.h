@@ -115,72 +115,111 @@ void launch_tiles(hipStream_t s, const uint64_t* plane, uint32_t rows, uint32_t 
                   uint32_t* w_nonpred, uint32_t* w_pred, uint8_t* modes, uint64_t* resid,
                   uint64_t* stats);
 
-// Single-pass row encoder (bic_fused.hip), rows of at most 256 words.
-struct FusedScratch {
+// Row encoders for rows of at most 256 words: the staged encoder (bic_fused.hip) and the look-back
+// encoders (bic_fused_lookback.hip). One encode is a FusedCall handed to the launch functions below.
+
+// The device arena of one call, carved from the context's scratch (n = rows * planes). Its layout is
+// fused_layout's walk in bic_fused.hip: the size and the carving both come from it.
+struct FusedArena {
+  // counter: kZeroWords u32 words in 256 bytes. [0] the look-back encoders' tile ticket, [1] slow_n,
+  // [2] the walk list's length, [3] rest_ids', [4] and [5] the k = 0 and k = 1 class lists'; the words from
+  // [6] on are unused ([6..10] served experiments whose code was removed)
   uint32_t* counter;
-  uint64_t *ones_rec, *bits_rec;
-  size_t zero_bytes;  // counter + records, zeroed per launch
-  bool zero_ready = false;  // (single / two-pass) already zero: the previous call's k_fixup cleared them
+  uint64_t *ones_rec, *bits_rec;  // the look-back records
   uint64_t *gboff, *glen, *gfrag, *gslow, *eboff, *elen, *efrag;
-  uint32_t* row_o;   // ones of the plane before each row (two-pass / staged encoders)
+  uint64_t* slow_ids;  // rows k_rows_global must write; their number in *slow_n
   // staged encoder's count pass: per (plane, row, strip) the residual 1-count and the Golomb k
-  // statistics record (bic_kstat.h); ns records per row
-  uint32_t* sones;
+  // statistics record (bic_kstat.h)
   int4* krec;
-  uint32_t* kpos;
-  uint32_t ns;
+  uint32_t *kpos, *sones;
+  uint32_t* row_o;     // ones of the plane before each row (two-pass / staged encoders)
   uint32_t* walk_ids;  // rows whose Golomb length is walked (k_row_walk)
-  uint32_t* walk_o;    // their ones before (row_o), beside the id: the walk loads both at once
   uint32_t* rest_ids;  // rows the REST emit launch writes (mixed k, the plane's first 1; counter[3])
-  // optional second stream for the REST launch (it then runs beside the main emit launch) and
-  // the fork / join events; null: one stream
-  hipStream_t aux = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // (bic_prof_*) recorded on the launch stream around the staged emission's main kernel alone
-  hipEvent_t ev_main0 = nullptr, ev_main1 = nullptr;
-  bool* ev_main_rec = nullptr;  // set true when ev_main1 was recorded (paths without a main kernel leave it)
-  bool counted;      // the count pass already ran (bic_encode_gray's fused bitplane kernel)
-  uint32_t* slow_n;
-  uint64_t* slow_ids;
-  // packed output (staged encoder): when off_g / off_e are set, each coder's streams are written
-  // word-aligned back to back from word 0 of its buffer (what bic_pack_streams makes of slots) and
-  // off_*[0..nplanes] receive the word offsets; pones / gbase / ebase: per-plane scratch
-  uint64_t* off_g = nullptr;
-  uint64_t* off_e = nullptr;
-  uint64_t *pones, *gbase, *ebase;
-  // row index for the decoders (bic_row_index): per row, the bit offset of its first Golomb
-  // codeword in its plane's stream and the residual 1s of the plane before it; null: not written
+  uint32_t* walk_o;    // the walked rows' ones before (row_o), beside the id: the walk loads both at once
+  // per plane: packed output's totals of residual 1s and start words / bits, the EG source's one bit to
+  // clear after the emission (found by the ONES scan; bic_fused.h eg_fix_bit)
+  uint64_t *pones, *gbase, *ebase, *efix;
+  // EG source: the LEN scan lists the rows whose codewords all have k = 0 (entries [0 .. counter[4]))
+  // and all k = 1 (entries [n ..], counter[5]) for the two class emission kernels, each entry two u64
+  // words: the row id | its Golomb length << 32, then its slot-relative Golomb bit offset (gboff's
+  // value): 2 n entries in all. The rows of mixed k stay k_emit_rest's
+  uint64_t* cls;
+  uint64_t* sink;      // 64 words the class kernels' idle lanes store to (a fixed store count)
+  uint32_t* slow_n;    // counter + 1: zeroed with the counter
+  size_t zero_bytes;   // counter + look-back records: what a look-back encoder needs zero at its start
+};
+size_t fused_scratch_bytes(const Geom& g);
+FusedArena carve_fused_arena(void* base, const Geom& g);
+bool fused_supported(const Geom& g);
+
+// One coder's output: nplanes slots of `slot` words from `out`, the planes' bit counts in bits.
+// off (packed output, staged encoder): the streams are written word-aligned back to back from word 0
+// of `out` (what bic_pack_streams makes of slots) and off[0..nplanes] receive their word offsets.
+struct CoderOut {
+  uint64_t* out = nullptr;
+  uint64_t slot = 0;
+  uint64_t *bits = nullptr, *off = nullptr;
+};
+
+// What one call asks of the row encoders.
+struct FusedRequest {
+  CoderOut g, e;  // Golomb, EG; out null: that coder is not wanted
+  // row index for the decoders: per row, the bit offset of its first Golomb codeword in its plane's
+  // stream and the residual 1s of the plane before it; null: not written. Without g.out
+  // (bic_row_index: the staged prefix alone) g.slot still gives the slot the offsets are relative to
   uint64_t* index = nullptr;
   // EG source (bic_encode_gray without planes, slot output): the count pass (launch_gray_rows with
   // out_e) wrote the EG stream in its uniform layout (row r at bit r (cols + 1) + 1) instead of the
   // residual planes; the Golomb kernels read the residual rows back from the stream, and one bit per
-  // plane (efix, found by the ONES scan) is cleared after them (bic_fused.hip eg_fix_bit)
+  // plane (FusedArena::efix) is cleared after them
   bool eg_src = false;
-  uint64_t* efix = nullptr;
-  // EG source: the LEN scan lists the rows whose codewords all have k = 0 (entries [0 .. counter[4]))
-  // and all k = 1 (entries [n ..], counter[5]) for the two class emission kernels (n = rows * planes),
-  // each entry two u64 words: the row id | its Golomb length << 32, then its slot-relative Golomb bit
-  // offset (gboff's value): 2 n entries in all. The rows of mixed k stay k_emit_rest's
-  uint64_t* cls = nullptr;
-  uint64_t* sink = nullptr;   // 64 words the class kernels' idle lanes store to (a fixed store count)
   bool eg_src_one = false;  // (A/B: the one emission kernel k_emit_known for every class instead)
+  bool counted = false;     // the count pass already ran (bic_encode_gray's fused bitplane kernel) ...
+  uint32_t ns = 1;          // ... with ns statistics records per row
+  bool zero_ready = false;  // (look-back encoders) the previous call's k_fixup left zero_bytes cleared
 };
-size_t fused_scratch_bytes(const Geom& g);
-FusedScratch carve_fused_scratch(void* base, const Geom& g);
-bool fused_supported(const Geom& g);
-// host: the fused encoder's byte tables -- lut[0..255] 64-bit entries for k = 3, then (as u32)
-// [2][256] packed entries for k = 1, 2 (bic_fused.hip encode_word); 4 KiB
-void build_byte_lut(uint64_t* lut);
-void launch_fused(hipStream_t s, const Geom& g, const uint64_t* planes, const uint64_t* lut, int predict,
-                  const FusedScratch& fs,
-                  uint64_t* out_g, uint64_t slot_g, uint64_t* bits_g, uint64_t* out_e, uint64_t slot_e,
-                  uint64_t* bits_e, uint32_t* flags, int mode, int stage);
-// launch_fused modes: the staged encoder (prefix kernels, then independent rows; planes 16-byte
-// aligned with an even row pitch), the single kernel with decoupled look-backs, the two-pass one
+
+// the staged encoder (prefix kernels, then independent rows; planes 16-byte aligned with an even row
+// pitch), the single kernel with decoupled look-backs, the two-pass one
 constexpr int kEncStaged = 0, kEncSingle = 1, kEncTwoPass = 2;
-// launch_fused stages: zero the tickets and records; the staged encoder's prefix kernels (counts,
-// scans, lengths); the row kernel(s); the LDS-overflow rows and the words adjacent rows share
-constexpr int kFusedPrep = 0, kFusedRows = 1, kFusedFinish = 2, kFusedPrefix = 3;
+
+struct FusedCall {
+  Geom g;
+  const uint64_t* planes;
+  int predict;
+  int mode;  // kEnc*
+  FusedRequest rq;
+  // the context's: its byte tables (build_byte_lut), its error flags, the arena carved from its scratch
+  const uint64_t* lut;
+  uint32_t* flags;
+  FusedArena ar;
+};
+
+// The staged emission's second stream (k_emit_rest then runs beside the main kernel) with its fork /
+// join events, null: one stream; and (bic_prof_*) the events recorded on the launch stream around the
+// main kernel alone, null: not timed. *main_rec is set when main1 was recorded.
+struct EmitStreams {
+  hipStream_t aux = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+  hipEvent_t main0 = nullptr, main1 = nullptr;
+  bool* main_rec = nullptr;
+};
+
+// host: the fused encoder's byte tables -- lut[0..255] 64-bit entries for k = 3, then (as u32)
+// [2][256] packed entries for k = 1, 2 (bic_fused.h encode_word); 4 KiB
+void build_byte_lut(uint64_t* lut);
+// The launches of one encode, in order (all asynchronous on `s`):
+// look-back encoders: zero the tile ticket and the records, unless rq.zero_ready
+void launch_lookback_clear(hipStream_t s, const FusedCall& c);
+// staged: the count pass unless rq.counted, the ONES scan, then -- with golomb_lengths -- the walk of
+// the mixed-k rows and the LEN scan (+ the row index), and the packed planes' bases
+void launch_staged_prefix(hipStream_t s, const FusedCall& c, bool golomb_lengths);
+// staged: k_emit_rest (on es.aux, forked from and joined back into s) and the main emission kernel
+void launch_staged_emit(hipStream_t s, const FusedCall& c, const EmitStreams& es);
+// look-back encoders: the single kernel (kEncSingle) or the length and emission passes (kEncTwoPass)
+void launch_lookback_rows(hipStream_t s, const FusedCall& c);
+// every encoder: the LDS-overflow rows (k_rows_global) and the words adjacent rows share (k_fixup)
+void launch_fused_finish(hipStream_t s, const FusedCall& c);
 // the staged encoder's count passes also zero its kZeroWords counters (no separate fill launch)
 constexpr uint32_t kZeroWords = 64;
 void launch_row_ones(hipStream_t s, const Geom& g, const uint64_t* planes, int predict, uint32_t* sones,
@@ -191,14 +230,14 @@ bool gray_rows_supported(const Geom& g, const void* gray, size_t pitch, const vo
 uint32_t gray_strips(const Geom& g);
 // store_resid: the words stored are the med residual R (planes = the caller's bitplanes are not
 // wanted; the encoder then reads R with predict off), not the bitplanes P. out_e (with predict, the
-// bitplanes not wanted): the EG stream instead of R (FusedScratch::eg_src; slots of eg_stride
+// bitplanes not wanted): the EG stream instead of R (FusedRequest::eg_src; slots of eg_stride
 // words); planes is then unused. bps = 2 (bic_encode_gray16): samples of two bytes, big-endian
 // (pnm.cpp:71-74) or the host's order, planes plane0 .. of 16 (k_gray_strips16)
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero,
                       bool store_resid = false, uint64_t* out_e = nullptr, uint64_t eg_stride = 0, int bps = 1,
                       int big_endian = 0);
-// the count pass can write the EG stream (FusedScratch::eg_src): rows of whole 64-word strips only
+// the count pass can write the EG stream (FusedRequest::eg_src): rows of whole 64-word strips only
 bool gray_eg_supported(const Geom& g);
 
 void launch_patch_search(hipStream_t s, const uint64_t* plane, uint32_t rows, uint32_t cols, uint32_t wpr,

@@ -547,7 +547,7 @@ constexpr bool kGrayByteMed = BIC_GRAY_BYTEMED != 0;
 // EGS (FULL strips of rows of whole strips, BM): the EG stream instead of R (eg.cpp:20-37 with the
 // block size fixed at 1: per row ~R then the end-of-row '1'), in the uniform layout -- bit 0 a '1', row
 // r at bit r (cols + 1) + 1 of plane b's slot (word b * eg_stride) -- which is the stream but for one
-// bit (bic_fused.hip eg_fix_bit). With the strip's first bit at offset e of a word, lane l stores the
+// bit (bic_fused.h eg_fix_bit). With the strip's first bit at offset e of a word, lane l stores the
 // word that starts inside its own row word: its bits and lane l + 1's; lane 63's word crosses the
 // strip's end, so the wave also forms the first word of what follows -- the next strip's, or after
 // the row's '1' the next row's -- from one pixel per lane of that segment (two byte loads, the med on
@@ -2059,7 +2059,7 @@ void launch_patch_search(hipStream_t s, const uint64_t* plane, uint32_t rows, ui
 }
 
 // ------------------------------------------------------------------------------------
-// Host: the fused encoder's byte table (bic_fused.hip encode_word). For k in 1..3 and byte v
+// Host: the fused encoder's byte table (bic_fused.h encode_word). For k in 1..3 and byte v
 // (MSB = first pixel), the codewords of the runs that start AND end inside v -- between its
 // first and last 1 -- as one MSB-first pattern, with the byte's leading and trailing zeros.
 void build_byte_lut(uint64_t* lut) {

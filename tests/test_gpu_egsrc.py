@@ -2,7 +2,7 @@
 the count pass writes each plane's EG stream (eg.cpp:20-37 with the block size fixed at 1) in its
 uniform layout -- row r at bit r (cols + 1) + 1 -- and the Golomb kernels read the residual rows
 back from it; the ONES scan assembles the words across strip edges and one bit per plane is
-cleared after the emission (bic_fused.hip eg_src_junctions / eg_fix_bit). Against the oracle and
+cleared after the emission (bic_fused.hip eg_src_junctions, bic_fused.h eg_fix_bit). Against the oracle and
 against the round-3 path (residual planes in a context buffer), at every row-offset phase (rows
 >= 64: offsets whose bit is 0 and 63 in their word), 1 to 4 strips per row, the plane's first 1 at
 column 0 of a later row, on a strip edge, far down the plane, and planes without a residual 1."""

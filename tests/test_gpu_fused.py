@@ -1,4 +1,4 @@
-"""The row encoders (bic_fused.hip: the default staged one, the single kernel and the two-pass one) against the
+"""The row encoders (bic_fused.hip: the default staged one; bic_fused_lookback.hip: the single kernel and the two-pass one) against the
 oracle and against the multi-pass chunk kernels, with inputs built to reach each of their paths:
 k = 0 copy mode, byte tables, lanes whose codewords exceed the 128-bit register string, rows whose
 output exceeds the LDS window (global fallback), many short rows sharing one output word (fixup

@@ -61,3 +61,73 @@ def test_prof_rows_timing_every_encoder(ctx, encoder):
         ctx.prof_only(None)
         ctx.prof_enable(False)
         ctx.set_encoder("auto")
+
+
+def _planes2(predict):
+    return lambda ctx, planes, gray: ctx.encode_planes2(planes, 4096, predict=predict)
+
+
+def _packed_index(ctx, planes, gray):
+    return ctx.encode_planes_packed(planes, 4096, golomb=True, eg=True, row_index=ctx.empty_i64(2 * 70 * 2))
+
+
+def _gray(store_planes):
+    return lambda ctx, planes, gray: ctx.encode_gray(gray, store_planes=store_planes)
+
+
+_STAGED = [("encode_finish", 1), ("encode_prefix", 1)]
+_LOOKBACK = [("encode_finish", 1)]
+_ROWS_GE = [("encode_rows_golomb_eg", 1), ("encode_rows_golomb_eg_stage", 1)]
+_GRAY = [("bitplanes_count", 1)] + _STAGED
+# (path, encoder, BIC_OPT_EG_SOURCE, the call, bic_prof_collect's lines: name and launch count, in its
+# order) -- the lists are those of a run of the commit before the host side of the row encoders was
+# reorganised into one driver (bic_capi.cpp run_fused), on these inputs
+_RECORD_PATHS = [
+    ("planes2-staged-predict", "staged", 1, _planes2(True), _STAGED + _ROWS_GE),
+    ("planes2-staged-nopredict", "staged", 1, _planes2(False), _STAGED + _ROWS_GE),
+    ("planes2-single-kernel", "single-kernel", 1, _planes2(True), _LOOKBACK + _ROWS_GE),
+    ("planes2-two-pass", "two-pass", 1, _planes2(True), _LOOKBACK + _ROWS_GE),
+    ("packed-index-staged", "staged", 1, _packed_index, _STAGED + _ROWS_GE),
+    ("packed-index-single-kernel", "single-kernel", 1, _packed_index,
+     _LOOKBACK + _ROWS_GE + [("pack", 2), ("row_index", 1)]),
+    ("gray-eg-source", "staged", 1, _gray(False),
+     _GRAY + [("encode_rows_golomb_egsrc", 1), ("encode_rows_golomb_egsrc_stage", 1)]),
+    ("gray-resid", "staged", 0, _gray(False), _GRAY + _ROWS_GE),
+    ("gray-planes", "staged", 1, _gray(True), _GRAY + _ROWS_GE),
+    ("row-index", "auto", 1, lambda ctx, planes, gray: ctx.row_index(planes, 4096), [("row_index", 1)]),
+]
+
+
+@pytest.fixture(scope="module")
+def record_inputs(ctx):
+    t = ctx.torch
+    g = t.Generator(device=ctx.dev)
+    g.manual_seed(11)
+    planes = t.randint(-2**62, 2**62, (2, 70, 64), dtype=t.int64, device=ctx.dev, generator=g)
+    gray = t.randint(0, 256, (70, 4096), dtype=t.uint8, device=ctx.dev, generator=g)
+    ctx.sync()
+    return planes, gray
+
+
+@pytest.mark.parametrize("path", _RECORD_PATHS, ids=[p[0] for p in _RECORD_PATHS])
+def test_record_names_per_path(ctx, record_inputs, path):
+    """what one call of each encode path records with profiling on and no bic_prof_only: the stages
+    the driver runs for it (70 x 4096: 2 planes, or the 8 of a gray image), pinned against the lists
+    above"""
+    _, encoder, eg_source, call, expected = path
+    planes, gray = record_inputs
+    ctx.prof_collect()
+    ctx.set_encoder(encoder)
+    ctx.set_eg_source(eg_source)
+    ctx.prof_enable(True)
+    try:
+        ctx.prof_only(None)
+        call(ctx, planes, gray)
+        got = ctx.prof_collect()
+        assert [(k, v[0]) for k, v in got.items()] == expected
+        assert all(v[1] >= 0 for v in got.values()), got
+    finally:
+        ctx.prof_only(None)
+        ctx.prof_enable(False)
+        ctx.set_eg_source(1)
+        ctx.set_encoder("auto")
