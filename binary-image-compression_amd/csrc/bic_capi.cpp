@@ -791,6 +791,33 @@ int bic_decode_planes(bic_ctx* ctx, int coder, const uint64_t* streams, size_t s
   return BIC_OK;
 }
 
+int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                    const uint64_t* plane_bits, const uint64_t* index, int plane0, int nplanes, size_t rows, size_t cols,
+                    int predict, const uint8_t* p00, int sample_bytes, int big_endian, void* gray, size_t pitch) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (coder != BIC_CODER_GOLOMB && coder != BIC_CODER_EG && coder != BIC_CODER_EG_ADAPTIVE) return BIC_EINVAL;
+  if ((sample_bytes != 1 && sample_bytes != 2) || plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 * sample_bytes)
+    return BIC_EINVAL;
+  const size_t wpr = (cols + 63) / 64;
+  if (!geom_ok(rows, cols, wpr) || !bic::decode_supported((uint32_t)cols) || pitch < cols * (size_t)sample_bytes)
+    return BIC_EINVAL;
+  if (rows == 0) return BIC_OK;
+  if (!streams || !plane_bits || !gray || (slot_words == 0 && !word_off)) return BIC_EINVAL;
+  if ((coder == BIC_CODER_GOLOMB || coder == BIC_CODER_EG_ADAPTIVE) && !index) return BIC_EINVAL;
+  if ((rc = ensure_scratch(ctx, bic::decode_gray_scratch_bytes((uint32_t)rows, (uint32_t)wpr, (uint32_t)nplanes))))
+    return rc;
+  const bic::GrayOut go{static_cast<uint8_t*>(gray), (uint64_t)pitch, plane0, sample_bytes,
+                        sample_bytes == 2 && big_endian ? 1 : 0};
+  timed(ctx, "decode_gray", [&] {
+    bic::launch_decode(ctx->cur, coder == BIC_CODER_GOLOMB ? 0 : coder == BIC_CODER_EG ? 1 : 2, streams, slot_words,
+                       word_off, plane_bits, index, p00, (uint32_t)rows, (uint32_t)cols, (uint32_t)wpr, (uint32_t)nplanes,
+                       predict ? 1 : 0, nullptr, ctx->scratch, ctx->flags, ctx->lut + bic::kLutEgadDec, &go);
+  });
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
 int bic_encode_gray(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size_t rows, size_t cols, int nplanes,
                     uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
                     uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg) {

@@ -954,6 +954,140 @@ __global__ __launch_bounds__(256) void k_col_apply(uint64_t* __restrict__ D, con
   }
 }
 
+// k_col_apply and k_planes_gray in one pass (bic_decode_gray): D -> gray samples; P is never written.
+// A lane takes kGraySeg columns of one chunk -- a quarter of a D word, so that configs[2]'s size
+// launches 4,096 waves (four per SIMD; a lane per whole word: 1,024, each a serial 64-row loop), a
+// lane's 16 one-byte samples are one 16-byte store and a wave's stores one contiguous KiB. It holds
+// one accumulator per sample bit, started from the chunk's totals (SCAN; without prediction the D
+// buffer holds the planes themselves and the accumulator is the row's own segment), and per row XORs
+// in each plane's D segment, gathers the accumulators' bytes into the 8 x 8 blocks (TL / TH as in
+// k_planes_gray), transposes them and stores the samples in the chosen byte order. The loads of
+// kGrayRows rows x all sample bits are issued before the first is used, unconditionally: rows past
+// the chunk's end read its last row, sample bits no plane covers read the nearest decoded plane and
+// are cleared in the output words (omask). 16-byte stores for the segments of full 64-sample words on
+// 16-byte aligned rows (VEC), byte stores otherwise, as k_planes_gray decides.
+// Measured at configs[2]'s size, streams -> image (profiles/r09): segments of 16 / 32 / 64 columns 696 / 700 /
+// 727 us from Golomb streams and 438 / 441 / 472 us from EG streams (the two calls there: 782 and 580 us).
+constexpr int kGraySeg = 16;
+template <int Q> struct SegWord;  // the segment as loaded and as held in registers
+template <> struct SegWord<16> { using load = uint16_t; using reg = uint32_t; };
+template <> struct SegWord<32> { using load = uint32_t; using reg = uint32_t; };
+template <> struct SegWord<64> { using load = uint64_t; using reg = uint64_t; };
+struct GrayArgs {
+  const uint64_t* D;     // [nplanes][rows][wpr]
+  const uint64_t* ctot;  // [nplanes][chunks][wpr]: k_col_scan_par's exclusive totals (SCAN)
+  uint32_t rows, cols, wpr;
+  int plane0, nplanes;
+  uint8_t* gray;
+  uint64_t pitch;
+  uint32_t sel0, sel1;  // blocks_to_samples' byte order (BPS 2)
+  uint32_t omask;       // an output word's bits that some plane covers
+};
+template <int BPS, bool VEC, bool SCAN>
+__global__ __launch_bounds__(256) void k_col_apply_gray(GrayArgs a) {
+  using T = typename SegWord<kGraySeg>::load;  // kGraySeg bits of a D word
+  using RT = typename SegWord<kGraySeg>::reg;
+  constexpr int Q = kGraySeg, NG = Q / 8, SUB = 64 / Q, NB = 8 * BPS;
+  constexpr int kGrayRows = 64 / (NB * (int)(sizeof(RT) / 4));  // 64 registers of loads in flight per lane
+  const uint32_t nch = (a.rows + kColChunk - 1) / kColChunk, segs = (a.cols + Q - 1) / Q;
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;  // (nch * segs < 2^26: rows * (cols + 1) < 2^31)
+  if (t >= nch * segs) return;
+  const uint32_t sg = t % segs, c = t / segs;
+  const uint32_t w = sg / SUB, sub = SUB - 1 - sg % SUB;  // the segment's place in its (little-endian) word
+  const uint32_t r0 = c * kColChunk, nr = min(kColChunk, a.rows - r0);
+  const uint32_t rowb = a.wpr * 8;
+  const uint64_t plane_bytes = (uint64_t)a.rows * rowb;
+  // loads as a wave-uniform base (the workgroup's first chunk of the sample bit's plane) plus a 32-bit
+  // lane offset: a workgroup spans at most 256 / segs + 2 chunks
+  const uint32_t c0 = uni_u32(blockIdx.x * 256 / segs);
+  const char* base = reinterpret_cast<const char*>(a.D) + (uint64_t)c0 * kColChunk * rowb;
+  const uint32_t loff = (c - c0) * kColChunk * rowb + w * 8 + sub * (Q / 8);
+  RT acc[NB];
+#pragma unroll
+  for (int sb = 0; sb < NB; ++sb) {
+    const uint32_t b = (uint32_t)min(max(sb - a.plane0, 0), a.nplanes - 1);
+    acc[sb] = SCAN ? reinterpret_cast<const T*>(a.ctot + ((uint64_t)b * nch + c) * a.wpr + w)[sub] : (RT)0;
+  }
+  uint8_t* dst = a.gray + (uint64_t)r0 * a.pitch + (uint64_t)sg * (Q * BPS);
+  const uint32_t nbytes = min((uint32_t)Q, a.cols - Q * sg) * BPS;
+  const bool vec = VEC && 64 * (w + 1) <= a.cols;
+  for (uint32_t rb = 0; rb < nr; rb += kGrayRows) {
+    RT d[kGrayRows][NB];
+#pragma unroll
+    for (int k = 0; k < kGrayRows; ++k) {
+      const uint32_t voff = loff + min(rb + k, nr - 1) * rowb;
+#pragma unroll
+      for (int sb = 0; sb < NB; ++sb) {
+        const uint32_t b = (uint32_t)min(max(sb - a.plane0, 0), a.nplanes - 1);
+        d[k][sb] = *reinterpret_cast<const T*>(base + (uint64_t)b * plane_bytes + voff);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kGrayRows; ++k) {
+      if (rb + k >= nr) break;
+      uint64_t TL[NG], TH[NG];
+#pragma unroll
+      for (int g = 0; g < NG; ++g) TL[g] = TH[g] = 0;
+#pragma unroll
+      for (int sb = 0; sb < NB; ++sb) {
+        acc[sb] = SCAN ? acc[sb] ^ d[k][sb] : d[k][sb];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          const uint64_t byte = (uint64_t)((acc[sb] >> (Q - 8 - 8 * g)) & 0xffu) << (8 * (sb & 7));
+          if (sb < 8) TL[g] |= byte;
+          else TH[g] |= byte;
+        }
+      }
+      uint32_t out[BPS * 2 * NG];  // the segment's samples in memory order
+      blocks_to_samples<BPS, NG>(TL, TH, a.sel0, a.sel1, out);
+#pragma unroll
+      for (int q = 0; q < BPS * 2 * NG; ++q) out[q] &= a.omask;
+      uint8_t* p = dst + (uint64_t)(rb + k) * a.pitch;
+      if (vec) {
+#pragma unroll
+        for (int q = 0; q < BPS * NG / 2; ++q)
+          reinterpret_cast<uint4*>(p)[q] = make_uint4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
+      } else if (nbytes == Q * BPS) {
+#pragma unroll
+        for (int i = 0; i < Q * BPS; ++i) p[i] = (uint8_t)(out[i >> 2] >> (8 * (i & 3)));
+      } else {  // the row's last segment
+#pragma unroll
+        for (int i = 0; i < Q * BPS; ++i)
+          if ((uint32_t)i < nbytes) p[i] = (uint8_t)(out[i >> 2] >> (8 * (i & 3)));
+      }
+    }
+  }
+}
+
+void launch_col_apply_gray(hipStream_t s, const uint64_t* D, const uint64_t* ctot, uint32_t rows, uint32_t cols,
+                           uint32_t wpr, uint32_t nplanes, const GrayOut& go) {
+  GrayArgs a;
+  a.D = D;
+  a.ctot = ctot;
+  a.rows = rows;
+  a.cols = cols;
+  a.wpr = wpr;
+  a.plane0 = go.plane0;
+  a.nplanes = (int)nplanes;
+  a.gray = go.gray;
+  a.pitch = go.pitch;
+  a.sel0 = go.big_endian ? kSelBE0 : kSelLE0;
+  a.sel1 = go.big_endian ? kSelBE1 : kSelLE1;
+  const uint32_t smask = ((1u << nplanes) - 1u) << go.plane0, lo = smask & 0xffu, hi = smask >> 8;
+  a.omask = go.bps == 1 ? lo * 0x01010101u : (go.big_endian ? hi | lo << 8 : lo | hi << 8) * 0x00010001u;
+  const uint64_t nt = (uint64_t)((rows + kColChunk - 1) / kColChunk) * ((cols + kGraySeg - 1) / kGraySeg);
+  const uint32_t grid = (uint32_t)((nt + 255) / 256);
+  const bool vec = reinterpret_cast<uintptr_t>(go.gray) % 16 == 0 && go.pitch % 16 == 0;
+#define BIC_CAG(B, V)                                                  \
+  do {                                                                 \
+    if (ctot) k_col_apply_gray<B, V, true><<<grid, 256, 0, s>>>(a);    \
+    else k_col_apply_gray<B, V, false><<<grid, 256, 0, s>>>(a);        \
+  } while (0)
+  if (go.bps == 1) { if (vec) BIC_CAG(1, true); else BIC_CAG(1, false); }
+  else { if (vec) BIC_CAG(2, true); else BIC_CAG(2, false); }
+#undef BIC_CAG
+}
+
 bool decode_supported(uint32_t cols) { return cols >= 1 && (cols + 63) / 64 <= kDecRowWords; }
 
 size_t decode_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes) {
@@ -961,10 +1095,20 @@ size_t decode_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes) {
   return (size_t)nplanes * nch * wpr * 8 + (size_t)nplanes * 4 + 256;
 }
 
+// bic_decode_gray's arena: bic_decode_planes' scratch, then the D buffer (nplanes * rows * wpr words)
+static size_t decode_gray_dbuf_offset(uint32_t rows, uint32_t wpr, uint32_t nplanes) {
+  return (decode_scratch_bytes(rows, wpr, nplanes) + 255) & ~(size_t)255;
+}
+size_t decode_gray_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes) {
+  return decode_gray_dbuf_offset(rows, wpr, nplanes) + (size_t)nplanes * rows * wpr * 8;
+}
+
 void launch_decode(hipStream_t s, int coder, const uint64_t* streams, uint64_t slot, const uint64_t* word_off,
                    const uint64_t* plane_bits, const uint64_t* index, const uint8_t* p00, uint32_t rows,
                    uint32_t cols, uint32_t wpr, uint32_t nplanes, int predict, uint64_t* out, void* scratch,
-                   uint32_t* flags, const uint64_t* egnib) {
+                   uint32_t* flags, const uint64_t* egnib, const GrayOut* go) {
+  // to gray samples: the row kernels' output goes to the arena's D buffer instead of the caller's planes
+  if (go) out = reinterpret_cast<uint64_t*>(static_cast<char*>(scratch) + decode_gray_dbuf_offset(rows, wpr, nplanes));
   DecArgs a;
   a.egnib = egnib;
   a.rows = rows;
@@ -1007,8 +1151,9 @@ void launch_decode(hipStream_t s, int coder, const uint64_t* streams, uint64_t s
     const uint64_t nt = (uint64_t)nplanes * nch * wpr;
     if (!fused_chunks) k_col_chunks<<<(uint32_t)((nt + 255) / 256), 256, 0, s>>>(out, ctot, rows, wpr, nplanes);
     k_col_scan_par<<<nplanes * wpr, 256, 0, s>>>(ctot, rows, wpr);
-    k_col_apply<<<(uint32_t)((nt + 255) / 256), 256, 0, s>>>(out, ctot, rows, wpr, nplanes);
+    if (!go) k_col_apply<<<(uint32_t)((nt + 255) / 256), 256, 0, s>>>(out, ctot, rows, wpr, nplanes);
   }
+  if (go) launch_col_apply_gray(s, out, predict ? ctot : nullptr, rows, cols, wpr, nplanes, *go);
 }
 
 }  // namespace bic

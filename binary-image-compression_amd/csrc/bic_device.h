@@ -292,6 +292,46 @@ __device__ __forceinline__ uint32_t golomb_k_state(uint32_t n, uint32_t A) {
 
 __device__ __forceinline__ uint64_t bswap64(uint64_t x) { return __builtin_bswap64(x); }
 
+// ------------------------------------------------------------------------------------
+// gray samples out of bit planes (k_planes_gray, k_col_apply_gray): per group of 8 samples the 8 x 8
+// bit block whose byte b is plane b's byte of the group; its transpose (an involution) holds the 8
+// samples' bytes.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t transpose8x8_r(uint64_t x) {
+  uint64_t t;
+  t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;
+  x = x ^ t ^ (t << 7);
+  t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull;
+  x = x ^ t ^ (t << 14);
+  t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull;
+  x = x ^ t ^ (t << 28);
+  return x;
+}
+// v_perm_b32 selectors that interleave four samples' low bytes (source 0) and high bytes (source 1):
+// big-endian (hi0 lo0 hi1 lo1: the P5 order) and the host's little-endian order
+constexpr uint32_t kSelBE0 = 0x05010400u, kSelBE1 = 0x07030602u, kSelLE0 = 0x01050004u, kSelLE1 = 0x03070206u;
+// NG groups' blocks of the samples' low (TL) and high (TH, BPS 2) bytes -> the 8 NG samples' bytes in
+// memory order (k_planes_gray's steps for its eight groups, with the byte order a parameter)
+template <int BPS, int NG>
+__device__ __forceinline__ void blocks_to_samples(const uint64_t (&TL)[NG], const uint64_t (&TH)[NG], uint32_t sel0,
+                                                  uint32_t sel1, uint32_t (&out)[BPS * 2 * NG]) {
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const uint64_t lo = bswap64(transpose8x8_r(TL[g]));  // byte k = sample 8g + k's low byte
+    if constexpr (BPS == 1) {
+      out[2 * g] = (uint32_t)lo;
+      out[2 * g + 1] = (uint32_t)(lo >> 32);
+    } else {
+      const uint64_t hi = bswap64(transpose8x8_r(TH[g]));
+      const uint32_t l0 = (uint32_t)lo, l1 = (uint32_t)(lo >> 32), h0 = (uint32_t)hi, h1 = (uint32_t)(hi >> 32);
+      out[4 * g] = __builtin_amdgcn_perm(l0, h0, sel0);
+      out[4 * g + 1] = __builtin_amdgcn_perm(l0, h0, sel1);
+      out[4 * g + 2] = __builtin_amdgcn_perm(l1, h1, sel0);
+      out[4 * g + 3] = __builtin_amdgcn_perm(l1, h1, sel1);
+    }
+  }
+}
+
 // Bits of the Golomb codewords whose '1' lies in residual word w of a row (plus the end-of-row
 // codeword when eol) -- the length the row encoder's emission produces for that word -- without
 // forming any codeword. n = samples of the plane before the word's first 1, jp = column of the

@@ -67,11 +67,21 @@ constexpr size_t kLutWords = kLutEgadDec + 992;    // the whole buffer
 // f1 decoders (bic_decode.hip)
 bool decode_supported(uint32_t cols);
 size_t decode_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes);
-// egnib: egad_build_dec_nib's table in device memory (the context's byte-table buffer, kLutEgadDec)
+// bic_decode_gray: the samples the decoded planes (plane b = bit plane0 + b) go to, and its arena
+// (decode_scratch_bytes plus the D buffer of nplanes * rows * wpr words)
+struct GrayOut {
+  uint8_t* gray;
+  uint64_t pitch;
+  int plane0, bps, big_endian;
+};
+size_t decode_gray_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes);
+// egnib: egad_build_dec_nib's table in device memory (the context's byte-table buffer, kLutEgadDec).
+// go null: streams -> planes in `out`; otherwise streams -> gray samples (`out` unused, the scratch
+// sized by decode_gray_scratch_bytes)
 void launch_decode(hipStream_t s, int coder, const uint64_t* streams, uint64_t slot, const uint64_t* word_off,
                    const uint64_t* plane_bits, const uint64_t* index, const uint8_t* p00, uint32_t rows,
                    uint32_t cols, uint32_t wpr, uint32_t nplanes, int predict, uint64_t* out, void* scratch,
-                   uint32_t* flags, const uint64_t* egnib);
+                   uint32_t* flags, const uint64_t* egnib, const GrayOut* go = nullptr);
 // the adaptive EG decoder's nibble table (62 states x 16 nibbles, u64), built on the host
 void egad_build_dec_nib(uint64_t* T);
 void launch_med_rows(hipStream_t s, const Geom& g, const uint64_t* planes, int predict, uint64_t* resid,

@@ -27,17 +27,6 @@ __device__ __forceinline__ uint64_t bytes8(const uint8_t* base, uint64_t p, uint
   return (lo >> (8 * s)) | (hi << (64 - 8 * s));
 }
 
-__device__ __forceinline__ uint64_t transpose8x8_r(uint64_t x) {
-  uint64_t t;
-  t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;
-  x = x ^ t ^ (t << 7);
-  t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull;
-  x = x ^ t ^ (t << 14);
-  t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull;
-  x = x ^ t ^ (t << 28);
-  return x;
-}
-
 // P4 raster -> plane. Thread per plane word. `base` is the raster's 8-aligned floor (off = the
 // raster's byte offset in it), so every load is aligned.
 __global__ __launch_bounds__(256) void k_pbm_unpack2(const uint8_t* __restrict__ base, uint32_t off, uint32_t rows,

@@ -30,7 +30,7 @@ EXPORTS = [
     "bic_bitplanes_u8_range", "bic_encode_gray_range", "bic_encode_planes_packed", "bic_encode_gray_packed",
     "bic_row_index", "bic_decode_planes", "bic_pgm_bitplanes", "bic_pnm_parse_header",
     "bic_gf2_transpose", "bic_gf2_mul", "bic_planes_to_gray", "bic_match_encode_inv", "bic_match_encode_var", "bic_egad_row_index",
-    "bic_encode_gray16", "bic_encode_gray16_packed", "bic_bitplanes_u16",
+    "bic_encode_gray16", "bic_encode_gray16_packed", "bic_bitplanes_u16", "bic_decode_gray",
 ]
 
 # bic_gf2_mul ops (include/bic.h)
@@ -125,6 +125,7 @@ def load(path=LIB_PATH):
     sig("bic_encode_gray16", i32, [vp, vp, sz, sz, sz, i32, i32, i32, vp, sz, i32, vp, sz, vp, vp, sz, vp])
     sig("bic_encode_gray16_packed", i32, [vp, vp, sz, sz, sz, i32, i32, i32, vp, sz, i32, vp, sz, vp, vp, vp, sz, vp,
                                           vp, vp])
+    sig("bic_decode_gray", i32, [vp, i32, vp, sz, vp, vp, vp, i32, i32, sz, sz, i32, vp, i32, i32, vp, sz])
     _lib = L
     return L
 
@@ -445,6 +446,20 @@ class Context:
         self._chk(self.lib.bic_decode_planes(self.h, coder, _p(streams), slot, _p(word_off), _p(plane_bits),
                                              _p(row_index), nplanes, rows, cols, wpr, int(predict), _p(p00), _p(out)),
                   "bic_decode_planes")
+        return out
+
+    def decode_gray(self, coder, streams, plane_bits, nplanes, rows, cols, predict=True, word_off=None,
+                    row_index=None, p00=None, plane0=0, sample_bytes=1, big_endian=True, out=None, pitch=None):
+        """bic_decode_gray: streams (as for decode_planes) -> uint8 device tensor [rows, pitch] of samples,
+        stream b in bit plane0 + b (sample_bytes 2: big-endian, or the host's order with big_endian=False).
+        out: a uint8 device tensor whose first byte is row 0's first (any alignment), rows `pitch` apart."""
+        pitch = pitch or cols * sample_bytes
+        out = self.torch.zeros(rows, pitch, dtype=self.torch.uint8, device=self.dev) if out is None else out
+        slot = streams.shape[-1] if (word_off is None and streams.dim() == 2) else 0
+        self._bind_stream()
+        self._chk(self.lib.bic_decode_gray(self.h, coder, _p(streams), slot, _p(word_off), _p(plane_bits),
+                                           _p(row_index), plane0, nplanes, rows, cols, int(predict), _p(p00),
+                                           sample_bytes, int(big_endian), _p(out), pitch), "bic_decode_gray")
         return out
 
     def _packed_bufs(self, n, rows, cols, golomb, eg, slots, outs, bits, offs):

@@ -192,8 +192,8 @@ int bic_encode_gray_packed(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size
  * 16384 columns whose gray rows hold ceil(cols/64)*128 readable bytes read the image once (with planes
  * NULL, predict and the EG stream into slots the count pass writes the EG stream itself, as for
  * bic_encode_gray); otherwise the same result through the two separate calls. The device round trip of
- * a 16-bit image is gray -> bic_encode_gray16_packed -> bic_decode_planes -> bic_planes_to_gray
- * (sample_bytes = 2). */
+ * a 16-bit image is gray -> bic_encode_gray16_packed -> bic_decode_gray (sample_bytes = 2, the same
+ * big_endian). */
 int bic_encode_gray16(bic_ctx* ctx, const void* gray, size_t pitch, size_t rows, size_t cols, int big_endian,
                       int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
                       size_t slot_golomb, uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg);
@@ -229,6 +229,23 @@ int bic_egad_row_index(bic_ctx* ctx, const uint64_t* planes, int nplanes, size_t
 int bic_decode_planes(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
                       const uint64_t* plane_bits, const uint64_t* row_index, int nplanes, size_t rows, size_t cols,
                       size_t wpr, int predict, const uint8_t* p00, uint64_t* planes);
+/* streams -> gray samples in one call: bic_decode_planes followed by bic_planes_to_gray, without the
+ * planes. coder, streams, slot_words, word_off, plane_bits, row_index, predict, p00, the limit
+ * cols <= 16384 and BIC_EDATA from bic_sync for a malformed stream (the samples are then undefined) as
+ * for bic_decode_planes; the samples as bic_planes_to_gray writes them: stream b sets bit plane0 + b
+ * of each sample, bits no plane covers are 0, sample_bytes 1 (plane0 + nplanes <= 8) or 2 (<= 16),
+ * gray = rows of `pitch` bytes (device, any byte alignment of pointer and pitch), of which only the
+ * first cols * sample_bytes are written. big_endian (sample_bytes 2 only): 1 = the P5 order
+ * bic_planes_to_gray writes, 0 = the host's uint16_t (what bic_encode_gray16 reads with big_endian = 0).
+ * The row decoders write D (the planes XORed with the row above; the planes themselves without
+ * prediction) into a buffer the context keeps -- nplanes * rows * ceil(cols/64) words in the scratch
+ * arena, which grows to the largest call and lives until bic_ctx_destroy -- and unmed's last kernel
+ * forms the samples as it sums D down the columns: the planes are never written. rows = 0: BIC_OK,
+ * nothing written. */
+int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words,
+                    const uint64_t* word_off, const uint64_t* plane_bits, const uint64_t* row_index,
+                    int plane0, int nplanes, size_t rows, size_t cols, int predict, const uint8_t* p00,
+                    int sample_bytes, int big_endian, void* gray, size_t pitch);
 /* A slot size (64-bit words) that every plane of this geometry fits for EG (exact) and for
  * Golomb on any input this build has seen (2*rows*(cols+1) bits + 64 words); a larger input
  * still reports BIC_ENOSPC rather than writing out of bounds. */
@@ -371,8 +388,9 @@ int bic_pgm_bitplanes(bic_ctx* ctx, const uint8_t* raster, size_t rows, size_t c
  * of each sample, bits no plane covers are 0. sample_bytes 1: one byte per sample (plane0 + nplanes
  * <= 8); 2: two bytes big-endian, the P5 raster write_p5_data writes for maxval >= 256
  * (pnm.cpp:111-124; plane0 + nplanes <= 16). gray: device, rows of `pitch` bytes (any alignment);
- * only the rows' first cols * sample_bytes bytes are written. The device round trip is then
- * gray -> bic_encode_gray_packed -> bic_decode_planes -> bic_planes_to_gray. */
+ * only the rows' first cols * sample_bytes bytes are written. From streams, bic_decode_gray writes
+ * the same samples without the planes: the device round trip is gray -> bic_encode_gray_packed ->
+ * bic_decode_gray. */
 int bic_planes_to_gray(bic_ctx* ctx, const uint64_t* planes, int plane0, int nplanes, size_t rows, size_t cols,
                        size_t wpr, int sample_bytes, void* gray, size_t pitch);
 

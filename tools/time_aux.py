@@ -1,8 +1,9 @@
 """Timing of the §8 rows beside the encoder (measurement for DESIGN.md §3, not a test): at configs[2]'s
 size (8 planes of 16384^2, Bernoulli(0.5) pixels, device-resident) -- the packed encoder with its row
 index, the device decoders (Golomb from the index, EG, both through unmed), the adaptive EG coder
-(encode, its row index and its device decoder), bic_row_index from planes, PBM unpack / pack of one plane, P5 raster -> planes, planes -> gray. HIP events
-around R launches of each call after a warm-up; every decode is checked against the planes.
+(encode, its row index and its device decoder), bic_row_index from planes, PBM unpack / pack of one plane, P5 raster -> planes, planes -> gray,
+and streams -> gray image in one call (bic_decode_gray) beside the two calls it replaces, alternating. HIP events
+around R launches of each call after a warm-up; every decode is checked against the planes or the image.
 Usage: python tools/time_aux.py [--reps R] > gpurun_out/time_aux.json"""
 import argparse
 import json
@@ -17,6 +18,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rows", type=int, default=16384)
+    ap.add_argument("--alternations", type=int, default=3, help="repeats of the one-call / two-call decode pair")
     args = ap.parse_args()
     import torch
     import pybic
@@ -113,6 +115,43 @@ def main():
     timed("planes_to_gray", lambda: ctx.planes_to_gray(pl8, cols, out=g8), rows * cols + plane_bytes)
     ctx.sync()
     out["planes_to_gray_ok"] = bool(torch.equal(g8, gray[:rows * cols].view(rows, cols)))
+    ctx.sync()
+
+    # streams -> gray image: bic_decode_gray beside the two calls it replaces (bic_decode_planes into the
+    # caller's planes, then bic_planes_to_gray), alternating in this process; every result against the image
+    img = gray[:rows * cols].view(rows, cols)
+    _, (qg, qbg, qfg), (qe, qbe, qfe) = ctx.encode_gray_packed(img, planes=pl8, row_index=idx)
+    ctx.sync()
+    q00 = (img[0, 0] >> torch.arange(8, device=ctx.dev)).to(torch.uint8) & 1
+    g1 = torch.empty(rows, cols, dtype=torch.uint8, device=ctx.dev)
+    for name, coder, so, sb, sf, ri_ in (("golomb", 0, qg, qbg, qfg, idx), ("eg", 1, qe, qbe, qfe, None)):
+        sbytes = int(pybic.as_u64(sf)[-1]) * 8 + (n * rows * 16 if coder == 0 else 0)
+
+        def two():
+            ctx.decode_planes(coder, so, sb, n, rows, cols, True, word_off=sf, row_index=ri_, p00=q00, out=back)
+            ctx.planes_to_gray(back, cols, out=g8)
+
+        def one():
+            ctx.decode_gray(coder, so, sb, n, rows, cols, True, word_off=sf, row_index=ri_, p00=q00, out=g1)
+        g8.zero_()
+        g1.zero_()
+        two()
+        one()
+        ctx.sync()
+        out[f"decode_planes_to_gray_{name}_ok"] = bool(torch.equal(g8, img))
+        out[f"decode_gray_{name}_ok"] = bool(torch.equal(g1, img))
+        reps1, reps2 = [], []
+        for _ in range(args.alternations):
+            # D written and read back (the two calls: D and P written, D and P read) + the image
+            timed(f"decode_planes_to_gray_{name}", two, sbytes + 4 * plane_bytes + rows * cols)
+            timed(f"decode_gray_{name}", one, sbytes + 2 * plane_bytes + rows * cols)
+            reps2.append(out[f"decode_planes_to_gray_{name}"]["us"])
+            reps1.append(out[f"decode_gray_{name}"]["us"])
+        for key, r in ((f"decode_planes_to_gray_{name}", reps2), (f"decode_gray_{name}", reps1)):
+            out[key]["repeats_us"] = r
+            out[key]["us"] = sorted(r)[len(r) // 2]
+            out[key]["GB_s"] = round(out[key]["algorithmic_bytes"] / out[key]["us"] / 1e3, 1)
+        out[f"decode_gray_{name}_faster_every_repeat"] = all(a < b for a, b in zip(reps1, reps2))
     ctx.sync()
     print(json.dumps(out))
 
