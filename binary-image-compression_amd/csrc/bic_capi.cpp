@@ -628,6 +628,18 @@ int encode_planes_impl(bic_ctx* ctx, const uint64_t* planes, const Shape& sh, in
   return BIC_OK;
 }
 
+// The context's residual buffer (bic_encode_gray*, bic_encode_pbm* without planes), grown to `need` bytes
+int ensure_rbuf(bic_ctx* ctx, size_t need) {
+  if (ctx->rbuf_bytes >= need) return BIC_OK;
+  BIC_HIP(hipStreamSynchronize(ctx->cur));  // earlier calls may still use the old buffer
+  if (ctx->rbuf) (void)hipFree(ctx->rbuf);
+  ctx->rbuf = nullptr;
+  ctx->rbuf_bytes = 0;
+  if (hipMalloc(&ctx->rbuf, need) != hipSuccess) return BIC_ENOMEM;
+  ctx->rbuf_bytes = need;
+  return BIC_OK;
+}
+
 // Only the count pass (and the fallback's plane extraction) knows the sample size; everything after
 // it is per (plane, row).
 int encode_gray_impl(bic_ctx* ctx, const GrayImage& img, int plane0, uint64_t* planes, const Shape& sh, int predict,
@@ -653,15 +665,7 @@ int encode_gray_impl(bic_ctx* ctx, const GrayImage& img, int plane0, uint64_t* p
     // no bitplanes wanted: the count pass stores the med residual planes into the context's buffer
     // (the same bytes the bitplanes would take) and the encoder reads them with prediction off --
     // no row above, no med in the emission. Same streams (predict off on R = med on P).
-    const size_t need = (size_t)nplanes * rows * wpr * 8;
-    if (ctx->rbuf_bytes < need) {
-      BIC_HIP(hipStreamSynchronize(ctx->cur));
-      if (ctx->rbuf) (void)hipFree(ctx->rbuf);
-      ctx->rbuf = nullptr;
-      ctx->rbuf_bytes = 0;
-      if (hipMalloc(&ctx->rbuf, need) != hipSuccess) return BIC_ENOMEM;
-      ctx->rbuf_bytes = need;
-    }
+    if ((rc = ensure_rbuf(ctx, (size_t)nplanes * rows * wpr * 8))) return rc;
   }
   const bool store_resid = !planes && predict;
   if (!planes && !eg_src) planes = ctx->rbuf;
@@ -687,8 +691,64 @@ int encode_gray_impl(bic_ctx* ctx, const GrayImage& img, int plane0, uint64_t* p
   if (row_index && !og.out) return bic_row_index(ctx, planes, nplanes, rows, cols, wpr, pr, row_index);
   return BIC_OK;
 }
+
+// nframes P4 rasters (frame f at raster + f * stride) as the planes of one encode. Only the count pass
+// (and the fallback's unpacking) knows the source; everything after it is per (plane, row).
+int encode_pbm_impl(bic_ctx* ctx, const uint8_t* raster, size_t stride, uint64_t* planes, const Shape& sh, int predict,
+                    const bic::CoderOut& og, const bic::CoderOut& oe, uint64_t* row_index = nullptr) {
+  const int nframes = sh.nplanes;
+  const size_t rows = sh.rows, cols = sh.cols, wpr = sh.wpr;
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (nframes < 1 || !geom_ok(rows, cols, wpr) || !outs_ok(og, oe) || (rows && !raster)) return BIC_EINVAL;
+  const size_t frame_bytes = rows * ((cols + 7) / 8);
+  if (nframes == 1) stride = frame_bytes;
+  else if (stride < frame_bytes) return BIC_EINVAL;
+  if (rows == 0) return encode_planes_impl(ctx, planes, sh, predict, og, oe, row_index);  // zero counts and offsets
+  const bic::Geom g = bic::make_geom(rows, cols, wpr, nframes);
+  // no planes wanted: the context's buffer takes the count pass's residual planes (or the fallback's planes)
+  if (!planes && (rc = ensure_rbuf(ctx, (size_t)nframes * rows * wpr * 8))) return rc;
+  const bool store_resid = !planes && predict;
+  if (!planes) planes = ctx->rbuf;
+  const bool fuse = bic::fused_supported(g) && !ctx->force_multipass && !ctx->two_pass && !ctx->single_kernel &&
+                    staged_pays(ctx, g) && bic::med_rows_supported(g, planes, nullptr);
+  if (!fuse) {  // the same result through the separate calls
+    for (int f = 0; f < nframes; ++f)
+      if ((rc = bic_pbm_unpack(ctx, raster + (size_t)f * stride, rows, cols, planes + (size_t)f * rows * wpr, wpr)))
+        return rc;
+    return encode_planes_impl(ctx, planes, sh, predict, og, oe, row_index);
+  }
+  const int pr = predict && !store_resid ? 1 : 0;  // R stored: the encoder codes it as given
+  bic::FusedCall c{g, planes, pr, bic::kEncStaged, {og, oe, og.out ? row_index : nullptr}};
+  c.rq.counted = true;
+  c.rq.ns = 1;
+  if ((rc = run_fused(ctx, c, [&](const bic::FusedArena& ar) {
+         bic::launch_pbm_rows(ctx->cur, raster, stride, g, predict ? 1 : 0, planes, store_resid, ar.sones, ar.krec,
+                              ar.kpos, ar.counter);
+       })))
+    return rc;
+  if (row_index && !og.out) return bic_row_index(ctx, planes, nframes, rows, cols, wpr, pr, row_index);
+  return BIC_OK;
+}
 }  // namespace
 }  // extern "C++"
+
+int bic_encode_pbm(bic_ctx* ctx, const uint8_t* raster, size_t frame_stride, int nframes, size_t rows, size_t cols,
+                   uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
+                   uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg) {
+  return encode_pbm_impl(ctx, raster, frame_stride, planes, {nframes, rows, cols, wpr}, predict,
+                         {out_golomb, slot_golomb, bits_golomb}, {out_eg, slot_eg, bits_eg});
+}
+
+int bic_encode_pbm_packed(bic_ctx* ctx, const uint8_t* raster, size_t frame_stride, int nframes, size_t rows,
+                          size_t cols, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
+                          size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
+                          size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
+  if ((out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
+  return encode_pbm_impl(ctx, raster, frame_stride, planes, {nframes, rows, cols, wpr}, predict,
+                         {out_golomb, slot_golomb, bits_golomb, off_golomb}, {out_eg, slot_eg, bits_eg, off_eg},
+                         row_index);
+}
 
 int bic_encode_planes2(bic_ctx* ctx, const uint64_t* planes, int nplanes, size_t rows, size_t cols,
                        size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
@@ -813,6 +873,32 @@ int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slo
     bic::launch_decode(ctx->cur, coder == BIC_CODER_GOLOMB ? 0 : coder == BIC_CODER_EG ? 1 : 2, streams, slot_words,
                        word_off, plane_bits, index, p00, (uint32_t)rows, (uint32_t)cols, (uint32_t)wpr, (uint32_t)nplanes,
                        predict ? 1 : 0, nullptr, ctx->scratch, ctx->flags, ctx->lut + bic::kLutEgadDec, &go);
+  });
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
+int bic_decode_pbm(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                   const uint64_t* plane_bits, const uint64_t* index, int nframes, size_t rows, size_t cols, int predict,
+                   const uint8_t* p00, uint8_t* raster, size_t frame_stride) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (coder != BIC_CODER_GOLOMB && coder != BIC_CODER_EG && coder != BIC_CODER_EG_ADAPTIVE) return BIC_EINVAL;
+  const size_t wpr = (cols + 63) / 64;
+  if (nframes < 1 || !geom_ok(rows, cols, wpr) || !bic::decode_supported((uint32_t)cols)) return BIC_EINVAL;
+  const size_t frame_bytes = rows * ((cols + 7) / 8);
+  if (nframes == 1) frame_stride = frame_bytes;
+  else if (frame_stride < frame_bytes) return BIC_EINVAL;
+  if (rows == 0) return BIC_OK;
+  if (!streams || !plane_bits || !raster || (slot_words == 0 && !word_off)) return BIC_EINVAL;
+  if ((coder == BIC_CODER_GOLOMB || coder == BIC_CODER_EG_ADAPTIVE) && !index) return BIC_EINVAL;
+  if ((rc = ensure_scratch(ctx, bic::decode_gray_scratch_bytes((uint32_t)rows, (uint32_t)wpr, (uint32_t)nframes))))
+    return rc;
+  const bic::PbmOut po{raster, (uint64_t)frame_stride};
+  timed(ctx, "decode_pbm", [&] {
+    bic::launch_decode(ctx->cur, coder == BIC_CODER_GOLOMB ? 0 : coder == BIC_CODER_EG ? 1 : 2, streams, slot_words,
+                       word_off, plane_bits, index, p00, (uint32_t)rows, (uint32_t)cols, (uint32_t)wpr, (uint32_t)nframes,
+                       predict ? 1 : 0, nullptr, ctx->scratch, ctx->flags, ctx->lut + bic::kLutEgadDec, nullptr, &po);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;

@@ -658,6 +658,9 @@ __global__ __launch_bounds__(256) void k_dec_golomb_nib(DecArgs a) {
   // one stepped-path step: a table step when this lane can take one, else 8 general steps
   auto careful_step = [&](uint32_t byte) {
     if (ph <= kPhU1 && n > 0 && x + 2 * (int)kStepBits <= (int)n && j + 2 * kStepBits <= cols) {
+      // (the general machine finishes words only at a 1: after it, a zero run may have carried j past
+      // words still open, and the table steps place their columns in word j >> 6)
+      while ((j >> 6) > ow) finish_word();
       const uint32_t e = tab_at(ph * kNibXN, x, byte);
       const uint32_t l = e & 31u;
       const uint64_t obw = (uint64_t)(e & 0xffff0000u) << 32;
@@ -719,6 +722,7 @@ __global__ __launch_bounds__(256) void k_dec_golomb_nib(DecArgs a) {
       // void.
       const bool ends = !__all(stop == (uint32_t)kBlkSteps);
       uint32_t phk = ph * kNibXN;
+      while (live && (j >> 6) > ow) finish_word();  // (as in careful_step: words a zero run left open)
       dbase = ow;
       auto group = [&](uint32_t half, uint64_t& Dg, uint32_t g) {
         uint64_t Q = 0;
@@ -1088,6 +1092,60 @@ void launch_col_apply_gray(hipStream_t s, const uint64_t* D, const uint64_t* cto
 #undef BIC_CAG
 }
 
+// k_col_apply with a P4 sink (bic_decode_pbm: k_col_apply and k_pbm_pack2 in one pass): a thread sums
+// word column w of one chunk of one plane down its rows (started from the chunk's total, SCAN; without
+// prediction the D buffer holds the planes themselves) and stores bswap64 of each summed word as the
+// row's raster bytes 8w .. 8w + 7 of frame `plane` (pbm.cpp:63-77; pad bits 0). Rows share aligned
+// words whenever nb % 8 != 0 or the raster is misaligned, so no store covers a byte outside its own
+// row's nb bytes: one 8-byte store where the row holds all 8 bytes at an aligned address, byte stores
+// otherwise. The loads of kPbmRows rows are issued before the first is used (rows past the chunk's end
+// read its last row).
+constexpr int kPbmRows = 8;
+template <bool SCAN>
+__global__ __launch_bounds__(256) void k_col_apply_pbm(const uint64_t* __restrict__ D, const uint64_t* __restrict__ ctot,
+                                                       uint32_t rows, uint32_t cols, uint32_t wpr, uint32_t nplanes,
+                                                       uint8_t* __restrict__ raster, uint64_t stride) {
+  const uint32_t nch = (rows + kColChunk - 1) / kColChunk, used = (cols + 63) / 64, nb = (cols + 7) / 8;
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (uint64_t)nplanes * nch * used) return;
+  const uint32_t w = (uint32_t)(t % used);
+  const uint64_t pc = t / used;
+  const uint32_t c = (uint32_t)(pc % nch), plane = (uint32_t)(pc / nch);
+  const uint32_t r0 = c * kColChunk, nr = min(kColChunk, rows - r0);
+  const uint64_t* p = D + ((uint64_t)plane * rows + r0) * wpr + w;
+  const uint64_t trail = (w == used - 1 && (cols & 63)) ? ~(~0ull >> (cols & 63)) : ~0ull;
+  const uint32_t nbytes = min(8u, nb - 8 * w);  // the row's bytes in this word
+  uint8_t* dst = raster + (uint64_t)plane * stride + (uint64_t)r0 * nb + 8ull * w;
+  uint64_t acc = SCAN ? ctot[((uint64_t)plane * nch + c) * wpr + w] : 0ull;
+  for (uint32_t rb = 0; rb < nr; rb += kPbmRows) {
+    uint64_t d[kPbmRows];
+#pragma unroll
+    for (int k = 0; k < kPbmRows; ++k) d[k] = p[(uint64_t)min(rb + k, nr - 1) * wpr];
+#pragma unroll
+    for (int k = 0; k < kPbmRows; ++k) {
+      if (rb + k >= nr) break;
+      acc = SCAN ? acc ^ d[k] : d[k];
+      const uint64_t v = bswap64(acc & trail);  // byte 0 = the word's MSB
+      uint8_t* q = dst + (uint64_t)(rb + k) * nb;
+      if (nbytes == 8 && (reinterpret_cast<uintptr_t>(q) & 7) == 0) {
+        *reinterpret_cast<uint64_t*>(q) = v;
+      } else {
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+          if ((uint32_t)b < nbytes) q[b] = (uint8_t)(v >> (8 * b));
+      }
+    }
+  }
+}
+
+void launch_col_apply_pbm(hipStream_t s, const uint64_t* D, const uint64_t* ctot, uint32_t rows, uint32_t cols,
+                          uint32_t wpr, uint32_t nplanes, const PbmOut& po) {
+  const uint64_t nt = (uint64_t)nplanes * ((rows + kColChunk - 1) / kColChunk) * ((cols + 63) / 64);
+  const uint32_t grid = (uint32_t)((nt + 255) / 256);
+  if (ctot) k_col_apply_pbm<true><<<grid, 256, 0, s>>>(D, ctot, rows, cols, wpr, nplanes, po.raster, po.stride);
+  else k_col_apply_pbm<false><<<grid, 256, 0, s>>>(D, ctot, rows, cols, wpr, nplanes, po.raster, po.stride);
+}
+
 bool decode_supported(uint32_t cols) { return cols >= 1 && (cols + 63) / 64 <= kDecRowWords; }
 
 size_t decode_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes) {
@@ -1106,9 +1164,10 @@ size_t decode_gray_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes) 
 void launch_decode(hipStream_t s, int coder, const uint64_t* streams, uint64_t slot, const uint64_t* word_off,
                    const uint64_t* plane_bits, const uint64_t* index, const uint8_t* p00, uint32_t rows,
                    uint32_t cols, uint32_t wpr, uint32_t nplanes, int predict, uint64_t* out, void* scratch,
-                   uint32_t* flags, const uint64_t* egnib, const GrayOut* go) {
-  // to gray samples: the row kernels' output goes to the arena's D buffer instead of the caller's planes
-  if (go) out = reinterpret_cast<uint64_t*>(static_cast<char*>(scratch) + decode_gray_dbuf_offset(rows, wpr, nplanes));
+                   uint32_t* flags, const uint64_t* egnib, const GrayOut* go, const PbmOut* po) {
+  // to gray samples or P4 rasters: the row kernels' output goes to the arena's D buffer instead of the
+  // caller's planes
+  if (go || po) out = reinterpret_cast<uint64_t*>(static_cast<char*>(scratch) + decode_gray_dbuf_offset(rows, wpr, nplanes));
   DecArgs a;
   a.egnib = egnib;
   a.rows = rows;
@@ -1151,9 +1210,10 @@ void launch_decode(hipStream_t s, int coder, const uint64_t* streams, uint64_t s
     const uint64_t nt = (uint64_t)nplanes * nch * wpr;
     if (!fused_chunks) k_col_chunks<<<(uint32_t)((nt + 255) / 256), 256, 0, s>>>(out, ctot, rows, wpr, nplanes);
     k_col_scan_par<<<nplanes * wpr, 256, 0, s>>>(ctot, rows, wpr);
-    if (!go) k_col_apply<<<(uint32_t)((nt + 255) / 256), 256, 0, s>>>(out, ctot, rows, wpr, nplanes);
+    if (!go && !po) k_col_apply<<<(uint32_t)((nt + 255) / 256), 256, 0, s>>>(out, ctot, rows, wpr, nplanes);
   }
   if (go) launch_col_apply_gray(s, out, predict ? ctot : nullptr, rows, cols, wpr, nplanes, *go);
+  if (po) launch_col_apply_pbm(s, out, predict ? ctot : nullptr, rows, cols, wpr, nplanes, *po);
 }
 
 }  // namespace bic

@@ -75,13 +75,19 @@ struct GrayOut {
   int plane0, bps, big_endian;
 };
 size_t decode_gray_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes);
+// bic_decode_pbm: the P4 rasters the decoded planes go to (plane f = frame f at raster + f * stride;
+// the arena as for GrayOut)
+struct PbmOut {
+  uint8_t* raster;
+  uint64_t stride;
+};
 // egnib: egad_build_dec_nib's table in device memory (the context's byte-table buffer, kLutEgadDec).
-// go null: streams -> planes in `out`; otherwise streams -> gray samples (`out` unused, the scratch
-// sized by decode_gray_scratch_bytes)
+// go and po null: streams -> planes in `out`; go: streams -> gray samples, po: streams -> P4 rasters
+// (`out` unused, the scratch sized by decode_gray_scratch_bytes)
 void launch_decode(hipStream_t s, int coder, const uint64_t* streams, uint64_t slot, const uint64_t* word_off,
                    const uint64_t* plane_bits, const uint64_t* index, const uint8_t* p00, uint32_t rows,
                    uint32_t cols, uint32_t wpr, uint32_t nplanes, int predict, uint64_t* out, void* scratch,
-                   uint32_t* flags, const uint64_t* egnib, const GrayOut* go = nullptr);
+                   uint32_t* flags, const uint64_t* egnib, const GrayOut* go = nullptr, const PbmOut* po = nullptr);
 // the adaptive EG decoder's nibble table (62 states x 16 nibbles, u64), built on the host
 void egad_build_dec_nib(uint64_t* T);
 void launch_med_rows(hipStream_t s, const Geom& g, const uint64_t* planes, int predict, uint64_t* resid,
@@ -234,6 +240,11 @@ void launch_fused_finish(hipStream_t s, const FusedCall& c);
 constexpr uint32_t kZeroWords = 64;
 void launch_row_ones(hipStream_t s, const Geom& g, const uint64_t* planes, int predict, uint32_t* sones,
                      int4* krec, uint32_t* kpos, uint32_t* zero);
+// P4 rasters -> planes + the count pass in one read (bic_encode_pbm): frame f (g.rows x ceil(cols/8) bytes at
+// raster + f * stride, any alignment) is plane f; one record per row (ns = 1). dst (med_rows_supported)
+// receives the planes, or with store_resid and predict their med residual
+void launch_pbm_rows(hipStream_t s, const uint8_t* raster, uint64_t stride, const Geom& g, int predict, uint64_t* dst,
+                     bool store_resid, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero);
 // bitplanes + the count pass in one read of the gray image (bic_encode_gray); gray_strips(g)
 // k statistics records per row (one per 64-word strip)
 bool gray_rows_supported(const Geom& g, const void* gray, size_t pitch, const void* planes, int bps = 1);

@@ -452,6 +452,108 @@ void launch_row_ones(hipStream_t s, const Geom& g, const uint64_t* planes, int p
 #undef BIC_KST
 }
 
+// From P4 rasters (bic_encode_pbm: pbm.cpp:29-77's unpacking and the count pass in one read): frame f's
+// raster is g.rows x nb bytes (nb = ceil(cols / 8)) at raster + f * stride, any byte alignment, and is
+// plane f. k_med_kstat's walk -- RPW rows of one frame per wave, lane l owning words LW*l .. LW*l + LW - 1
+// (LW >= 2: a lane's words are whole 16-byte pairs of the even-pitched output), the row above in
+// registers, the next row's loads in flight -- with plane word w of a row = bswap64 of the row's bytes
+// 8w .. 8w + 7: the aligned 8-byte chunks that hold them, shifted by the row's misalignment (the same
+// for every lane of the wave: 8 w keeps it). A chunk is loaded only if it holds a byte of the frame's
+// raster (never one past its last byte's chunk: no read past the buffer's last page); the bytes after a
+// row's last one (the next row's, or another frame's) and the pad bits fall to g.trail. Writes the
+// row's record and its words: the plane P, or with store_r the med residual R (the encoder then codes
+// it with prediction off); words used .. wpr - 1 are written 0.
+template <int LW, int RPW, bool PREDICT>
+__global__ __launch_bounds__(kBlock) void k_pbm_kstat(Geom g, const uint8_t* __restrict__ raster, uint64_t stride,
+                                                      uint64_t* __restrict__ dst, int store_r,
+                                                      uint32_t* __restrict__ sones, int4* __restrict__ krec,
+                                                      uint32_t* __restrict__ kpos, uint32_t* __restrict__ zero) {
+  static_assert(LW % 2 == 0, "a lane stores 16-byte word pairs");
+  if (blockIdx.x == 0 && threadIdx.x < kZeroWords) zero[threadIdx.x] = 0;  // the encoder's counters
+  const int lane = lane_id();
+  const uint32_t wpp = (g.rows + RPW - 1) / RPW;  // waves per frame
+  const uint64_t gw = (uint64_t)xcd_remap(blockIdx.x, gridDim.x) * kWaves + wave_id();
+  if (gw >= (uint64_t)wpp * g.nplanes) return;  // whole wave
+  const uint32_t plane = (uint32_t)(gw / wpp), r0 = (uint32_t)(gw % wpp) * RPW;
+  const uint32_t nb = (g.cols + 7) / 8;
+  const uint8_t* fp = raster + (uint64_t)plane * stride;  // the frame's first byte
+  const uint64_t fb = reinterpret_cast<uint64_t>(fp);
+  const uint64_t lastc = (fb + (uint64_t)g.rows * nb - 1) & ~7ull;                    // the chunk of its last byte
+  const uint32_t w0 = LW * lane;
+  auto load = [&](uint32_t row, uint64_t (&v)[LW]) {
+    const uint64_t a = fb + (uint64_t)row * nb + 8ull * w0;  // word w0's first byte (in the frame when w0 < used)
+    const uint32_t sh = 8 * (uint32_t)__builtin_amdgcn_readfirstlane((int)((fb + (uint64_t)row * nb) & 7));
+    const uint64_t ca = a & ~7ull;
+    uint64_t c[LW + 1];
+#pragma unroll
+    for (int j = 0; j <= LW; ++j) {
+      // chunk j holds bytes of word w0 + j and (misaligned rows) of word w0 + j - 1
+      const bool need = w0 + (j ? j - 1 : 0) < g.used && (j < LW || sh) && ca + 8 * j <= lastc;
+      // (pointer arithmetic from the kernel argument: stays a global load)
+      c[j] = need ? *reinterpret_cast<const uint64_t*>(fp + (int64_t)(ca + 8 * j - fb)) : 0ull;
+    }
+#pragma unroll
+    for (int i = 0; i < LW; ++i) {
+      const uint32_t w = w0 + i;
+      const uint64_t x = bswap64(sh ? (c[i] >> sh) | (c[i + 1] << (64 - sh)) : c[i]);  // byte 0 = MSB
+      v[i] = w < g.used ? (w == g.used - 1 ? x & g.trail : x) : 0;
+    }
+  };
+  uint64_t up[LW], cur[LW];
+#pragma unroll
+  for (int i = 0; i < LW; ++i) up[i] = 0;
+  if (PREDICT && r0) load(r0 - 1, up);
+  load(r0, cur);
+  const uint32_t nr = min((uint32_t)RPW, g.rows - r0);
+  uint64_t* out = dst + (uint64_t)plane * g.plane_words;
+  for (uint32_t r = 0; r < nr; ++r) {
+    const uint32_t row = r0 + r;
+    uint64_t nxt[LW];
+    if (r + 1 < nr) load(row + 1, nxt);
+    LaneK k;
+    uint64_t D[LW], R[LW];
+#pragma unroll
+    for (int i = 0; i < LW; ++i) D[i] = PREDICT ? cur[i] ^ up[i] : cur[i];
+    const uint64_t dl = wave_shr1_u64(D[LW - 1]);  // word LW*l - 1 (lane l - 1's last; lane 0: 0)
+#pragma unroll
+    for (int i = 0; i < LW; ++i) {
+      const uint32_t w = w0 + i;
+      R[i] = D[i];
+      if constexpr (PREDICT) {
+        R[i] = D[i] ^ ((D[i] >> 1) | ((i ? D[i - 1] : dl) << 63));
+        if (row == 0 && w == 0) R[i] &= ~BIC_MSB;  // pred.cpp never writes pP(0,0)
+      }
+      R[i] = w < g.used ? (w == g.used - 1 ? R[i] & g.trail : R[i]) : 0;
+      lanek_word(k, R[i], (int32_t)(w * 64));
+      up[i] = cur[i];
+    }
+    const uint64_t id = (uint64_t)plane * g.rows + row;
+    lanek_store(k, krec + id, kpos + id, sones + id);
+    uint64_t* orow = out + (uint64_t)row * g.wpr;
+#pragma unroll
+    for (int i = 0; i < LW; i += 2)  // (wpr is even: a pair below wpr lies inside the row pitch)
+      if (w0 + i < g.wpr)
+        *reinterpret_cast<ulonglong2*>(orow + w0 + i) =
+            store_r ? make_ulonglong2(R[i], R[i + 1]) : make_ulonglong2(cur[i], cur[i + 1]);
+    for (uint32_t w = 64 * LW + 2 * lane; w < g.wpr; w += 128)  // a pitch wider than the lanes' words
+      *reinterpret_cast<ulonglong2*>(orow + w) = make_ulonglong2(0, 0);
+#pragma unroll
+    for (int i = 0; i < LW; ++i) cur[i] = nxt[i];
+  }
+}
+
+void launch_pbm_rows(hipStream_t s, const uint8_t* raster, uint64_t stride, const Geom& g, int predict, uint64_t* dst,
+                     bool store_resid, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero) {
+  constexpr int RPW = 8;
+  const uint32_t wpp = (g.rows + RPW - 1) / RPW;
+  const uint32_t grid = (uint32_t)(((uint64_t)wpp * g.nplanes + kWaves - 1) / kWaves);
+  const int sr = store_resid && predict ? 1 : 0;
+#define BIC_PKS(LW, P) k_pbm_kstat<LW, RPW, P><<<grid, kBlock, 0, s>>>(g, raster, stride, dst, sr, sones, krec, kpos, zero)
+  if (g.used <= 128) { if (predict) BIC_PKS(2, true); else BIC_PKS(2, false); }
+  else { if (predict) BIC_PKS(4, true); else BIC_PKS(4, false); }
+#undef BIC_PKS
+}
+
 // From the gray image (bic_encode_gray: bitplane_tool.cpp:24-30 and the count pass in one read):
 // one wave per strip of 64 plane words (4096 columns) and gray_rows_per_wave() rows; lane l owns word
 // 64 s + l of strip s: four 16-byte loads give its 64 pixels (load64_mis when the rows are not

@@ -31,6 +31,7 @@ EXPORTS = [
     "bic_row_index", "bic_decode_planes", "bic_pgm_bitplanes", "bic_pnm_parse_header",
     "bic_gf2_transpose", "bic_gf2_mul", "bic_planes_to_gray", "bic_match_encode_inv", "bic_match_encode_var", "bic_egad_row_index",
     "bic_encode_gray16", "bic_encode_gray16_packed", "bic_bitplanes_u16", "bic_decode_gray",
+    "bic_encode_pbm", "bic_encode_pbm_packed", "bic_decode_pbm",
 ]
 
 # bic_gf2_mul ops (include/bic.h)
@@ -126,6 +127,9 @@ def load(path=LIB_PATH):
     sig("bic_encode_gray16_packed", i32, [vp, vp, sz, sz, sz, i32, i32, i32, vp, sz, i32, vp, sz, vp, vp, vp, sz, vp,
                                           vp, vp])
     sig("bic_decode_gray", i32, [vp, i32, vp, sz, vp, vp, vp, i32, i32, sz, sz, i32, vp, i32, i32, vp, sz])
+    sig("bic_encode_pbm", i32, [vp, vp, sz, i32, sz, sz, vp, sz, i32, vp, sz, vp, vp, sz, vp])
+    sig("bic_encode_pbm_packed", i32, [vp, vp, sz, i32, sz, sz, vp, sz, i32, vp, sz, vp, vp, vp, sz, vp, vp, vp])
+    sig("bic_decode_pbm", i32, [vp, i32, vp, sz, vp, vp, vp, i32, sz, sz, i32, vp, vp, sz])
     _lib = L
     return L
 
@@ -460,6 +464,67 @@ class Context:
         self._chk(self.lib.bic_decode_gray(self.h, coder, _p(streams), slot, _p(word_off), _p(plane_bits),
                                            _p(row_index), plane0, nplanes, rows, cols, int(predict), _p(p00),
                                            sample_bytes, int(big_endian), _p(out), pitch), "bic_decode_gray")
+        return out
+
+    def _pbm_args(self, rows, cols, nframes, frame_stride, planes, wpr):
+        """frame_stride (default: the frame's bytes), planes (None: NULL; True: allocated here; or an int64
+        tensor [nframes, rows, wpr]) and wpr (default ceil(cols / 64); the one-read count pass needs it even)"""
+        stride = rows * ((cols + 7) // 8) if frame_stride is None else frame_stride
+        wpr = wpr or (cols + 63) // 64
+        if planes is True:
+            planes = self.empty_i64(nframes, rows, wpr)
+        wpr = planes.shape[-1] if planes is not None else wpr
+        return stride, planes, wpr
+
+    def encode_pbm(self, raster, rows, cols, nframes=1, frame_stride=None, predict=True, planes=None, golomb=True,
+                   eg=True, slots=(None, None), outs=(None, None), bits=(None, None), wpr=None):
+        """bic_encode_pbm: raster = a uint8 device tensor whose first byte is frame 0's first raster byte (any
+        alignment, e.g. a P4 file's bytes [data_offset:]), frame f frame_stride bytes further ->
+        (planes, (out_g, bits_g) or None, (out_e, bits_e) or None). planes: see _pbm_args (None: not
+        returned, the count pass keeps the residual planes in the context)."""
+        stride, planes, wpr = self._pbm_args(rows, cols, nframes, frame_stride, planes, wpr)
+        res = []
+        for on, coder, slot, out, b in ((golomb, CODER_GOLOMB, slots[0], outs[0], bits[0]),
+                                        (eg, CODER_EG, slots[1], outs[1], bits[1])):
+            if not on:
+                res.append((None, 0, None))
+                continue
+            slot = slot or self.slot_words(rows, cols, coder)
+            out = self.empty_i64(nframes, slot) if out is None else out
+            b = self.empty_i64(nframes) if b is None else b
+            res.append((out, slot, b))
+        (og, sg, bg), (oe, se, be) = res
+        self._bind_stream()
+        self._chk(self.lib.bic_encode_pbm(self.h, _p(raster), stride, nframes, rows, cols, _p(planes), wpr, int(predict),
+                                          _p(og), sg, _p(bg), _p(oe), se, _p(be)), "bic_encode_pbm")
+        return planes, ((og, bg) if golomb else None), ((oe, be) if eg else None)
+
+    def encode_pbm_packed(self, raster, rows, cols, nframes=1, frame_stride=None, predict=True, planes=None,
+                          golomb=True, eg=True, slots=(None, None), outs=(None, None), bits=(None, None),
+                          offs=(None, None), row_index=None, wpr=None):
+        """bic_encode_pbm_packed -> (planes, (out_g, bits_g, off_g) or None, (out_e, bits_e, off_e) or None)"""
+        stride, planes, wpr = self._pbm_args(rows, cols, nframes, frame_stride, planes, wpr)
+        (og, sg, bg, fg), (oe, se, be, fe) = self._packed_bufs(nframes, rows, cols, golomb, eg, slots, outs, bits, offs)
+        self._bind_stream()
+        self._chk(self.lib.bic_encode_pbm_packed(self.h, _p(raster), stride, nframes, rows, cols, _p(planes), wpr,
+                                                 int(predict), _p(og), sg, _p(bg), _p(fg), _p(oe), se, _p(be), _p(fe),
+                                                 _p(row_index)), "bic_encode_pbm_packed")
+        return planes, ((og, bg, fg) if golomb else None), ((oe, be, fe) if eg else None)
+
+    def decode_pbm(self, coder, streams, plane_bits, nframes, rows, cols, predict=True, word_off=None,
+                   row_index=None, p00=None, out=None, frame_stride=None):
+        """bic_decode_pbm: streams (as for decode_planes) -> uint8 device tensor of P4 raster bytes, frame f at
+        byte f * frame_stride (default: the frame's bytes). out: a uint8 device tensor whose first byte is
+        frame 0's first (any alignment). p00: uint8 device tensor [nframes] (raster_f[0] >> 7) or None."""
+        stride = rows * ((cols + 7) // 8) if frame_stride is None else frame_stride
+        if out is None:
+            out = self.torch.zeros((nframes - 1) * stride + rows * ((cols + 7) // 8), dtype=self.torch.uint8,
+                                   device=self.dev)
+        slot = streams.shape[-1] if (word_off is None and streams.dim() == 2) else 0
+        self._bind_stream()
+        self._chk(self.lib.bic_decode_pbm(self.h, coder, _p(streams), slot, _p(word_off), _p(plane_bits),
+                                          _p(row_index), nframes, rows, cols, int(predict), _p(p00), _p(out), stride),
+                  "bic_decode_pbm")
         return out
 
     def _packed_bufs(self, n, rows, cols, golomb, eg, slots, outs, bits, offs):

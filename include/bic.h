@@ -201,6 +201,30 @@ int bic_encode_gray16_packed(bic_ctx* ctx, const void* gray, size_t pitch, size_
                              int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
                              size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
                              size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index);
+/* P4 rasters -> streams in one call: bic_pbm_unpack per frame followed by bic_encode_planes2 /
+ * bic_encode_planes_packed, bit-identical streams, bit counts, offsets and row index. Frame f's raster
+ * (pbm.cpp:29-77: rows x ceil(cols/8) bytes, MSB = leftmost pixel) lies at raster + f * frame_stride:
+ * device memory of any byte alignment, e.g. a buffer of concatenated P4 files + data_offset;
+ * frame_stride >= rows * ceil(cols/8) (ignored when nframes = 1). Frame f is plane f of every output:
+ * slots, bits_*, off_*, row_index and planes + f * rows * wpr. The pad bits of a row's last byte are
+ * ignored, whatever they hold. planes may be NULL; given, it receives the unpacked planes (pad bits 0).
+ * Arguments, nullable outputs, BIC_ENOSPC, the domain and rows = 0 as for bic_encode_gray_packed.
+ * With the staged encoder (>= 32768 rows in all frames, or BIC_OPT_STAGED), cols <= 16384, an even wpr
+ * and 16-byte aligned planes, one count kernel reads every raster byte once and writes the encoder's
+ * per-row records together with the planes or, with planes NULL, their med residual into the context's
+ * residual buffer (nframes * rows * wpr words; it grows to the largest call and lives until
+ * bic_ctx_destroy), which the emission codes with prediction off. Otherwise the same result through
+ * the separate calls (with planes NULL, unpacked into that buffer).
+ * Reads of a raster round out to the enclosing aligned 8-byte chunks (never a chunk without one of the
+ * frame's raster bytes, so never past the last page of the buffer, but up to 7 bytes before a frame's
+ * first byte and beyond its last). */
+int bic_encode_pbm(bic_ctx* ctx, const uint8_t* raster, size_t frame_stride, int nframes, size_t rows, size_t cols,
+                   uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
+                   uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg);
+int bic_encode_pbm_packed(bic_ctx* ctx, const uint8_t* raster, size_t frame_stride, int nframes, size_t rows,
+                          size_t cols, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
+                          size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
+                          size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index);
 
 /* ---- f1: decoders on the device (GolombDecoder.cpp:15-23 read order, eg.cpp:20-37 as written) --
  * row_index (device, nplanes * rows * 2 u64; nullable in the encoders above): per row of each plane,
@@ -246,6 +270,18 @@ int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slo
                     const uint64_t* word_off, const uint64_t* plane_bits, const uint64_t* row_index,
                     int plane0, int nplanes, size_t rows, size_t cols, int predict, const uint8_t* p00,
                     int sample_bytes, int big_endian, void* gray, size_t pitch);
+/* streams -> P4 rasters in one call: bic_decode_planes followed by bic_pbm_pack per frame, without the
+ * planes. coder, streams, slot_words, word_off, plane_bits, row_index, predict, the limit cols <= 16384
+ * and BIC_EDATA from bic_sync (the rasters are then undefined) as for bic_decode_gray; stream f is frame
+ * f, written at raster + f * frame_stride (device, any byte alignment; frame_stride >= rows *
+ * ceil(cols/8), ignored when nframes = 1). Only the rows * ceil(cols/8) bytes of each frame are written;
+ * the pad bits of a row's last byte are written 0. p00 (device, one byte per frame; nullable: 0):
+ * p00[f] = raster_f[0] >> 7, the frame's first pixel. The row decoders write D into the scratch arena
+ * as for bic_decode_gray, and the last kernel forms each row's raster bytes as it sums D down the
+ * columns. rows = 0: BIC_OK, nothing written. */
+int bic_decode_pbm(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                   const uint64_t* plane_bits, const uint64_t* row_index, int nframes, size_t rows, size_t cols,
+                   int predict, const uint8_t* p00, uint8_t* raster, size_t frame_stride);
 /* A slot size (64-bit words) that every plane of this geometry fits for EG (exact) and for
  * Golomb on any input this build has seen (2*rows*(cols+1) bits + 64 words); a larger input
  * still reports BIC_ENOSPC rather than writing out of bounds. */
