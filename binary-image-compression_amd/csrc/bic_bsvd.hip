@@ -1,0 +1,376 @@
+// bic_bsvd.hip -- the two steps of the reference's binary dictionary learning on the device
+// (include/bic.h "binary dictionary learning"):
+//
+//  * bsvd.cpp:399-460 update_coefficients_basic (= :1029-1107 _omp, rows are independent): greedy
+//    sparse coding, per row of E the atom (row of D) at least Hamming distance, first in k among
+//    equals (:423-437, strict <), XORed in while it lowers the row's weight (:439-447);
+//  * bsvd.cpp:463-527 update_dictionary_steepest: atom by atom, in order, the per-column majority over
+//    the rows that use the atom (:486-506), the change carried into those rows of E (:512-520);
+//  * bsvd.cpp:1220 add(E, X, E) after mul(A, D, E): the word-wise XOR.
+//
+// Matrices are in the plane layout (bic.h): row-major u64 words, column j at bit 63 - j % 64 of word
+// j / 64. Distances, weights and XORs run over the mw = ceil(m / 64) whole words of a row, as dist,
+// weight and add do (binmat.cpp:57-67, 463-512); words past mw (the pitch) are never touched.
+#include "bic_device.h"
+
+#include <algorithm>
+
+namespace bic {
+
+// ------------------------------------------------------------------------------------------------
+// Sparse coding. One row per wave: lane w < mw holds word w of E_i, lane w < ceil(p / 64) word w of
+// A_i, and a copy of E_i sits in LDS where every lane reads it (same address: a broadcast). The atoms
+// are in LDS word-major (word w of atom k at tile[w * ta + k]), so the 64 lanes of a wave, one atom
+// each, read 64 consecutive words. A lane runs kBsvdJ atoms per E word it reads. The least key
+// (dist << 12) | k over the wave is the least distance and, among equals, the least k.
+//
+// D is resident (loaded once per workgroup, waves then run their rows without meeting) while
+// roundup64(p) * mw words fit in kBsvdTileWords; otherwise every round streams it through LDS in
+// tiles of ta atoms, the four rows of a workgroup in step, the running minimum carried across tiles.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t kBsvdTileWords = 7680;  // 60 KiB of atoms + 2 KiB of rows: two workgroups per CU
+constexpr int kBsvdJ = 4;
+
+__device__ __forceinline__ int bsvd_scan(const uint64_t* erow, const uint64_t* tile, uint32_t ta, uint32_t cnt,
+                                         uint32_t k0, uint32_t mw, int best) {
+  const uint32_t lane = lane_id();
+  for (uint32_t base = 0; base < cnt; base += 64 * kBsvdJ) {
+    uint32_t d[kBsvdJ];
+#pragma unroll
+    for (int j = 0; j < kBsvdJ; ++j) d[j] = 0;
+    for (uint32_t w = 0; w < mw; ++w) {
+      const uint64_t e = erow[w];
+      const uint64_t* col = tile + w * ta + base + lane;
+#pragma unroll
+      for (int j = 0; j < kBsvdJ; ++j)  // (wave-uniform guard; ta is a multiple of 64, so base + 64 j + lane < ta)
+        if (base + 64 * j < cnt) d[j] += (uint32_t)__popcll(e ^ col[64 * j]);
+    }
+#pragma unroll
+    for (int j = 0; j < kBsvdJ; ++j) {
+      const uint32_t k = base + 64 * j + lane;
+      if (k < cnt) best = min(best, (int)((d[j] << 12) | (k0 + k)));
+    }
+  }
+  return best;
+}
+
+__device__ __forceinline__ void bsvd_load_tile(uint64_t* tile, uint32_t ta, const uint64_t* D, uint32_t d_wpr,
+                                               uint32_t k0, uint32_t cnt, uint32_t mw) {
+  for (uint32_t idx = threadIdx.x; idx < cnt * mw; idx += blockDim.x) {
+    const uint32_t k = idx / mw, w = idx - k * mw;
+    tile[w * ta + k] = D[(uint64_t)(k0 + k) * d_wpr + w];
+  }
+}
+
+// the step of one row once the wave knows its best key: true if the atom was taken
+__device__ __forceinline__ bool bsvd_take(int best, uint64_t& ew, uint64_t& aw, uint64_t* erow, const uint64_t* D,
+                                          uint32_t d_wpr, uint32_t mw) {
+  const uint32_t lane = lane_id();
+  const uint32_t wgt = wave_total_u32((uint32_t)__popcll(ew));  // (lanes >= mw hold 0)
+  const uint32_t bestd = (uint32_t)best >> 12, bestk = (uint32_t)best & 4095u;
+  if (bestd >= wgt) return false;  // bsvd.cpp:439: only a strictly lower weight is a step
+  if (lane < mw) {
+    ew ^= D[(uint64_t)bestk * d_wpr + lane];
+    erow[lane] = ew;
+  }
+  if (lane == (bestk >> 6)) aw ^= BIC_MSB >> (bestk & 63u);  // Ai.flip(0, bestk): may switch an atom off
+  __builtin_amdgcn_wave_barrier();
+  return true;
+}
+
+template <bool RESIDENT>
+__global__ __launch_bounds__(256) void k_bsvd_coef(uint64_t* __restrict__ E, uint32_t n, uint32_t mw, uint32_t e_wpr,
+                                                   const uint64_t* __restrict__ D, uint32_t p, uint32_t d_wpr,
+                                                   uint64_t* __restrict__ A, uint32_t a_wpr, uint32_t ta,
+                                                   unsigned long long* changed) {
+  extern __shared__ __attribute__((aligned(16))) uint64_t bsvd_lds[];
+  const uint32_t lane = lane_id(), wave = wave_id();
+  uint64_t* erow = bsvd_lds + wave * 64;
+  uint64_t* tile = bsvd_lds + 4 * 64;
+  const uint32_t pw = (p + 63) / 64;
+  const uint32_t max_steps = 64 * mw;  // every step lowers the row's weight, which is at most 64 mw
+  uint32_t nchanged = 0;
+  if constexpr (RESIDENT) {
+    bsvd_load_tile(tile, ta, D, d_wpr, 0, p, mw);
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * 4 + wave; i < n; i += (uint64_t)gridDim.x * 4) {
+      uint64_t ew = lane < mw ? E[i * e_wpr + lane] : 0ull;
+      uint64_t aw = lane < pw ? A[i * a_wpr + lane] : 0ull;
+      if (lane < mw) erow[lane] = ew;
+      __builtin_amdgcn_wave_barrier();
+      bool ch = false;
+      for (uint32_t step = 0; step <= max_steps; ++step) {
+        const int best = wave_min(bsvd_scan(erow, tile, ta, p, 0, mw, INT_MAX));
+        if (!bsvd_take(best, ew, aw, erow, D, d_wpr, mw)) break;
+        ch = true;
+      }
+      if (ch) {
+        if (lane < mw) E[i * e_wpr + lane] = ew;
+        if (lane < pw) A[i * a_wpr + lane] = aw;
+        ++nchanged;
+      }
+    }
+  } else {
+    const uint32_t ngroups = (n + 3) / 4;
+    for (uint32_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+      const uint64_t i = (uint64_t)g * 4 + wave;
+      bool active = i < n;  // wave-uniform
+      uint64_t ew = (active && lane < mw) ? E[i * e_wpr + lane] : 0ull;
+      uint64_t aw = (active && lane < pw) ? A[i * a_wpr + lane] : 0ull;
+      if (lane < mw) erow[lane] = ew;
+      bool ch = false;
+      for (uint32_t step = 0; step <= max_steps; ++step) {
+        // (the barrier also separates the last tile's readers from the next round's first load)
+        if (!__syncthreads_or(active ? 1 : 0)) break;
+        int best = INT_MAX;
+        for (uint32_t k0 = 0; k0 < p; k0 += ta) {
+          const uint32_t cnt = min(ta, p - k0);
+          if (k0) __syncthreads();
+          bsvd_load_tile(tile, ta, D, d_wpr, k0, cnt, mw);
+          __syncthreads();
+          if (active) best = bsvd_scan(erow, tile, ta, cnt, k0, mw, best);
+        }
+        if (active) {
+          best = wave_min(best);
+          if (bsvd_take(best, ew, aw, erow, D, d_wpr, mw)) ch = true;
+          else active = false;
+        }
+      }
+      if (ch) {
+        if (lane < mw) E[i * e_wpr + lane] = ew;
+        if (lane < pw) A[i * a_wpr + lane] = aw;
+        ++nchanged;
+      }
+      __syncthreads();  // the next group's rows overwrite erow
+    }
+  }
+  if (lane == 0 && nchanged && changed) atomicAdd(changed, (unsigned long long)nchanged);
+}
+
+void launch_bsvd_coef(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* D,
+                      uint32_t p, uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, uint64_t* changed) {
+  const uint32_t mw = (m + 63) / 64, p64 = (p + 63) / 64 * 64;
+  const bool resident = (uint64_t)p64 * mw <= kBsvdTileWords;
+  const uint32_t ta = resident ? p64 : kBsvdTileWords / mw / 64 * 64;  // mw <= 64: at least 64 atoms
+  const size_t lds = (size_t)(4 * 64 + (size_t)ta * mw) * 8;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 3) / 4, 512);
+  if (!grid) return;
+  auto* ch = reinterpret_cast<unsigned long long*>(changed);
+  if (resident)
+    k_bsvd_coef<true><<<grid, 256, lds, s>>>(E, n, mw, e_wpr, D, p, d_wpr, A, a_wpr, ta, ch);
+  else
+    k_bsvd_coef<false><<<grid, 256, lds, s>>>(E, n, mw, e_wpr, D, p, d_wpr, A, a_wpr, ta, ch);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Dictionary update. At = the transpose of A: row k is the bit row of atom k's users. A workgroup
+// owns wpb words of it, i.e. 64 wpb rows of E, for the whole update; the thread (slot, w) walks the
+// users in the At words a0 + slot, a0 + slot + nslots, .. and touches word w of each. So a word of E
+// is read and written by one thread only, whatever the atom, and one launch can do both
+//
+//   * atom k - 1's change: E_i ^= delta (D_k-1 ^ its new value) for its users, and
+//   * atom k's column counts over E_i of its users, then in bit-sliced carry-save counters (five
+//     planes: 31 rows between two flushes into the workgroup's LDS counts), LDS counts to the global
+//     ones with atomicAdd.
+//
+// The workgroup that takes the last ticket of the launch turns the counts into the new atom: with
+// U users and c' the count of E's bit, the count of (E ^ D_k)'s bit is c' where D_k's bit is 0 and
+// U - c' where it is 1; the new bit is count > U / 2 (bsvd.cpp:502-506) for j < m, D_k's own bit
+// past m. It stores delta, D_k and the flag "delta != 0", counts the atom in *changed and leaves the
+// counts, U and the ticket zero for the next atom. Nothing waits on another workgroup: the launches
+// k = k_lo .. k_hi are ordered on the stream (one atom each), or, when one workgroup owns every row,
+// it walks all the atoms in one launch. k = p only applies atom p - 1's change.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint64_t ld_agent(const uint64_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+constexpr int kBsvdPlanes = 5;
+constexpr uint32_t kBsvdFlush = (1u << kBsvdPlanes) - 1;
+
+__device__ __forceinline__ void bsvd_flush(uint64_t (&pl)[kBsvdPlanes], uint32_t* lc) {
+  for (uint32_t b = 0; b < 64; ++b) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int q = 0; q < kBsvdPlanes; ++q) c |= (uint32_t)((pl[q] >> (63 - b)) & 1ull) << q;
+    if (c) atomicAdd(&lc[b], c);
+  }
+#pragma unroll
+  for (int q = 0; q < kBsvdPlanes; ++q) pl[q] = 0;
+}
+
+// misc: [0] U, [1] ticket, [2] delta != 0
+__global__ __launch_bounds__(256) void k_bsvd_dict(uint64_t* __restrict__ E, uint32_t m, uint32_t mw, uint32_t lg,
+                                                   uint32_t e_wpr, uint64_t* __restrict__ D, uint32_t p,
+                                                   uint32_t d_wpr, const uint64_t* __restrict__ At, uint32_t atw,
+                                                   uint32_t wpb, uint32_t k_lo, uint32_t k_hi, uint32_t* cnt,
+                                                   uint64_t* delta, uint32_t* misc, unsigned long long* changed) {
+  __shared__ uint32_t lcnt[64 * 64];
+  __shared__ uint32_t s_users, s_last, s_u, s_any;
+  const uint32_t t = threadIdx.x, lane = lane_id(), wave = wave_id();
+  const uint32_t w = t & ((1u << lg) - 1u), slot = t >> lg, nslots = 256u >> lg;
+  const uint32_t a0 = blockIdx.x * wpb, a1 = min(a0 + wpb, atw);
+  const bool mine = w < mw;
+  for (uint32_t k = k_lo; k <= k_hi; ++k) {
+    if (k > 0 && ld_agent(&misc[2])) {  // atom k - 1 changed: carry it into its users' rows
+      const uint64_t dl = mine ? ld_agent(&delta[w]) : 0ull;
+      const uint64_t* at = At + (uint64_t)(k - 1) * atw;
+      for (uint32_t a = a0 + slot; a < a1; a += nslots) {
+        uint64_t bits = at[a];
+        while (bits) {
+          const uint32_t b = (uint32_t)__builtin_clzll(bits);
+          bits &= ~(BIC_MSB >> b);
+          if (mine) E[((uint64_t)a * 64 + b) * e_wpr + w] ^= dl;
+        }
+      }
+    }
+    if (k >= p) break;
+    for (uint32_t j = t; j < mw * 64; j += 256) lcnt[j] = 0;
+    if (t == 0) s_users = 0;
+    __syncthreads();
+    {
+      const uint64_t* at = At + (uint64_t)k * atw;
+      uint64_t pl[kBsvdPlanes];
+#pragma unroll
+      for (int q = 0; q < kBsvdPlanes; ++q) pl[q] = 0;
+      uint32_t nacc = 0, users = 0;
+      for (uint32_t a = a0 + slot; a < a1; a += nslots) {
+        uint64_t bits = at[a];
+        if (w == 0) users += (uint32_t)__popcll(bits);
+        while (bits) {
+          const uint32_t b = (uint32_t)__builtin_clzll(bits);
+          bits &= ~(BIC_MSB >> b);
+          if (mine) {
+            uint64_t carry = E[((uint64_t)a * 64 + b) * e_wpr + w];
+#pragma unroll
+            for (int q = 0; q < kBsvdPlanes; ++q) {  // the vertical adder: plane q holds bit q of 64 counts
+              const uint64_t c2 = pl[q] & carry;
+              pl[q] ^= carry;
+              carry = c2;
+            }
+            if (++nacc == kBsvdFlush) {
+              bsvd_flush(pl, lcnt + w * 64);
+              nacc = 0;
+            }
+          }
+        }
+      }
+      if (mine && nacc) bsvd_flush(pl, lcnt + w * 64);
+      if (users) atomicAdd(&s_users, users);
+    }
+    __syncthreads();
+    for (uint32_t j = t; j < mw * 64; j += 256)
+      if (lcnt[j]) atomicAdd(&cnt[j], lcnt[j]);
+    if (t == 0 && s_users) atomicAdd(&misc[0], s_users);
+    __threadfence();
+    __syncthreads();
+    if (t == 0) {
+      s_last = atomicAdd(&misc[1], 1u) == gridDim.x - 1 ? 1u : 0u;
+      s_any = 0;
+    }
+    __syncthreads();
+    if (!s_last) return;  // (gridDim.x > 1: the launch holds one atom)
+    __threadfence();
+    if (t == 0) {
+      s_u = atomicExch(&misc[0], 0u);
+      atomicExch(&misc[1], 0u);
+    }
+    __syncthreads();
+    const uint32_t U = s_u;
+    bool any = false;
+    for (uint32_t wi = wave; wi < mw; wi += 4) {  // wave-uniform: one word of the atom per wave
+      const uint32_t j = wi * 64 + lane;
+      const uint64_t dk = D[(uint64_t)k * d_wpr + wi];
+      const uint32_t c0 = atomicExch(&cnt[j], 0u);
+      const bool dbit = (dk >> (63 - lane)) & 1ull;
+      const uint32_t c = dbit ? U - c0 : c0;
+      const bool nb = (U && j < m) ? c > U / 2 : dbit;  // U = 0: the atom is skipped (bsvd.cpp:499)
+      const uint64_t nw = __builtin_bitreverse64(__builtin_amdgcn_ballot_w64(nb));
+      const uint64_t dl = dk ^ nw;
+      if (lane == 0) {
+        __hip_atomic_store(&delta[wi], dl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (dl) D[(uint64_t)k * d_wpr + wi] = nw;
+      }
+      any |= dl != 0;
+    }
+    if (any && lane == 0) atomicOr(&s_any, 1u);
+    __syncthreads();
+    if (t == 0) {
+      __hip_atomic_store(&misc[2], s_any, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (s_any) atomicAdd(changed, 1ull);
+    }
+    __threadfence();
+    __syncthreads();
+  }
+}
+
+size_t bsvd_dict_scratch_bytes(uint32_t n, uint32_t p) {
+  return kBsvdDictHead + (size_t)p * (((size_t)n + 63) / 64) * 8;
+}
+
+uint32_t bsvd_dict_blocks(uint32_t n) {
+  const uint32_t atw = (n + 63) / 64;
+  const uint32_t want = std::min<uint32_t>(256, (atw + 15) / 16);  // at least 16 words of At (1,024 rows) each
+  const uint32_t wpb = (atw + want - 1) / want;
+  return (atw + wpb - 1) / wpb;
+}
+
+namespace {
+struct DictArena {
+  uint32_t *misc, *cnt;
+  uint64_t *delta, *At;
+};
+DictArena dict_arena(void* scratch) {
+  uint8_t* base = static_cast<uint8_t*>(scratch);
+  return {reinterpret_cast<uint32_t*>(base), reinterpret_cast<uint32_t*>(base + 64),
+          reinterpret_cast<uint64_t*>(base + 64 + 64 * 64 * 4), reinterpret_cast<uint64_t*>(base + kBsvdDictHead)};
+}
+}  // namespace
+
+void launch_bsvd_dict_prepare(hipStream_t s, uint32_t n, uint32_t p, const uint64_t* A, uint32_t a_wpr,
+                              void* scratch) {
+  const DictArena ar = dict_arena(scratch);
+  const uint32_t pw = (p + 63) / 64, atw = (n + 63) / 64;
+  launch_fill(s, ar.misc, 0, 64 + (size_t)64 * 64 * 4);  // U, the ticket, the flag; the column counts
+  // the transpose's grid holds four 64-row blocks per unit of gridDim.y (at most 65,535): in chunks of rows
+  for (uint32_t r0 = 0; r0 < n; r0 += kGf2MaxRows) {
+    const uint32_t rows = std::min(n - r0, kGf2MaxRows);
+    launch_gf2_transpose(s, A + (uint64_t)r0 * a_wpr, rows, a_wpr, pw, p, ar.At + r0 / 64, atw, (rows + 63) / 64);
+  }
+}
+
+void launch_bsvd_dict_atoms(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, uint64_t* D,
+                            uint32_t p, uint32_t d_wpr, void* scratch, uint32_t k_lo, uint32_t k_hi,
+                            uint64_t* changed) {
+  const DictArena ar = dict_arena(scratch);
+  const uint32_t mw = (m + 63) / 64, atw = (n + 63) / 64;
+  uint32_t lg = 0;
+  while ((1u << lg) < mw) ++lg;
+  const uint32_t grid = bsvd_dict_blocks(n), wpb = (atw + grid - 1) / grid;
+  k_bsvd_dict<<<grid, 256, 0, s>>>(E, m, mw, lg, e_wpr, D, p, d_wpr, ar.At, atw, wpb, k_lo, k_hi, ar.cnt, ar.delta,
+                                   ar.misc, reinterpret_cast<unsigned long long*>(changed));
+}
+
+// E ^= X over the first mw words of every row (add(E, X, E), binmat.cpp:463-480)
+__global__ __launch_bounds__(256) void k_bsvd_xor(uint64_t* __restrict__ E, uint32_t e_wpr,
+                                                  const uint64_t* __restrict__ X, uint32_t x_wpr, uint64_t total,
+                                                  uint32_t mw) {
+  for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (uint64_t)gridDim.x * 256) {
+    const uint64_t i = idx / mw;
+    const uint32_t w = (uint32_t)(idx - i * mw);
+    E[i * e_wpr + w] ^= X[i * x_wpr + w];
+  }
+}
+
+void launch_bsvd_xor(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* X,
+                     uint32_t x_wpr) {
+  const uint32_t mw = (m + 63) / 64;
+  const uint64_t total = (uint64_t)n * mw;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
+  if (grid) k_bsvd_xor<<<grid, 256, 0, s>>>(E, e_wpr, X, x_wpr, total, mw);
+}
+
+}  // namespace bic

@@ -1384,6 +1384,121 @@ int bic_gf2_mul(bic_ctx* ctx, int op, const uint64_t* A, size_t a_rows, size_t a
   return BIC_OK;
 }
 
+// ---- binary dictionary learning (bsvd.cpp) -----------------------------------------------------
+namespace {
+// E (n x m), D (p x m), A (n x p): the domain and the pitches
+bool bsvd_geom(size_t n, size_t m, size_t e_wpr, size_t p, size_t d_wpr, size_t a_wpr) {
+  if (m < 1 || m > 4096 || p < 1 || p > 4096 || n > 0x7fffffffu) return false;
+  const size_t mw = (m + 63) / 64, pw = (p + 63) / 64;
+  return e_wpr >= mw && d_wpr >= mw && a_wpr >= pw && e_wpr <= 0xffffffffu && d_wpr <= 0xffffffffu &&
+         a_wpr <= 0xffffffffu;
+}
+
+// the two steps without their argument checks; `changed` a device u64 that is written
+int bsvd_coef(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D, size_t p, size_t d_wpr,
+              uint64_t* A, size_t a_wpr, uint64_t* changed) {
+  timed(ctx, "bsvd_coef", [&] {
+    if (changed) bic::launch_fill(ctx->cur, changed, 0, 8);
+    if (n)
+      bic::launch_bsvd_coef(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, (uint32_t)p, (uint32_t)d_wpr, A,
+                            (uint32_t)a_wpr, changed);
+  });
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
+int bsvd_dict(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr,
+              const uint64_t* A, size_t a_wpr, uint64_t* changed) {
+  if (!n) {
+    if (changed) bic::launch_fill(ctx->cur, changed, 0, 8);
+    BIC_HIP(hipGetLastError());
+    return BIC_OK;
+  }
+  int rc = ensure_scratch(ctx, bic::bsvd_dict_scratch_bytes((uint32_t)n, (uint32_t)p));
+  if (rc) return rc;
+  // (a replay of these launches dirties the arena behind the look-back encoders' bookkeeping)
+  hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(ctx->cur, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone) ctx->captured = true;
+  uint8_t* arena = static_cast<uint8_t*>(ctx->scratch);
+  if (!changed) changed = reinterpret_cast<uint64_t*>(arena + bic::kBsvdDictCounts + 16);
+  timed(ctx, "bsvd_dict_prepare", [&] {
+    bic::launch_fill(ctx->cur, changed, 0, 8);
+    bic::launch_bsvd_dict_prepare(ctx->cur, (uint32_t)n, (uint32_t)p, A, (uint32_t)a_wpr, ctx->scratch);
+  });
+  // (the atom launches trust the transpose for which rows exist: none is enqueued after a refused launch)
+  BIC_HIP(hipGetLastError());
+  auto atoms = [&](uint32_t k_lo, uint32_t k_hi) {
+    timed(ctx, "bsvd_dict", [&] {
+      bic::launch_bsvd_dict_atoms(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, (uint32_t)p,
+                                  (uint32_t)d_wpr, ctx->scratch, k_lo, k_hi, changed);
+    });
+  };
+  // one workgroup that owns every row walks the atoms in one launch; otherwise one launch per atom and
+  // one for the last atom's change, ordered by the stream (no workgroup ever waits for another)
+  if (bic::bsvd_dict_blocks((uint32_t)n) == 1) {
+    atoms(0, (uint32_t)p);
+  } else {
+    for (uint32_t k = 0; k <= (uint32_t)p; ++k) atoms(k, k);
+  }
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+}  // namespace
+
+int bic_bsvd_update_coefficients(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D,
+                                 size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* changed) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || (n && (!E || !D || !A))) return BIC_EINVAL;
+  return bsvd_coef(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed);
+}
+
+int bic_bsvd_update_dictionary(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p,
+                               size_t d_wpr, const uint64_t* A, size_t a_wpr, uint64_t* changed) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || (n && (!E || !D || !A))) return BIC_EINVAL;
+  return bsvd_dict(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed);
+}
+
+// learn_model_traditional (bsvd.cpp:1215-1244): E = A D ^ X, then the two steps until neither changes
+// anything. The two counts are read back every iteration: the call blocks.
+int bic_bsvd_learn(bic_ctx* ctx, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m, size_t e_wpr,
+                   uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter, size_t* iters) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || x_wpr < (m + 63) / 64 || x_wpr > 0xffffffffu ||
+      (n && (!X || !E || !D || !A)))
+    return BIC_EINVAL;
+  if (iters) *iters = 0;
+  // mul_AB as bic_gf2_mul launches it, in chunks of the rows one launch's grid can hold
+  const uint32_t mw = (uint32_t)((m + 63) / 64);
+  timed(ctx, "gf2_mul", [&] {
+    for (size_t r0 = 0; r0 < n; r0 += bic::kGf2MaxRows)
+      bic::launch_gf2_ab(ctx->cur, A + r0 * a_wpr, (uint32_t)std::min<size_t>(n - r0, bic::kGf2MaxRows), (uint32_t)a_wpr,
+                         (uint32_t)p, D, (uint32_t)d_wpr, mw, E + r0 * e_wpr, (uint32_t)e_wpr, mw * 64u);
+  });
+  timed(ctx, "bsvd_xor", [&] {
+    bic::launch_bsvd_xor(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, X, (uint32_t)x_wpr);
+  });
+  BIC_HIP(hipGetLastError());
+  // the counts live in the dictionary step's arena, which is sized here once (n = 0 still needs them)
+  if ((rc = ensure_scratch(ctx, bic::bsvd_dict_scratch_bytes((uint32_t)n, (uint32_t)p)))) return rc;
+  size_t it = 0;
+  for (;;) {
+    ++it;
+    uint64_t* counts = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->scratch) + bic::kBsvdDictCounts);
+    if ((rc = bsvd_coef(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, counts))) return rc;
+    if ((rc = bsvd_dict(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, counts + 1))) return rc;
+    uint64_t h[2] = {0, 0};
+    BIC_HIP(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, ctx->cur));
+    BIC_HIP(hipStreamSynchronize(ctx->cur));
+    if (h[0] + h[1] == 0 || (max_iter && it >= max_iter)) break;
+  }
+  if (iters) *iters = it;
+  return BIC_OK;
+}
+
 // log2 C(n, r): the reference's enumL / enumerative_codelength (coding.cpp:19-22,
 // compress7_test.cpp:25-28) without GSL. Exact at r in {0, n} (0) and, for power-of-two n,
 // at r in {1, n-1} (log2 n -- where GSL's last-ulp rounding is unpinned, SURVEY.md §8 c);

@@ -309,11 +309,35 @@ void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_
 void launch_planes_gray(hipStream_t s, const uint64_t* planes, uint32_t rows, uint32_t cols, uint32_t wpr, int plane0,
                         int nplanes, int bps, uint8_t* gray, uint64_t pitch);
 
-// GF(2) algebra (bic_gf2.hip)
+// GF(2) algebra (bic_gf2.hip). Both launches spread their rows over gridDim.y (at most 65,535): the transpose
+// four 64-row blocks per unit, the product 256 rows per unit, so either takes at most kGf2MaxRows source rows
+// (rows of A for the product); a caller with more rows launches them in chunks of that many (a multiple of 64)
+constexpr uint32_t kGf2MaxRows = 65535u * 256u;
 void launch_gf2_transpose(hipStream_t s, const uint64_t* src, uint32_t s_rows, uint32_t s_stride, uint32_t s_words,
                           uint32_t ncols_out, uint64_t* dst, uint32_t d_stride, uint32_t d_words);
 void launch_gf2_ab(hipStream_t s, const uint64_t* A, uint32_t M, uint32_t a_stride, uint32_t kbits, const uint64_t* B,
                    uint32_t b_stride, uint32_t nw, uint64_t* C, uint32_t c_stride, uint32_t nset);
+
+// Binary dictionary learning (bic_bsvd.hip). All matrices in the plane layout; m, p in 1 .. 4096.
+// changed (device u64) is added to, not written: the caller zeroes it. launch_bsvd_coef takes a null one;
+// launch_bsvd_dict_atoms does not (k_bsvd_dict adds to it unconditionally: bsvd_dict in bic_capi.cpp puts a
+// word of the arena in a null pointer's place).
+void launch_bsvd_coef(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* D,
+                      uint32_t p, uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, uint64_t* changed);
+// the dictionary update's arena: kBsvdDictHead bytes (u32 U, ticket, flag at 0; the 4,096 column counts
+// at 64; delta's 64 words after them; at kBsvdDictCounts three u64: the learn loop's two counts and the
+// stand-in for a null `changed`), then the transpose of A
+constexpr size_t kBsvdDictCounts = 64 + 64 * 64 * 4 + 64 * 8, kBsvdDictHead = 17408;
+size_t bsvd_dict_scratch_bytes(uint32_t n, uint32_t p);
+uint32_t bsvd_dict_blocks(uint32_t n);  // 1: one workgroup walks the atoms in one launch
+// the zeroed counters and the transpose of A (in row chunks of kGf2MaxRows); then the atoms k_lo .. k_hi
+// (k = p: the last atom's change alone) in one launch: 0 .. p when bsvd_dict_blocks(n) is 1, else one atom per launch, in order; n >= 1
+void launch_bsvd_dict_prepare(hipStream_t s, uint32_t n, uint32_t p, const uint64_t* A, uint32_t a_wpr, void* scratch);
+void launch_bsvd_dict_atoms(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, uint64_t* D,
+                            uint32_t p, uint32_t d_wpr, void* scratch, uint32_t k_lo, uint32_t k_hi,
+                            uint64_t* changed);
+void launch_bsvd_xor(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* X,
+                     uint32_t x_wpr);
 
 // Byte fill by a kernel (every device-side memset of the library): hipMemsetAsync enqueued under stream
 // capture replays wrongly on this ROCm (the first captured memset of a process zeroed 800 of 1,280 bytes,

@@ -2,6 +2,7 @@
 // HIP kernels through the C ABI (bic.h). This file only moves data and bookkeeping; every
 // pixel-level operation runs in the kernels.
 #include "bic_gpu.h"
+#include "bsvd.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -334,6 +335,57 @@ int Device::match_encode(binary_matrix& I, unsigned W, unsigned T, unsigned R, M
   return BIC_OK;
 }
 
+int Device::bsvd_run(int step, const binary_matrix* X, binary_matrix& E, binary_matrix& D, binary_matrix& A,
+                     size_t max_iter, idx_t* result) {
+  BIC_TRY(status_);
+  const idx_t n = E.get_rows(), m = E.get_cols(), p = D.get_rows();
+  if (D.get_cols() != m || A.get_rows() != n || A.get_cols() != p || (X && !same_shape(*X, E))) return BIC_EINVAL;
+  if ((n && (!E.raw_blocks() || !A.raw_blocks())) || (p && !D.raw_blocks())) return BIC_EINVAL;
+  const idx_t ew = E.get_blocks_per_row(), dw = D.get_blocks_per_row(), aw = A.get_blocks_per_row();
+  BIC_TRY(ensure(out_a_, n * ew * 8 + 8));
+  BIC_TRY(ensure(out_b_, p * dw * 8 + 8));
+  BIC_TRY(ensure(aux_, n * aw * 8 + 8));
+  BIC_TRY(ensure(small_, 64));
+  if (X) BIC_TRY(ensure(in_, n * ew * 8 + 8));
+  uint64_t* d_E = static_cast<uint64_t*>(out_a_.p);
+  uint64_t* d_D = static_cast<uint64_t*>(out_b_.p);
+  uint64_t* d_A = static_cast<uint64_t*>(aux_.p);
+  uint64_t* d_ch = static_cast<uint64_t*>(small_.p);
+  if (!X) BIC_TRY(upload(E, d_E));  // (learn forms E itself)
+  BIC_TRY(upload(D, d_D));
+  BIC_TRY(upload(A, d_A));
+  uint64_t res = 0;
+  if (step == 2) {
+    uint64_t* d_X = static_cast<uint64_t*>(in_.p);
+    BIC_TRY(upload(*X, d_X));
+    size_t it = 0;
+    BIC_TRY(bic_bsvd_learn(ctx_, d_X, ew, d_E, n, m, ew, d_D, p, dw, d_A, aw, max_iter, &it));
+    res = it;
+  } else {
+    if (step == 0) BIC_TRY(bic_bsvd_update_coefficients(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch));
+    else BIC_TRY(bic_bsvd_update_dictionary(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch));
+    BIC_TRY(bic_memcpy_d2h(ctx_, &res, d_ch, 8));  // (waits for the step)
+  }
+  BIC_TRY(download(d_E, E));
+  if (step != 0) BIC_TRY(download(d_D, D));
+  if (step != 1) BIC_TRY(download(d_A, A));
+  if (result) *result = res;
+  return BIC_OK;
+}
+
+int Device::bsvd_update_coefficients(binary_matrix& E, const binary_matrix& D, binary_matrix& A, idx_t* changed) {
+  return bsvd_run(0, nullptr, E, const_cast<binary_matrix&>(D), A, 0, changed);  // (step 0 only reads D)
+}
+
+int Device::bsvd_update_dictionary(binary_matrix& E, binary_matrix& D, const binary_matrix& A, idx_t* changed) {
+  return bsvd_run(1, nullptr, E, D, const_cast<binary_matrix&>(A), 0, changed);  // (step 1 only reads A)
+}
+
+int Device::bsvd_learn(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A, size_t max_iter,
+                       idx_t* iters) {
+  return bsvd_run(2, &X, E, D, A, max_iter, iters);
+}
+
 Device& default_device() {
   static Device* dev = new Device(0);
   if (dev->status() != BIC_OK) {
@@ -344,3 +396,38 @@ Device& default_device() {
 }
 
 }  // namespace bic
+
+// ---- include/bsvd.h on the default device --------------------------------------------------------
+namespace {
+idx_t bsvd_or_abort(const char* what, int rc, idx_t value) {
+  if (rc != BIC_OK) {
+    std::fprintf(stderr, "%s: %s\n", what, bic_strerror(rc));
+    std::abort();
+  }
+  return value;
+}
+}  // namespace
+
+idx_t update_coefficients_basic(binary_matrix& E, const binary_matrix& D, binary_matrix& A) {
+  idx_t changed = 0;
+  const int rc = bic::default_device().bsvd_update_coefficients(E, D, A, &changed);
+  return bsvd_or_abort("update_coefficients_basic", rc, changed);
+}
+
+idx_t update_coefficients_omp(binary_matrix& E, const binary_matrix& D, binary_matrix& A) {
+  idx_t changed = 0;
+  const int rc = bic::default_device().bsvd_update_coefficients(E, D, A, &changed);
+  return bsvd_or_abort("update_coefficients_omp", rc, changed);
+}
+
+idx_t update_dictionary_steepest(binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  idx_t changed = 0;
+  const int rc = bic::default_device().bsvd_update_dictionary(E, D, A, &changed);
+  return bsvd_or_abort("update_dictionary_steepest", rc, changed);
+}
+
+idx_t learn_model_traditional(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  idx_t iters = 0;
+  const int rc = bic::default_device().bsvd_learn(X, E, D, A, 0, &iters);
+  return bsvd_or_abort("learn_model_traditional", rc, iters);
+}

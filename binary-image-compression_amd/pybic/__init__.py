@@ -32,6 +32,7 @@ EXPORTS = [
     "bic_gf2_transpose", "bic_gf2_mul", "bic_planes_to_gray", "bic_match_encode_inv", "bic_match_encode_var", "bic_egad_row_index",
     "bic_encode_gray16", "bic_encode_gray16_packed", "bic_bitplanes_u16", "bic_decode_gray",
     "bic_encode_pbm", "bic_encode_pbm_packed", "bic_decode_pbm",
+    "bic_bsvd_update_coefficients", "bic_bsvd_update_dictionary", "bic_bsvd_learn",
 ]
 
 # bic_gf2_mul ops (include/bic.h)
@@ -130,6 +131,9 @@ def load(path=LIB_PATH):
     sig("bic_encode_pbm", i32, [vp, vp, sz, i32, sz, sz, vp, sz, i32, vp, sz, vp, vp, sz, vp])
     sig("bic_encode_pbm_packed", i32, [vp, vp, sz, i32, sz, sz, vp, sz, i32, vp, sz, vp, vp, vp, sz, vp, vp, vp])
     sig("bic_decode_pbm", i32, [vp, i32, vp, sz, vp, vp, vp, i32, sz, sz, i32, vp, vp, sz])
+    sig("bic_bsvd_update_coefficients", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
+    sig("bic_bsvd_update_dictionary", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
+    sig("bic_bsvd_learn", i32, [vp, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
     _lib = L
     return L
 
@@ -722,6 +726,34 @@ class Context:
         self._chk(self.lib.bic_gf2_mul(self.h, op, _p(A), A.shape[0], a_cols, A.shape[1], _p(B), B.shape[0], b_cols,
                                        B.shape[1], _p(C), C.shape[0], c_cols, C.shape[1]), "bic_gf2_mul")
         return C
+
+    def _bsvd_step(self, f, name, E, m, D, A, p, changed):
+        ch = self.empty_i64(1) if changed is None else changed
+        self._bind_stream()
+        self._chk(f(self.h, _p(E), E.shape[0], m, E.shape[1], _p(D), p, D.shape[1], _p(A), A.shape[1], _p(ch)), name)
+        return int(as_u64(ch)[0]) if changed is None else changed
+
+    def bsvd_update_coefficients(self, E, m, D, A, p, changed=None):
+        """sparse coding step in place on E [n, e_wpr] and A [n, a_wpr] with the atoms D [p, d_wpr] (int64
+        device tensors, m bits per row of E and D) -> the number of rows that changed (a host read; with
+        `changed`, a device int64[1], nothing is read back: for stream capture)."""
+        return self._bsvd_step(self.lib.bic_bsvd_update_coefficients, "bic_bsvd_update_coefficients", E, m, D, A, p,
+                               changed)
+
+    def bsvd_update_dictionary(self, E, m, D, A, p, changed=None):
+        """dictionary update step in place on E and D, atoms in order -> the number of atoms that changed
+        (`changed` as for bsvd_update_coefficients)."""
+        return self._bsvd_step(self.lib.bic_bsvd_update_dictionary, "bic_bsvd_update_dictionary", E, m, D, A, p,
+                               changed)
+
+    def bsvd_learn(self, X, E, m, D, A, p, max_iter=0):
+        """E = A D ^ X, then both steps until nothing changes (or max_iter iterations) -> iterations run.
+        Blocks (bic_bsvd_learn reads its counts back every iteration)."""
+        it = C.c_size_t(0)
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_learn(self.h, _p(X), X.shape[1], _p(E), E.shape[0], m, E.shape[1], _p(D), p,
+                                          D.shape[1], _p(A), A.shape[1], max_iter, C.byref(it)), "bic_bsvd_learn")
+        return it.value
 
     def pack_streams(self, slots, plane_bits, dst_words=None):
         n, slot_words = slots.shape

@@ -451,6 +451,53 @@ int bic_gf2_mul(bic_ctx* ctx, int op, const uint64_t* A, size_t a_rows, size_t a
                 const uint64_t* B, size_t b_rows, size_t b_cols, size_t b_wpr, uint64_t* C, size_t c_rows,
                 size_t c_cols, size_t c_wpr);
 
+/* ---- binary dictionary learning (bsvd.cpp) ----------------------------------------------------
+ * The two alternating steps of the reference's dictionary learning and the loop around them, for
+ * X = A D ^ E over GF(2): E (n x m) the residual, D (p x m) one atom per row, A (n x p) the
+ * coefficients, X (n x m) the data; all in the plane layout, device memory, pitches e_wpr, d_wpr,
+ * x_wpr >= ceil(m/64) and a_wpr >= ceil(p/64). Domain: 1 <= m <= 4096, 1 <= p <= 4096, n < 2^31;
+ * outside it BIC_EINVAL; n = 0 is BIC_OK with changed = 0. The whole domain runs: where one launch's
+ * grid cannot hold n rows (the transpose and the product behind these entries take 16,776,960 rows
+ * per launch) the rows go in chunks. Padding bits are not masked: as the
+ * reference's dist, weight and add (binmat.cpp:57-67, 463-512) the kernels run over the first
+ * ceil(m/64) whole words of a row; the padding bits of D and A are never changed; words past a
+ * row's own (the pitch) are neither read nor written. The caller supplies D and A (the reference's
+ * model initialisers are not part of this build).
+ *
+ * bic_bsvd_update_coefficients = update_coefficients_basic / _omp (bsvd.cpp:399-460, 1029-1107; the
+ * same result, rows are independent): for each row i, repeat: w = weight(E_i), d_k = dist(E_i, D_k)
+ * for every k, bestk the smallest k that attains the minimum (the scan runs k upward with a strict
+ * <, :423-437); if d_bestk < w then E_i ^= D_bestk and A(i, bestk) is flipped (an atom may be
+ * switched off again), else the row is done. Every step lowers weight(E_i): at most
+ * 64 ceil(m/64) steps per row. changed (device u64, nullable) is written, not accumulated, with the
+ * number of rows that took at least one step.
+ *
+ * bic_bsvd_update_dictionary = update_dictionary_steepest (bsvd.cpp:463-527; not the _omp variant,
+ * whose counters race). The atoms are updated in order, k = 0 .. p - 1: U = the rows with A(i,k)
+ * set (U = 0 skips the atom); c_j = how many of them have bit j of E_i ^ D_k set, j < m; the new
+ * atom has bit j = (c_j > U / 2), integer division, and D_k's own padding bits; if it differs from
+ * D_k, every using row gets E_i ^= D_k ^ new, D_k = new, and changed (device u64, nullable,
+ * written) counts the atom. The order is part of the result: a row that uses atoms k1 < k2 carries
+ * k1's change into k2's counts. Runs as launches ordered on the ctx stream, p + 1 of one kernel (or
+ * one when a single workgroup owns every row), without host synchronisation and without any
+ * workgroup waiting for another; the transpose of A and the counters live in the ctx scratch.
+ *
+ * Both steps can be stream-captured once the scratch has its size: it is sized on first use, so
+ * call bic_bsvd_update_dictionary once with the same n and p before capturing.
+ *
+ * bic_bsvd_learn = learn_model_traditional (bsvd.cpp:1215-1244): E = A D ^ X (bic_gf2_mul with
+ * BIC_GF2_AB, then a word-wise XOR), then the two steps alternate until the sum of their changed
+ * counts is 0. iters (HOST pointer, nullable) receives the number of iterations run, the
+ * reference's return value; max_iter = 0 means no cap (as the reference), otherwise the call stops
+ * after max_iter iterations and still returns BIC_OK. This call blocks: it reads the two counts
+ * back every iteration, so it returns after the work has completed and cannot be stream-captured. */
+int bic_bsvd_update_coefficients(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D,
+                                 size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* changed);
+int bic_bsvd_update_dictionary(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p,
+                               size_t d_wpr, const uint64_t* A, size_t a_wpr, uint64_t* changed);
+int bic_bsvd_learn(bic_ctx* ctx, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m, size_t e_wpr,
+                   uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter, size_t* iters);
+
 /* ---- kernel timing ------------------------------------------------------------------------
  * When enabled, every kernel launch of this ctx is bracketed by HIP events on the launch stream.
  * bic_prof_collect syncs, writes one line per kernel name ("name launches total_ms\n") into buf

@@ -110,6 +110,15 @@ class Device {
                    GolombCoder* golomb_match = nullptr, GolombCoder* golomb_nomatch = nullptr,
                    const double* enuml = nullptr);
 
+  // bsvd.cpp:399-460 / 463-527 / 1215-1244 (bic.h "binary dictionary learning"): E and X n x m, D p x m,
+  // A n x p, 1 <= m, p <= 4096. The matrices are uploaded, the step runs on the device, and what it
+  // may have changed is downloaded: E and A; E and D; E, D and A. changed / iters (nullable) receive the
+  // reference functions' return values. max_iter = 0: no cap (the reference's loop).
+  int bsvd_update_coefficients(binary_matrix& E, const binary_matrix& D, binary_matrix& A, idx_t* changed = nullptr);
+  int bsvd_update_dictionary(binary_matrix& E, binary_matrix& D, const binary_matrix& A, idx_t* changed = nullptr);
+  int bsvd_learn(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A, size_t max_iter = 0,
+                 idx_t* iters = nullptr);
+
  private:
   struct Buf {
     void* p = nullptr;
@@ -119,6 +128,9 @@ class Device {
   int upload(const binary_matrix& M, uint64_t* dst);
   int download(uint64_t* src, binary_matrix& M);
   int fetch_stream(const uint64_t* slot, uint64_t bits, Stream* s);
+  // step: 0 coefficients, 1 dictionary, 2 learn (X then non-null)
+  int bsvd_run(int step, const binary_matrix* X, binary_matrix& E, binary_matrix& D, binary_matrix& A,
+               size_t max_iter, idx_t* result);
 
   bic_ctx* ctx_ = nullptr;
   int status_ = BIC_ENODEV;
