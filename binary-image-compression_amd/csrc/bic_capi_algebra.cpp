@@ -1,0 +1,206 @@
+// bic_capi_algebra.cpp -- GF(2) algebra (bic_gf2.hip) and binary dictionary learning (bic_bsvd.hip).
+#include "bic_ctx.h"
+
+#include <algorithm>
+
+namespace {
+
+bool gf2_geom(size_t rows, size_t cols, size_t wpr) {
+  return rows <= 0x7fffffffu && cols <= 0x7fffff00u && wpr >= (cols + 63) / 64 && wpr <= 0xffffffffu;
+}
+
+// E (n x m), D (p x m), A (n x p): the domain and the pitches
+bool bsvd_geom(size_t n, size_t m, size_t e_wpr, size_t p, size_t d_wpr, size_t a_wpr) {
+  if (m < 1 || m > 4096 || p < 1 || p > 4096 || n > 0x7fffffffu) return false;
+  const size_t mw = (m + 63) / 64, pw = (p + 63) / 64;
+  return e_wpr >= mw && d_wpr >= mw && a_wpr >= pw && e_wpr <= 0xffffffffu && d_wpr <= 0xffffffffu &&
+         a_wpr <= 0xffffffffu;
+}
+
+// the two steps without their argument checks; `changed` a device u64 that is written
+int bsvd_coef(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D, size_t p, size_t d_wpr,
+              uint64_t* A, size_t a_wpr, uint64_t* changed) {
+  timed(ctx, "bsvd_coef", [&] {
+    if (changed) bic::launch_fill(ctx->cur, changed, 0, 8);
+    if (n)
+      bic::launch_bsvd_coef(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, (uint32_t)p, (uint32_t)d_wpr, A,
+                            (uint32_t)a_wpr, changed);
+  });
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
+int bsvd_dict(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr,
+              const uint64_t* A, size_t a_wpr, uint64_t* changed) {
+  if (!n) {
+    if (changed) bic::launch_fill(ctx->cur, changed, 0, 8);
+    BIC_HIP(hipGetLastError());
+    return BIC_OK;
+  }
+  int rc = ensure_scratch(ctx, bic::bsvd_dict_scratch_bytes((uint32_t)n, (uint32_t)p));
+  if (rc) return rc;
+  uint8_t* arena = static_cast<uint8_t*>(ctx->scratch);
+  if (!changed) changed = reinterpret_cast<uint64_t*>(arena + bic::kBsvdDictCounts + 16);
+  timed(ctx, "bsvd_dict_prepare", [&] {
+    bic::launch_fill(ctx->cur, changed, 0, 8);
+    bic::launch_bsvd_dict_prepare(ctx->cur, (uint32_t)n, (uint32_t)p, A, (uint32_t)a_wpr, ctx->scratch);
+  });
+  // (the atom launches trust the transpose for which rows exist: none is enqueued after a refused launch)
+  BIC_HIP(hipGetLastError());
+  auto atoms = [&](uint32_t k_lo, uint32_t k_hi) {
+    timed(ctx, "bsvd_dict", [&] {
+      bic::launch_bsvd_dict_atoms(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, (uint32_t)p,
+                                  (uint32_t)d_wpr, ctx->scratch, k_lo, k_hi, changed);
+    });
+  };
+  // one workgroup that owns every row walks the atoms in one launch; otherwise one launch per atom and
+  // one for the last atom's change, ordered by the stream (no workgroup ever waits for another)
+  if (bic::bsvd_dict_blocks((uint32_t)n) == 1) {
+    atoms(0, (uint32_t)p);
+  } else {
+    for (uint32_t k = 0; k <= (uint32_t)p; ++k) atoms(k, k);
+  }
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bic_gf2_transpose(bic_ctx* ctx, const uint64_t* src, size_t rows, size_t cols, size_t wpr, uint64_t* dst,
+                      size_t dst_wpr) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!gf2_geom(rows, cols, wpr) || !gf2_geom(cols, rows, dst_wpr)) return BIC_EINVAL;
+  if (!rows || !cols) return BIC_OK;
+  if (!src || !dst) return BIC_EINVAL;
+  timed(ctx, "gf2_transpose", [&] {
+    bic::launch_gf2_transpose(ctx->cur, src, (uint32_t)rows, (uint32_t)wpr, (uint32_t)((cols + 63) / 64),
+                              (uint32_t)cols, dst, (uint32_t)dst_wpr, (uint32_t)((rows + 63) / 64));
+  });
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
+// mul_AB as the kernel; mul_AtB = transpose(A) then mul_AB; mul_ABt = A times the transpose of B's
+// whole words (its loop runs over A's blocks, binmat.cpp:586-588), stored for j < B.cols.
+int bic_gf2_mul(bic_ctx* ctx, int op, const uint64_t* A, size_t a_rows, size_t a_cols, size_t a_wpr,
+                const uint64_t* B, size_t b_rows, size_t b_cols, size_t b_wpr, uint64_t* C, size_t c_rows,
+                size_t c_cols, size_t c_wpr) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!gf2_geom(a_rows, a_cols, a_wpr) || !gf2_geom(b_rows, b_cols, b_wpr) || !gf2_geom(c_rows, c_cols, c_wpr))
+    return BIC_EINVAL;
+  const uint32_t cw = (uint32_t)((c_cols + 63) / 64);
+  switch (op) {
+    case BIC_GF2_AB:
+      if (c_rows != a_rows || c_cols != b_cols || a_cols != b_rows) return BIC_EINVAL;
+      break;
+    case BIC_GF2_ATB:
+      if (c_rows != a_cols || c_cols != b_cols || a_rows != b_rows) return BIC_EINVAL;
+      break;
+    case BIC_GF2_ABT:
+      if (c_rows != a_rows || c_cols != b_rows || a_cols != b_cols) return BIC_EINVAL;
+      break;
+    case BIC_GF2_ATBT:
+      if (c_rows != a_cols || c_cols != b_rows || a_rows != b_cols) return BIC_EINVAL;
+      return BIC_OK;  // binmat.cpp:596-604: "FALTA!" -- C is returned unchanged
+    default:
+      return BIC_EINVAL;
+  }
+  if (!c_rows || !cw) return BIC_OK;
+  if (!A || !B || !C) return BIC_EINVAL;
+  if (op == BIC_GF2_AB) {
+    timed(ctx, "gf2_mul", [&] {
+      bic::launch_gf2_ab(ctx->cur, A, (uint32_t)a_rows, (uint32_t)a_wpr, (uint32_t)a_cols, B, (uint32_t)b_wpr, cw, C,
+                         (uint32_t)c_wpr, cw * 64u);
+    });
+    BIC_HIP(hipGetLastError());
+    return BIC_OK;
+  }
+  // the transposed operand: At (a_cols x a_rows) or B's whole words transposed (64 aw x b_rows)
+  const bool atb = op == BIC_GF2_ATB;
+  const uint32_t aw = (uint32_t)((a_cols + 63) / 64);
+  const uint64_t t_rows = atb ? a_cols : 64ull * aw, t_src_rows = atb ? a_rows : b_rows;
+  const uint32_t t_words = (uint32_t)((t_src_rows + 63) / 64);
+  uint64_t* T = nullptr;
+  if (t_rows && t_words) {
+    BIC_HIP(hipMallocAsync(reinterpret_cast<void**>(&T), (size_t)t_rows * t_words * 8, ctx->cur));
+    timed(ctx, "gf2_transpose", [&] {
+      if (atb)
+        bic::launch_gf2_transpose(ctx->cur, A, (uint32_t)a_rows, (uint32_t)a_wpr, aw, (uint32_t)a_cols, T, t_words,
+                                  t_words);
+      else
+        bic::launch_gf2_transpose(ctx->cur, B, (uint32_t)b_rows, (uint32_t)b_wpr, aw, (uint32_t)t_rows, T, t_words,
+                                  t_words);
+    });
+  }
+  timed(ctx, "gf2_mul", [&] {
+    if (atb)
+      bic::launch_gf2_ab(ctx->cur, T, (uint32_t)a_cols, t_words, (uint32_t)a_rows, B, (uint32_t)b_wpr, cw, C,
+                         (uint32_t)c_wpr, cw * 64u);
+    else  // cw == t_words (c_cols == b_rows); bits j >= b_rows of the product are 0
+      bic::launch_gf2_ab(ctx->cur, A, (uint32_t)a_rows, (uint32_t)a_wpr, (uint32_t)t_rows, T, t_words, cw, C,
+                         (uint32_t)c_wpr, (uint32_t)std::min<size_t>(b_cols, 64ull * cw));
+  });
+  if (T) (void)hipFreeAsync(T, ctx->cur);
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
+int bic_bsvd_update_coefficients(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D,
+                                 size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* changed) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || (n && (!E || !D || !A))) return BIC_EINVAL;
+  return bsvd_coef(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed);
+}
+
+int bic_bsvd_update_dictionary(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p,
+                               size_t d_wpr, const uint64_t* A, size_t a_wpr, uint64_t* changed) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || (n && (!E || !D || !A))) return BIC_EINVAL;
+  return bsvd_dict(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed);
+}
+
+// learn_model_traditional (bsvd.cpp:1215-1244): E = A D ^ X, then the two steps until neither changes
+// anything. The two counts are read back every iteration: the call blocks.
+int bic_bsvd_learn(bic_ctx* ctx, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m, size_t e_wpr,
+                   uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter, size_t* iters) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || x_wpr < (m + 63) / 64 || x_wpr > 0xffffffffu ||
+      (n && (!X || !E || !D || !A)))
+    return BIC_EINVAL;
+  if (iters) *iters = 0;
+  // mul_AB as bic_gf2_mul launches it, in chunks of the rows one launch's grid can hold
+  const uint32_t mw = (uint32_t)((m + 63) / 64);
+  timed(ctx, "gf2_mul", [&] {
+    for (size_t r0 = 0; r0 < n; r0 += bic::kGf2MaxRows)
+      bic::launch_gf2_ab(ctx->cur, A + r0 * a_wpr, (uint32_t)std::min<size_t>(n - r0, bic::kGf2MaxRows), (uint32_t)a_wpr,
+                         (uint32_t)p, D, (uint32_t)d_wpr, mw, E + r0 * e_wpr, (uint32_t)e_wpr, mw * 64u);
+  });
+  timed(ctx, "bsvd_xor", [&] {
+    bic::launch_bsvd_xor(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, X, (uint32_t)x_wpr);
+  });
+  BIC_HIP(hipGetLastError());
+  // the counts live in the dictionary step's arena, which is sized here once (n = 0 still needs them)
+  if ((rc = ensure_scratch(ctx, bic::bsvd_dict_scratch_bytes((uint32_t)n, (uint32_t)p)))) return rc;
+  size_t it = 0;
+  for (;;) {
+    ++it;
+    uint64_t* counts = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->scratch) + bic::kBsvdDictCounts);
+    if ((rc = bsvd_coef(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, counts))) return rc;
+    if ((rc = bsvd_dict(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, counts + 1))) return rc;
+    uint64_t h[2] = {0, 0};
+    BIC_HIP(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, ctx->cur));
+    BIC_HIP(hipStreamSynchronize(ctx->cur));
+    if (h[0] + h[1] == 0 || (max_iter && it >= max_iter)) break;
+  }
+  if (iters) *iters = it;
+  return BIC_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,96 @@
+// bic_capi_decode.cpp -- the decoders' entry points (bic_decode.hip): streams to planes, to gray samples,
+// to P4 rasters. The three differ in their sink alone.
+#include "bic_ctx.h"
+
+namespace {
+
+// The stream arguments every decoder takes, checked and put into c. BIC_OK with c.rows == 0: nothing
+// to decode, the pointers (`sink` = where the entry's output goes) unchecked.
+int stream_call(bic::DecodeCall& c, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                const uint64_t* plane_bits, const uint64_t* index, int nplanes, size_t rows, size_t cols, size_t wpr,
+                int predict, const uint8_t* p00, const void* sink) {
+  if (coder != BIC_CODER_GOLOMB && coder != BIC_CODER_EG && coder != BIC_CODER_EG_ADAPTIVE) return BIC_EINVAL;
+  if (nplanes < 1 || !geom_ok(rows, cols, wpr) || !bic::decode_supported((uint32_t)cols)) return BIC_EINVAL;
+  c.rows = (uint32_t)rows;
+  if (rows == 0) return BIC_OK;
+  if (!streams || !plane_bits || !sink || (slot_words == 0 && !word_off)) return BIC_EINVAL;
+  if (coder != BIC_CODER_EG && !index) return BIC_EINVAL;  // the two coders whose rows start from an index
+  c.coder = coder == BIC_CODER_GOLOMB ? 0 : coder == BIC_CODER_EG ? 1 : 2;
+  c.streams = streams;
+  c.slot = slot_words;
+  c.word_off = word_off;
+  c.plane_bits = plane_bits;
+  c.index = index;
+  c.p00 = p00;
+  c.cols = (uint32_t)cols;
+  c.wpr = (uint32_t)wpr;
+  c.nplanes = (uint32_t)nplanes;
+  c.predict = predict ? 1 : 0;
+  return BIC_OK;
+}
+
+int run_decode(bic_ctx* ctx, const char* name, bic::DecodeCall& c) {
+  const int rc = ensure_scratch(ctx, bic::decode_scratch_bytes(c));
+  if (rc) return rc;
+  c.scratch = ctx->scratch;
+  c.flags = ctx->flags;
+  c.egnib = ctx->lut + bic::kLutEgadDec;
+  timed(ctx, name, [&] { bic::launch_decode(ctx->cur, c); });
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bic_decode_planes(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                      const uint64_t* plane_bits, const uint64_t* index, int nplanes, size_t rows, size_t cols,
+                      size_t wpr, int predict, const uint8_t* p00, uint64_t* planes) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  bic::DecodeCall c{};
+  if ((rc = stream_call(c, coder, streams, slot_words, word_off, plane_bits, index, nplanes, rows, cols, wpr, predict,
+                        p00, planes)) || !c.rows)
+    return rc;
+  c.sink = bic::DecodeCall::kPlanes;
+  c.planes = planes;
+  return run_decode(ctx, "decode", c);
+}
+
+int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                    const uint64_t* plane_bits, const uint64_t* index, int plane0, int nplanes, size_t rows, size_t cols,
+                    int predict, const uint8_t* p00, int sample_bytes, int big_endian, void* gray, size_t pitch) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if ((sample_bytes != 1 && sample_bytes != 2) || plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 * sample_bytes ||
+      pitch < cols * (size_t)sample_bytes)
+    return BIC_EINVAL;
+  bic::DecodeCall c{};
+  if ((rc = stream_call(c, coder, streams, slot_words, word_off, plane_bits, index, nplanes, rows, cols,
+                        (cols + 63) / 64, predict, p00, gray)) || !c.rows)
+    return rc;
+  c.sink = bic::DecodeCall::kGray;
+  c.gray = {static_cast<uint8_t*>(gray), (uint64_t)pitch, plane0, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0};
+  return run_decode(ctx, "decode_gray", c);
+}
+
+int bic_decode_pbm(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                   const uint64_t* plane_bits, const uint64_t* index, int nframes, size_t rows, size_t cols, int predict,
+                   const uint8_t* p00, uint8_t* raster, size_t frame_stride) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  bic::DecodeCall c{};
+  if ((rc = stream_call(c, coder, streams, slot_words, word_off, plane_bits, index, nframes, rows, cols,
+                        (cols + 63) / 64, predict, p00, raster)))
+    return rc;
+  const size_t frame_bytes = rows * ((cols + 7) / 8);
+  if (nframes == 1) frame_stride = frame_bytes;  // (one frame: the stride is not read)
+  else if (frame_stride < frame_bytes) return BIC_EINVAL;
+  if (!c.rows) return BIC_OK;
+  c.sink = bic::DecodeCall::kPbm;
+  c.pbm = {raster, (uint64_t)frame_stride};
+  return run_decode(ctx, "decode_pbm", c);
+}
+
+}  // extern "C"

@@ -90,139 +90,6 @@ __device__ __forceinline__ void store_row(const DecArgs& a, uint32_t plane, uint
   for (uint32_t w = a.used + lane; w < a.wpr; w += 64) dst[w] = 0;  // pad words
 }
 
-// Golomb: one LANE per row, so a wave decodes 64 rows side by side (each lane's codeword chain is
-// serial, and 64 chains in lockstep keep the SIMD issuing). The lanes' stream words come through a
-// per-lane ring in LDS, refilled on a uniform cadence: every kDecRefill codewords each lane issues
-// the loads of its next kDecBatch words into registers and writes the batch loaded one cadence
-// earlier into its ring. (Loading each word when a lane crosses into it would make the wave wait
-// for the latest load into the same registers -- issued one codeword earlier by some other lane --
-// at nearly every codeword: vmcnt is per wave and in order.) A lane that runs ahead of its ring
-// (long codewords) reads the words it lacks directly. Each 1 of the residual row goes into an
-// output word in a register; a word is stored when the next 1 lies beyond it -- as D (the row's
-// prefix XOR, unmed's row part) when predicting, R otherwise.
-constexpr uint32_t kDecRing = 32, kDecBatch = 8, kDecRefill = 16;
-__global__ __launch_bounds__(256) void k_dec_golomb_lanes(DecArgs a) {
-  __shared__ uint64_t ring[kDecRing * 256];  // [slot][thread]
-  const uint64_t id = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (id >= (uint64_t)a.rows * a.nplanes) return;
-  const uint32_t plane = (uint32_t)(id / a.rows), row = (uint32_t)(id % a.rows);
-  const uint64_t* st = plane_stream(a, plane);
-  const uint64_t G = a.index[2 * id], O = a.index[2 * id + 1];
-  const uint64_t E = row + 1 < a.rows ? a.index[2 * id + 2] : a.plane_bits[plane];
-  bool over;
-  const uint64_t maxw = plane_words(a, plane, over);  // words of this plane's stream
-  uint64_t* dst = a.out + ((uint64_t)plane * a.rows + row) * a.wpr;
-  bool bad = over || E < G + 1;  // every row has at least its end-of-row codeword
-  const uint64_t len = bad ? 0 : E - G;
-  auto ld = [&](uint64_t i) -> uint64_t { return i < maxw ? bswap64(st[i]) : 0ull; };
-  uint64_t* my = ring + threadIdx.x;
-  auto slot = [&](uint64_t i) -> uint64_t& { return my[(uint32_t)(i % kDecRing) * 256]; };
-  // ring: words [wl - kDecRing, wr) readable from LDS; [wr, wl) in flight in pend[]
-  uint64_t pend[kDecBatch];
-  uint64_t wl = (G >> 6) & ~(uint64_t)(kDecBatch - 1), wr = wl;
-  auto issue = [&]() {
-#pragma unroll
-    for (uint32_t q = 0; q < kDecBatch; ++q) pend[q] = wl + q < maxw ? st[wl + q] : 0ull;
-    wl += kDecBatch;
-  };
-  auto commit = [&]() {  // the batch in pend[] -> its ring slots
-#pragma unroll
-    for (uint32_t q = 0; q < kDecBatch; ++q) slot(wr + q) = bswap64(pend[q]);
-    wr += kDecBatch;
-  };
-  issue();
-  commit();
-  issue();
-  uint64_t wi = G >> 6;
-  auto get = [&](uint64_t i) -> uint64_t { return i < wr ? slot(i) : ld(i); };
-  uint64_t w0 = get(wi), w1 = get(wi + 1);
-  uint32_t b = (uint32_t)(G & 63);  // bit position in w0
-  uint64_t used_bits = 0;           // stream bits consumed by the row so far
-  auto peek = [&]() -> uint64_t { return b ? (w0 << b) | (w1 >> (64 - b)) : w0; };
-  auto advance = [&](uint32_t nb) {  // nb <= 64
-    used_bits += nb;
-    b += nb;
-    if (b >= 64) {
-      b -= 64;
-      w0 = w1;
-      ++wi;
-      w1 = get(wi + 1);
-    }
-  };
-  auto refill = [&]() {  // every lane still decoding, at the same codeword count
-    if (wl > wr) commit();
-    if (wl + kDecBatch - wi <= kDecRing) issue();  // (the slots it will fill hold words < wi)
-  };
-  uint32_t it = 0;
-  const bool pred = a.predict != 0;
-  const uint64_t p00 = (pred && row == 0 && a.p00 && a.p00[plane]) ? BIC_MSB : 0ull;
-  uint32_t ow = 0, carry = 0;  // output word being filled, the prefix-XOR carry into it
-  uint64_t acc = 0;
-  auto flush = [&]() {  // store word ow (then ow + 1 is the open one)
-    uint64_t x = acc;
-    if (pred) {
-      if (row == 0 && ow == 0) x = (x & ~BIC_MSB) | p00;  // R(0, 0) -> P(0, 0)
-      x ^= x >> 1;
-      x ^= x >> 2;
-      x ^= x >> 4;
-      x ^= x >> 8;
-      x ^= x >> 16;
-      x ^= x >> 32;  // bit j (MSB-first) = XOR of the word's bits 0..j
-      const uint32_t par = (uint32_t)(x & 1ull);
-      if (carry) x = ~x;
-      carry ^= par;
-    }
-    if (ow == a.used - 1) x &= a.trail;
-    dst[ow] = x;
-    ++ow;
-    acc = 0;
-  };
-  uint32_t n = (uint32_t)(O + row), A = (uint32_t)((uint64_t)row * a.cols - O);
-  uint32_t j = 0;  // the row's next column
-  while (!bad) {
-    if ((++it & (kDecRefill - 1)) == 0) refill();
-    const uint32_t k = golomb_k_state(n, A);
-    uint32_t low = 0;
-    if (k) {
-      low = (uint32_t)(peek() >> (64 - k));
-      advance(k);
-    }
-    uint64_t z = 0;  // unary zeros up to the '1'
-    for (;;) {
-      const uint64_t y = peek();
-      if (y) {
-        const uint32_t c = (uint32_t)__builtin_clzll(y);
-        z += c;
-        advance(c + 1);
-        break;
-      }
-      z += 64;
-      advance(64);
-      if (used_bits > len || z > a.cols) break;
-    }
-    if (used_bits > len || z > a.cols) {
-      bad = true;
-      break;
-    }
-    const uint32_t s = ((uint32_t)z << k) | low;
-    if ((uint64_t)j + s > a.cols) {
-      bad = true;
-      break;
-    }
-    ++n;
-    A += s;
-    if (j + s == a.cols) break;  // the end-of-row codeword
-    const uint32_t c = j + s;    // the 1 of this codeword's sample
-    while ((c >> 6) > ow) flush();
-    acc |= BIC_MSB >> (c & 63);
-    j = c + 1;
-  }
-  if (used_bits != len) bad = true;
-  while (ow < a.used) flush();
-  for (uint32_t w = a.used; w < a.wpr; ++w) dst[w] = 0;  // pad words
-  if (bad) atomicOr(&a.flags[1], 2u);                     // malformed stream (bic_sync: BIC_EDATA)
-}
-
 // EG adaptive (BIC_CODER_EG_ADAPTIVE: eg.cpp:20-37 with incBlockSize enabled) in the read order of the
 // #if 0 decoder (eg.cpp:41-55): per run '1' = a full block (len += blockSize, then incBlockSize), until
 // a '0' and the g-bit remainder (then decBlockSize) -- or until a block passes the columns left,
@@ -1148,72 +1015,68 @@ void launch_col_apply_pbm(hipStream_t s, const uint64_t* D, const uint64_t* ctot
 
 bool decode_supported(uint32_t cols) { return cols >= 1 && (cols + 63) / 64 <= kDecRowWords; }
 
-size_t decode_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes) {
-  const uint64_t nch = (rows + kColChunk - 1) / kColChunk;
-  return (size_t)nplanes * nch * wpr * 8 + (size_t)nplanes * 4 + 256;
+// The arena: ctot (per plane, column chunk and word) at offset 0, first_row (per plane) behind it, and
+// for a gray or P4 sink the D buffer (nplanes * rows * wpr words) at the next 256-aligned offset
+static size_t decode_dbuf_offset(const DecodeCall& c) {
+  const uint64_t nch = (c.rows + kColChunk - 1) / kColChunk;
+  const size_t head = (size_t)c.nplanes * nch * c.wpr * 8 + (size_t)c.nplanes * 4 + 256;
+  return c.sink == DecodeCall::kPlanes ? head : (head + 255) & ~(size_t)255;
+}
+size_t decode_scratch_bytes(const DecodeCall& c) {
+  return decode_dbuf_offset(c) + (c.sink == DecodeCall::kPlanes ? 0 : (size_t)c.nplanes * c.rows * c.wpr * 8);
 }
 
-// bic_decode_gray's arena: bic_decode_planes' scratch, then the D buffer (nplanes * rows * wpr words)
-static size_t decode_gray_dbuf_offset(uint32_t rows, uint32_t wpr, uint32_t nplanes) {
-  return (decode_scratch_bytes(rows, wpr, nplanes) + 255) & ~(size_t)255;
-}
-size_t decode_gray_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes) {
-  return decode_gray_dbuf_offset(rows, wpr, nplanes) + (size_t)nplanes * rows * wpr * 8;
-}
-
-void launch_decode(hipStream_t s, int coder, const uint64_t* streams, uint64_t slot, const uint64_t* word_off,
-                   const uint64_t* plane_bits, const uint64_t* index, const uint8_t* p00, uint32_t rows,
-                   uint32_t cols, uint32_t wpr, uint32_t nplanes, int predict, uint64_t* out, void* scratch,
-                   uint32_t* flags, const uint64_t* egnib, const GrayOut* go, const PbmOut* po) {
+void launch_decode(hipStream_t s, const DecodeCall& c) {
+  const uint32_t rows = c.rows, cols = c.cols, wpr = c.wpr, nplanes = c.nplanes;
+  const bool to_planes = c.sink == DecodeCall::kPlanes;
   // to gray samples or P4 rasters: the row kernels' output goes to the arena's D buffer instead of the
   // caller's planes
-  if (go || po) out = reinterpret_cast<uint64_t*>(static_cast<char*>(scratch) + decode_gray_dbuf_offset(rows, wpr, nplanes));
+  uint64_t* out = to_planes ? c.planes
+                            : reinterpret_cast<uint64_t*>(static_cast<char*>(c.scratch) + decode_dbuf_offset(c));
   DecArgs a;
-  a.egnib = egnib;
+  a.egnib = c.egnib;
   a.rows = rows;
   a.cols = cols;
   a.wpr = wpr;
   a.used = (cols + 63) / 64;
   a.nplanes = nplanes;
   a.trail = cols % 64 ? ~(~0ull >> (cols % 64)) : ~0ull;
-  a.streams = streams;
-  a.slot = slot;
-  a.word_off = word_off;
-  a.plane_bits = plane_bits;
-  a.index = index;
-  a.p00 = p00;
+  a.streams = c.streams;
+  a.slot = c.slot;
+  a.word_off = c.word_off;
+  a.plane_bits = c.plane_bits;
+  a.index = c.index;
+  a.p00 = c.p00;
   a.out = out;
-  a.flags = flags;
-  a.predict = predict;
-  uint64_t* ctot = reinterpret_cast<uint64_t*>(scratch);
+  a.flags = c.flags;
+  a.predict = c.predict;
+  uint64_t* ctot = reinterpret_cast<uint64_t*>(c.scratch);
   const uint64_t nch = (rows + kColChunk - 1) / kColChunk;
   a.first_row = reinterpret_cast<uint32_t*>(ctot + (uint64_t)nplanes * nch * wpr);
   const uint64_t nrows = (uint64_t)rows * nplanes;
   const uint32_t grid = (uint32_t)((nrows + 3) / 4);
   a.ctot = nullptr;
-  const bool fused_chunks = coder == 0 && predict && rows % kColChunk == 0;
-  if (coder == 0) {
+  const bool fused_chunks = c.coder == 0 && c.predict && rows % kColChunk == 0;
+  if (c.coder == 0) {
     if (fused_chunks) a.ctot = ctot;
-#ifdef BIC_DEC_LANES
-    k_dec_golomb_lanes<<<(uint32_t)((nrows + 255) / 256), 256, 0, s>>>(a);
-#else
     k_dec_golomb_nib<<<(uint32_t)((nrows + 255) / 256), 256, 0, s>>>(a);
-#endif
-  } else if (coder == 2) {
+  } else if (c.coder == 2) {
     k_dec_egad<<<(uint32_t)((nrows + 255) / 256), 256, 0, s>>>(a);
   } else {
     (void)launch_fill(s, a.first_row, 0xff, (size_t)nplanes * 4);
     k_dec_eg_first<<<grid, 256, 0, s>>>(a);
     k_dec_eg_rows<<<grid, 256, 0, s>>>(a);
   }
-  if (predict) {
+  if (c.predict) {
     const uint64_t nt = (uint64_t)nplanes * nch * wpr;
     if (!fused_chunks) k_col_chunks<<<(uint32_t)((nt + 255) / 256), 256, 0, s>>>(out, ctot, rows, wpr, nplanes);
     k_col_scan_par<<<nplanes * wpr, 256, 0, s>>>(ctot, rows, wpr);
-    if (!go && !po) k_col_apply<<<(uint32_t)((nt + 255) / 256), 256, 0, s>>>(out, ctot, rows, wpr, nplanes);
+    if (to_planes) k_col_apply<<<(uint32_t)((nt + 255) / 256), 256, 0, s>>>(out, ctot, rows, wpr, nplanes);
   }
-  if (go) launch_col_apply_gray(s, out, predict ? ctot : nullptr, rows, cols, wpr, nplanes, *go);
-  if (po) launch_col_apply_pbm(s, out, predict ? ctot : nullptr, rows, cols, wpr, nplanes, *po);
+  if (c.sink == DecodeCall::kGray)
+    launch_col_apply_gray(s, out, c.predict ? ctot : nullptr, rows, cols, wpr, nplanes, c.gray);
+  if (c.sink == DecodeCall::kPbm)
+    launch_col_apply_pbm(s, out, c.predict ? ctot : nullptr, rows, cols, wpr, nplanes, c.pbm);
 }
 
 }  // namespace bic

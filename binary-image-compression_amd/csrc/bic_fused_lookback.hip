@@ -1,6 +1,6 @@
 // bic_fused_lookback.hip -- the row encoders that resolve the dependencies between rows with
 // decoupled look-backs inside one launch. The staged encoder (bic_fused.hip) is the default; these
-// serve the small batches (bic_capi.cpp staged_pays; BIC_OPT_SINGLE_KERNEL forces the single kernel)
+// serve the small batches (bic_capi_rows.cpp staged_pays; BIC_OPT_SINGLE_KERNEL forces the single kernel)
 // and are its cross-checks (BIC_OPT_TWO_PASS). The single kernel (k_encode_rows):
 //  * tiles are claimed in order through an atomic ticket, so every tile a workgroup looks back
 //    at was claimed earlier and is running or finished (no deadlock, whatever the dispatch order);

@@ -1,5 +1,5 @@
 // bic_internal.h -- shared between the HIP kernels (bic_kernels.hip) and the C ABI
-// (bic_capi.cpp). Not installed; the public surface is include/bic.h.
+// (bic_capi*.cpp; the context they share is bic_ctx.h). Not installed; the public surface is include/bic.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -66,28 +66,41 @@ constexpr size_t kLutEgadDec = kLutEgadNib + 976;  // the decoder's table (992 u
 constexpr size_t kLutWords = kLutEgadDec + 992;    // the whole buffer
 // f1 decoders (bic_decode.hip)
 bool decode_supported(uint32_t cols);
-size_t decode_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes);
-// bic_decode_gray: the samples the decoded planes (plane b = bit plane0 + b) go to, and its arena
-// (decode_scratch_bytes plus the D buffer of nplanes * rows * wpr words)
+// bic_decode_gray: the samples the decoded planes (plane b = bit plane0 + b) go to
 struct GrayOut {
   uint8_t* gray;
   uint64_t pitch;
   int plane0, bps, big_endian;
 };
-size_t decode_gray_scratch_bytes(uint32_t rows, uint32_t wpr, uint32_t nplanes);
-// bic_decode_pbm: the P4 rasters the decoded planes go to (plane f = frame f at raster + f * stride;
-// the arena as for GrayOut)
+// bic_decode_pbm: the P4 rasters the decoded planes go to (plane f = frame f at raster + f * stride)
 struct PbmOut {
   uint8_t* raster;
   uint64_t stride;
 };
-// egnib: egad_build_dec_nib's table in device memory (the context's byte-table buffer, kLutEgadDec).
-// go and po null: streams -> planes in `out`; go: streams -> gray samples, po: streams -> P4 rasters
-// (`out` unused, the scratch sized by decode_gray_scratch_bytes)
-void launch_decode(hipStream_t s, int coder, const uint64_t* streams, uint64_t slot, const uint64_t* word_off,
-                   const uint64_t* plane_bits, const uint64_t* index, const uint8_t* p00, uint32_t rows,
-                   uint32_t cols, uint32_t wpr, uint32_t nplanes, int predict, uint64_t* out, void* scratch,
-                   uint32_t* flags, const uint64_t* egnib, const GrayOut* go = nullptr, const PbmOut* po = nullptr);
+// One decode: the streams, the geometry, and the sink the decoded planes go to.
+struct DecodeCall {
+  int coder;  // 0 Golomb, 1 EG, 2 adaptive EG
+  const uint64_t* streams;
+  uint64_t slot;  // > 0: plane p at streams + p * slot; 0: packed, plane p at word_off[p]
+  const uint64_t *word_off, *plane_bits, *index;
+  const uint8_t* p00;
+  uint32_t rows, cols, wpr, nplanes;
+  int predict;
+  enum { kPlanes, kGray, kPbm } sink;
+  // the one `sink` names
+  uint64_t* planes;
+  GrayOut gray;
+  PbmOut pbm;
+  // the context's: its arena (decode_scratch_bytes of this call), its error flags, and egad_build_dec_nib's
+  // table in device memory (the context's byte-table buffer, kLutEgadDec)
+  void* scratch;
+  uint32_t* flags;
+  const uint64_t* egnib;
+};
+// the column totals and the EG first rows; for kGray and kPbm also the D buffer (nplanes * rows * wpr
+// words) the row kernels write instead of the caller's planes
+size_t decode_scratch_bytes(const DecodeCall& c);
+void launch_decode(hipStream_t s, const DecodeCall& c);
 // the adaptive EG decoder's nibble table (62 states x 16 nibbles, u64), built on the host
 void egad_build_dec_nib(uint64_t* T);
 void launch_med_rows(hipStream_t s, const Geom& g, const uint64_t* planes, int predict, uint64_t* resid,
@@ -320,7 +333,7 @@ void launch_gf2_ab(hipStream_t s, const uint64_t* A, uint32_t M, uint32_t a_stri
 
 // Binary dictionary learning (bic_bsvd.hip). All matrices in the plane layout; m, p in 1 .. 4096.
 // changed (device u64) is added to, not written: the caller zeroes it. launch_bsvd_coef takes a null one;
-// launch_bsvd_dict_atoms does not (k_bsvd_dict adds to it unconditionally: bsvd_dict in bic_capi.cpp puts a
+// launch_bsvd_dict_atoms does not (k_bsvd_dict adds to it unconditionally: bsvd_dict in bic_capi_algebra.cpp puts a
 // word of the arena in a null pointer's place).
 void launch_bsvd_coef(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* D,
                       uint32_t p, uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, uint64_t* changed);

@@ -443,7 +443,7 @@ def test_narrow_rows_pitched(ctx, oracle, rows, cols, wpr, p):
 
 def test_look_back_records_left_zero(ctx, oracle):
     """The single-kernel and two-pass encoders skip zeroing their counters and look-back records when
-    the previous call's k_fixup left them zero (bic_capi.cpp scratch_zero): calls of growing and
+    the previous call's k_fixup left them zero (bic_ctx.h scratch_zero): calls of growing and
     shrinking row counts, with other users of the context's scratch (the staged encoder, the
     multi-pass kernels) in between, each checked against the oracle"""
     seq = [("single-kernel", 40, 1000), ("single-kernel", 12, 1000), ("single-kernel", 90, 1000),
@@ -461,7 +461,7 @@ def test_look_back_records_left_zero(ctx, oracle):
 @pytest.mark.parametrize("encoder_name", ["single-kernel", "two-pass"])
 def test_capture_replay_between_other_work(ctx, oracle, encoder_name):
     """the single and two-pass encoders skip their record / counter memset when the previous
-    call's k_fixup left them zero (host bookkeeping, bic_capi.cpp scratch_zero). A call captured into a
+    call's k_fixup left them zero (host bookkeeping, bic_ctx.h scratch_zero). A call captured into a
     graph, and replays of it between other calls of the context, are work that bookkeeping never sees: a
     graph captured while the arena was clean must still clear it on every replay. Capture an encode, then
     replay it right after a staged encode (which leaves its counters dirty) and between eager calls;
@@ -507,5 +507,56 @@ def test_capture_replay_between_other_work(ctx, oracle, encoder_name):
             ctx.sync()
             torch.cuda.synchronize()
             assert same(o3, b3, P2), rep
+    finally:
+        ctx.set_encoder("auto")
+
+
+@pytest.mark.parametrize("encoder_name", ["single-kernel", "two-pass"])
+def test_captured_decode_replayed_between_look_back_encodes(ctx, oracle, encoder_name):
+    """Every user of the context's arena notes stream capture (bic_ctx.h ensure_scratch), not the row
+    encoders alone: a captured decode's replay writes its column totals (k_col_chunks: the EG coder with
+    prediction) over the arena's first words, where the look-back encoders keep their tile ticket and
+    records, between two eager encodes that the host bookkeeping sees back to back. Each eager encode
+    around each replay must equal the oracle's, and the replayed decode the source."""
+    torch = ctx.torch
+    rows, cols = 64, 2000
+    P1 = oracle.gen_plane(43, 0.3, rows, cols)[None]
+    P2 = oracle.gen_plane(44, 0.45, 3 * rows, cols)[None]
+    d1, d2 = ctx.to_dev(P1), ctx.to_dev(P2)
+    p00 = torch.tensor([int(P1[0, 0, 0] >> np.uint64(63))], dtype=torch.uint8, device=ctx.dev)
+    back = ctx.empty_i64(1, rows, (cols + 63) // 64)
+
+    def encode_p2(tag):  # an eager look-back encode, both coders against the oracle
+        (og, bg), (oe, be) = ctx.encode_planes2(d2, cols, True)
+        ctx.sync()
+        torch.cuda.synchronize()
+        for coder, out, bits in ((0, og, bg), (1, oe, be)):
+            eb, est, _ = oracle.encode_plane(P2[0], cols, 1, coder)
+            nb = int(as_u64(bits)[0])
+            assert nb == eb, (tag, coder)
+            assert stream_bytes(out[0], nb) == est.tobytes(), (tag, coder)
+
+    ctx.set_encoder(encoder_name)
+    try:
+        # every call once eagerly: the arena has its final size before the capture
+        (_, _), (oe1, be1) = ctx.encode_planes2(d1, cols, True)
+        ctx.decode_planes(CODER_EG, oe1, be1, 1, rows, cols, True, p00=p00, out=back)
+        encode_p2("setup")
+        assert np.array_equal(as_u64(back), P1)
+        side = torch.cuda.Stream(ctx.dev)
+        side.wait_stream(torch.cuda.current_stream(ctx.dev))
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(gr, stream=side):
+                ctx.decode_planes(CODER_EG, oe1, be1, 1, rows, cols, True, p00=p00, out=back)
+        torch.cuda.current_stream(ctx.dev).wait_stream(side)
+        torch.cuda.synchronize()
+        for rep in range(3):
+            encode_p2((rep, "before"))  # leaves the records zero
+            back.zero_()
+            gr.replay()  # the decoder's column totals now lie over them
+            torch.cuda.synchronize()
+            encode_p2((rep, "after"))
+            assert np.array_equal(as_u64(back), P1), rep
     finally:
         ctx.set_encoder("auto")

@@ -30,7 +30,7 @@ def test_prof_only_brackets_named_launches(ctx):
 
 @pytest.mark.parametrize("encoder", ["auto", "staged", "single-kernel", "two-pass"])
 def test_prof_rows_timing_every_encoder(ctx, encoder):
-    """the emission's kernel timing (bic_capi.cpp timed_rows) on every row encoder: the single and
+    """the emission's kernel timing (bic_ctx.h timed_rows) on every row encoder: the single and
     two-pass encoders have no separate main kernel, and their end event must still be recorded --
     an event left unrecorded fails the elapsed-time query, and that HIP error used to stay pending and
     fail the NEXT call (bench.py --gpus 2 --shard planes: bic error 3)"""
@@ -81,7 +81,7 @@ _ROWS_GE = [("encode_rows_golomb_eg", 1), ("encode_rows_golomb_eg_stage", 1)]
 _GRAY = [("bitplanes_count", 1)] + _STAGED
 # (path, encoder, BIC_OPT_EG_SOURCE, the call, bic_prof_collect's lines: name and launch count, in its
 # order) -- the lists are those of a run of the commit before the host side of the row encoders was
-# reorganised into one driver (bic_capi.cpp run_fused), on these inputs
+# reorganised into one driver (bic_capi_rows.cpp run_fused), on these inputs
 _RECORD_PATHS = [
     ("planes2-staged-predict", "staged", 1, _planes2(True), _STAGED + _ROWS_GE),
     ("planes2-staged-nopredict", "staged", 1, _planes2(False), _STAGED + _ROWS_GE),

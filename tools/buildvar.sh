@@ -9,7 +9,7 @@ SRCS=${@:-csrc/bic_fused.hip csrc/bic_kernels.hip}
 make -s lib/libbic.so
 FL="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -I../include -Icsrc $D"
 mkdir -p build/var lib
-OBJS=$(sed -n 's/^lib\/libbic.so:\(.*\)$/\1/p' Makefile | tr ' ' '\n' | grep '\.o$')
+OBJS=$(make -s objs)
 OUT=""
 for o in $OBJS; do
   b=$(basename $o .o)
