@@ -842,7 +842,10 @@ __global__ __launch_bounds__(256) void k_egad_rmap(EgadArgs a) {
 #pragma unroll
     for (int t = 0; t < K; ++t) {
       if (!found && L.R[t]) {
-        const uint32_t b = (uint32_t)__builtin_clzll(L.R[t]);
+        // (after the last 1 of that 1's nibble: eg_lane_nib2 codes whole nibbles from the one holding the next
+        // 1, and a start inside it would have the columns up to the start coded again, as zeros)
+        const uint32_t q = (uint32_t)__builtin_clzll(L.R[t]) >> 2;
+        const uint32_t b = 4 * q + 3 - (uint32_t)__builtin_ctz((uint32_t)(L.R[t] >> (60 - 4 * q)) & 15u);
         L.jp = (int)((L.w0 + t) * 64 + b);
         L.R[t] &= b == 63 ? 0ull : ~0ull >> (b + 1);
         found = true;

@@ -438,9 +438,10 @@ def test_from_file(ctx, oracle, staged, tmp_path):
 
 
 # 13. the first row of a plane starts from a fresh coder, so its Golomb decoder reads the first stream
-#     bytes bit by bit and only then from its byte table. In these rows (seeds found with a host model of
-#     that decoder) the last bit-by-bit byte ends inside a zero run that has just crossed a 64-column word:
-#     the table steps after it must place their columns in the word the run reached
+#     bytes bit by bit and only then from its byte table. In these rows (seeds found with the decoder
+#     census, tests/decoder_census.py: g_stale_step_first_row) the last bit-by-bit byte ends inside a zero
+#     run that has just crossed a 64-column word: the table steps after it must place their columns in the
+#     word the run reached
 @pytest.mark.parametrize("seed", [105, 111, 590])
 def test_round_trip_first_row_run_across_word(ctx, oracle, staged, seed):
     rows, cols, n = 1, 256, 1
