@@ -683,4 +683,34 @@ __device__ __forceinline__ void emit_codeword(Sink& sk, Off off, uint32_t s, uin
   sk.bit(off + k + (s >> k));
 }
 
+// A plane read with get_submatrix's flat word indexing (binmat.cpp:267-298): the word after the last
+// one of a row is the first of the next row, words past the last row read 0 (k_patch_search, bic_dict.hip)
+struct FlatImage {
+  const uint64_t* I;
+  uint32_t rows, used, wpr;
+  // 64 bits of row i starting at column j (j < 64 * used)
+  __device__ __forceinline__ uint64_t window(uint32_t i, uint32_t j) const {
+    if (i >= rows) return 0;
+    const uint32_t w = j >> 6, sh = j & 63;
+    const uint64_t a = I[(uint64_t)i * wpr + w];
+    if (!sh) return a;
+    uint64_t b = 0;
+    if (w + 1 < used) b = I[(uint64_t)i * wpr + w + 1];
+    else if (i + 1 < rows) b = I[(uint64_t)(i + 1) * wpr];
+    return (a << sh) | (b >> (64 - sh));
+  }
+  // the first 32 of those bits (window(i, j) >> 32): the next word is read only when they cross
+  // into it (sh > 32)
+  __device__ __forceinline__ uint32_t window32(uint32_t i, uint32_t j) const {
+    if (i >= rows) return 0;
+    const uint32_t w = j >> 6, sh = j & 63;
+    const uint64_t a = I[(uint64_t)i * wpr + w];
+    if (sh <= 32) return (uint32_t)(a >> (32 - sh));
+    uint64_t b = 0;
+    if (w + 1 < used) b = I[(uint64_t)i * wpr + w + 1];
+    else if (i + 1 < rows) b = I[(uint64_t)(i + 1) * wpr];
+    return __builtin_amdgcn_alignbit((uint32_t)a, (uint32_t)(b >> 32), 64 - sh);
+  }
+};
+
 }  // namespace bic

@@ -352,6 +352,38 @@ void launch_bsvd_dict_atoms(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, 
 void launch_bsvd_xor(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* X,
                      uint32_t x_wpr);
 
+// The growing-dictionary tile coder of compress2_test.cpp:79-129 / compress3_test.cpp:87-149 (bic_dict.hip).
+// The plane is only read. Everything below `arena` is carved from the scratch by dict_carve, which also
+// puts arena arrays in the place of null per-tile outputs.
+struct DictArgs {
+  const uint64_t* I;
+  uint32_t rows, cols, wpr, used, W, nx, ny, T;
+  uint32_t step;                    // atom k's window is at pixel (i * step, j * step) of its tile (i, j)
+  uint32_t variant;                 // 2 or 3
+  double h;                         // 0.5 log2(W*W) (variant 2) or 0 (variant 3)
+  const double* enuml;              // device, W*W+1
+  uint32_t *bestk, *bestd, *dsize, *weights;
+  uint8_t *modes, *joined;
+  uint32_t* dict_tiles;
+  // arena
+  uint64_t* state;                  // [0] |D|, [1] L, [2] matches
+  unsigned long long* keys;         // per tile (distance << 32) | atom: the running first argmin
+  uint64_t *P, *Q;                  // per tile W words: its rows, its atom window's rows (Q = P when step = W)
+  uint32_t* wt;                     // per tile weight
+  uint64_t* nml;                    // per tile nomatch_len
+  uint32_t* lens;                   // per tile chosen length (the sample coder's input)
+  uint32_t* noflags;                // stand-in for the context's flags when no stream is written
+};
+size_t dict_scratch_bytes(size_t ntiles, uint32_t W);
+void dict_carve(DictArgs& a, void* scratch);
+// tiles resolved per block: code 0 = automatic, else code, at most what the resolve kernel's LDS holds
+uint32_t dict_block_tiles(uint32_t W, uint32_t code);
+void launch_dict_gather(hipStream_t s, const DictArgs& a);
+// the block's tiles t0 .. t0 + bn against the atoms in the dictionary (none when t0 = 0: no launch)
+void launch_dict_dist(hipStream_t s, const DictArgs& a, uint32_t t0, uint32_t bn);
+void launch_dict_resolve(hipStream_t s, const DictArgs& a, uint32_t t0, uint32_t bn);
+void launch_dict_finish(hipStream_t s, const DictArgs& a, uint64_t* stats);
+
 // Byte fill by a kernel (every device-side memset of the library): hipMemsetAsync enqueued under stream
 // capture replays wrongly on this ROCm (the first captured memset of a process zeroed 800 of 1,280 bytes,
 // tools/capture_memset_probe.py), and the encoders' calls are meant to be capturable

@@ -335,6 +335,66 @@ int Device::match_encode(binary_matrix& I, unsigned W, unsigned T, unsigned R, M
   return BIC_OK;
 }
 
+int Device::dict_encode(const binary_matrix& I, int variant, unsigned W, unsigned T, unsigned atom_step,
+                        DictResult* out, GolombCoder* golomb_match, GolombCoder* golomb_nomatch, const double* enuml) {
+  BIC_TRY(status_);
+  if (!out || W < 1 || W > 64 || (variant != 2 && variant != 3) || (atom_step != 1 && atom_step != W)) return BIC_EINVAL;
+  if ((golomb_match && !coder_state::fresh(*golomb_match)) || (golomb_nomatch && !coder_state::fresh(*golomb_nomatch)))
+    return BIC_EINVAL;
+  const idx_t rows = I.get_rows(), cols = I.get_cols(), wpr = I.get_blocks_per_row();
+  const size_t nt = ((W - 1 + rows) / W) * ((W - 1 + cols) / W), M = (size_t)W * W;
+  *out = DictResult();
+  if (nt == 0) return BIC_OK;
+  std::vector<double> table;
+  if (!enuml) {
+    table.resize(M + 1);
+    for (size_t w = 0; w <= M; ++w) table[w] = bic_enum_codelength((unsigned)M, (unsigned)w);
+    enuml = table.data();
+  }
+  const size_t cap = variant == 3 ? (nt * (M + 33) + 63) / 64 + 1 : 0;  // a sample <= M: always enough
+  const size_t tile_bytes = ((5 * 4 + 2) * nt + 255) & ~(size_t)255;
+  BIC_TRY(ensure(in_, rows * wpr * 8));
+  BIC_TRY(ensure(out_a_, 2 * cap * 8 + 8));
+  BIC_TRY(ensure(aux_, tile_bytes));
+  BIC_TRY(ensure(small_, 64));
+  uint64_t* d_I = static_cast<uint64_t*>(in_.p);
+  uint64_t* d_s = static_cast<uint64_t*>(out_a_.p);
+  uint32_t* d_t = static_cast<uint32_t*>(aux_.p);
+  uint8_t* d_b = reinterpret_cast<uint8_t*>(d_t + 5 * nt);
+  uint64_t* d_st = static_cast<uint64_t*>(small_.p);
+  BIC_TRY(upload(I, d_I));
+  BIC_TRY(bic_dict_encode(ctx_, variant, d_I, rows, cols, wpr, W, T, atom_step, enuml, d_t, d_t + nt, d_t + 2 * nt,
+                          d_t + 3 * nt, d_b, d_b + nt, d_t + 4 * nt, cap ? d_s : nullptr, cap ? d_s + cap : nullptr,
+                          cap, d_st));
+  BIC_TRY(bic_sync(ctx_));
+  uint64_t st[5];
+  BIC_TRY(bic_memcpy_d2h(ctx_, st, d_st, sizeof(st)));
+  std::vector<uint32_t>* arrs[5] = {&out->bestk, &out->bestd, &out->dsize, &out->weights, &out->dict_tiles};
+  for (int k = 0; k < 5; ++k) {
+    arrs[k]->resize(k == 4 ? st[4] : nt);
+    BIC_TRY(bic_memcpy_d2h(ctx_, arrs[k]->data(), d_t + k * nt, arrs[k]->size() * 4));
+  }
+  out->modes.resize(nt);
+  out->joined.resize(nt);
+  BIC_TRY(bic_memcpy_d2h(ctx_, out->modes.data(), d_b, nt));
+  BIC_TRY(bic_memcpy_d2h(ctx_, out->joined.data(), d_b + nt, nt));
+  out->matches = st[0];
+  out->L = st[3];
+  if (variant != 3) return BIC_OK;
+  BIC_TRY(fetch_stream(d_s, st[1], &out->stream_match));
+  BIC_TRY(fetch_stream(d_s + cap, st[2], &out->stream_nomatch));
+  // the coders' state: samples, their sum and bits per coder (the first tile codes no sample)
+  uint64_t n[2] = {0, 0}, sum[2] = {0, 0};
+  for (size_t i = 1; i < nt; ++i) {
+    const int c = out->modes[i] == 'x' ? 0 : 1;
+    n[c] += 1;
+    sum[c] += out->weights[i];
+  }
+  if (golomb_match) coder_state::advance(*golomb_match, n[0], sum[0], st[1]);
+  if (golomb_nomatch) coder_state::advance(*golomb_nomatch, n[1], sum[1], st[2]);
+  return BIC_OK;
+}
+
 int Device::bsvd_run(int step, const binary_matrix* X, binary_matrix& E, binary_matrix& D, binary_matrix& A,
                      size_t max_iter, idx_t* result) {
   BIC_TRY(status_);

@@ -33,6 +33,7 @@ EXPORTS = [
     "bic_encode_gray16", "bic_encode_gray16_packed", "bic_bitplanes_u16", "bic_decode_gray",
     "bic_encode_pbm", "bic_encode_pbm_packed", "bic_decode_pbm",
     "bic_bsvd_update_coefficients", "bic_bsvd_update_dictionary", "bic_bsvd_learn",
+    "bic_dict_encode", "bic_set_dict_block",
 ]
 
 # bic_gf2_mul ops (include/bic.h)
@@ -108,6 +109,8 @@ def load(path=LIB_PATH):
     sig("bic_patch_search", i32, [vp, vp, sz, sz, sz, u32, vp, vp, vp])
     sig("bic_match_encode", i32, [vp, vp, sz, sz, sz, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp])
     sig("bic_set_match_parts", i32, [vp, u32])
+    sig("bic_dict_encode", i32, [vp, i32, vp, sz, sz, sz, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp])
+    sig("bic_set_dict_block", i32, [vp, u32])
     sig("bic_match_encode_inv", i32, [vp, vp, sz, sz, sz, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp])
     sig("bic_egad_row_index", i32, [vp, vp, i32, sz, sz, sz, i32, vp])
     sig("bic_match_encode_var", i32, [vp, i32, vp, sz, sz, sz, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp])
@@ -673,6 +676,38 @@ class Context:
 
     def set_match_parts(self, parts):
         self._chk(self.lib.bic_set_match_parts(self.h, parts), "bic_set_match_parts")
+
+    def dict_encode(self, plane, cols, variant, W, T=0, atom_step=1, enuml=None, cap_words=None, streams=True):
+        """the growing-dictionary tile coder of compress2_test.cpp (variant 2) / compress3_test.cpp (variant 3,
+        threshold T) (bic_dict_encode). plane: int64 [rows, wpr] device tensor (only read); atom_step 1 (the
+        drivers: atom windows at the pixel of the tile's index pair) or W (the tile itself); enuml: numpy
+        float64 [W*W+1] (host), default enumL from this build. Returns device tensors per tile, dict_tiles
+        (the first stats[4] entries are the dictionary), the two streams (variant 3 with `streams`) and
+        stats int64[5]: matches, bits match, bits nomatch, L, |D|."""
+        rows, wpr = plane.shape
+        nt = ((rows + W - 1) // W) * ((cols + W - 1) // W)
+        t = self.torch
+        bk, bd, ds, wt, dt = (t.empty(nt, dtype=t.int32, device=self.dev) for _ in range(5))
+        modes, joined = (t.empty(nt, dtype=t.uint8, device=self.dev) for _ in range(2))
+        sm = sn = None
+        if variant == 3 and streams:  # a sample is at most W*W, a codeword at most sample + 33 bits
+            cap_words = cap_words or max(1, (nt * (W * W + 33) + 63) // 64 + 1)
+            sm, sn = self.empty_i64(cap_words), self.empty_i64(cap_words)
+        else:
+            cap_words = 0
+        stats = self.empty_i64(5)
+        e = enum_table(W) if enuml is None else np.ascontiguousarray(enuml, np.float64)
+        self._bind_stream()
+        self._chk(self.lib.bic_dict_encode(self.h, variant, _p(plane), rows, cols, wpr, W, T, atom_step,
+                                           e.ctypes.data_as(C.c_void_p), _p(bk), _p(bd), _p(ds), _p(wt), _p(modes),
+                                           _p(joined), _p(dt), _p(sm), _p(sn), cap_words, _p(stats)),
+                  "bic_dict_encode")
+        return dict(bestk=bk, bestd=bd, dsize=ds, weights=wt, modes=modes, joined=joined, dict_tiles=dt,
+                    stream_match=sm, stream_nomatch=sn, stats=stats)
+
+    def set_dict_block(self, tiles):
+        """tiles bic_dict_encode resolves per block (0: automatic); every value gives the same result"""
+        self._chk(self.lib.bic_set_dict_block(self.h, tiles), "bic_set_dict_block")
 
     def pgm_bitplanes(self, raster, rows, cols, maxval, nplanes, plane0=0, wpr=None, out=None):
         """P5 samples (uint8 device tensor view starting at the first sample, any alignment) -> planes"""

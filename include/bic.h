@@ -382,6 +382,41 @@ int bic_match_encode_var(bic_ctx* ctx, int variant, const uint64_t* plane, size_
  * W: the row workgroup alone); other values: per-tile workgroups, count from W and R. */
 int bic_set_match_parts(bic_ctx* ctx, unsigned parts);
 
+/* ---- the growing-dictionary tile coder: compress2_test.cpp:79-129, compress3_test.cpp:87-149 ------
+ * The drivers' whole tile loop with W (argv[2]) and, variant 3, T (argv[3]). Tiles t = 0 .. ny*nx-1 in
+ * raster order over ny = ceil(rows/W), nx = ceil(cols/W), read with get_submatrix's flat indexing as for
+ * bic_patch_search; the image is never written. The dictionary is an ordered list of tiles. Per tile:
+ *   - search: bestk = 0, bestd = W*W; the atoms in dictionary order with strict <, stopping at the first
+ *     distance 0: the first atom at least distance, (0, W*W) when none beats W*W;
+ *   - nomatch_len = (idx_t)(1 + enuml[weight(P)] + h), match_len = (idx_t)(1 + ceil(log2(|D|)) +
+ *     enuml[bestd] + h), the doubles added left to right; h = 0.5 log2(W*W) (variant 2) or 0 (variant 3);
+ *   - an empty dictionary: the tile is pushed, L += nomatch_len, mode 'o', no sample is coded;
+ *   - variant 2: a match ('x', L += match_len) iff nomatch_len > match_len, else pushed ('o',
+ *     L += nomatch_len); no Golomb coder;
+ *   - variant 3: a match iff nomatch_len > match_len ('x', golomb_match codes bestd), else 'o'
+ *     (golomb_nomatch codes weight(P)); then, whatever the mode, pushed iff bestd > T.
+ * atom_step: the drivers push the tile's INDEX pair (i, j) and read atom windows at PIXEL (i, j)
+ * (compress2_test.cpp:87-88,105,124; compress3_test.cpp:95-96,118,145). Atom k's window is at pixel
+ * (i * atom_step, j * atom_step): 1 = the drivers, W = the tile itself; anything else is BIC_EINVAL.
+ *   plane: device, rows x wpr. enuml: HOST array of W*W+1 doubles as for bic_match_encode. Per tile
+ *   (device, each nullable): bestk, bestd, dsize (|D| as the tile saw it), weights (the coded value:
+ *   bestd or weight(P)), modes, joined (1 iff pushed). dict_tiles (device, ny*nx u32, nullable): the
+ *   tile index of every atom, in dictionary order. stream_match / stream_nomatch (device, cap_words each):
+ *   variant 3's codewords; both may be NULL with cap_words = 0 (the lengths only); variant 2 ignores
+ *   them. stats: device u64[5]: matches, bits of golomb_match, bits of golomb_nomatch, L, the final |D|.
+ * BIC_EINVAL (arguments; no device work) for variant not 2 or 3, W outside 1..64, atom_step, geometry.
+ * A stream too small is BIC_ENOSPC from bic_sync, as for bic_match_encode. Nothing is read back and
+ * nothing waits inside the call. */
+int bic_dict_encode(bic_ctx* ctx, int variant, const uint64_t* plane, size_t rows, size_t cols, size_t wpr,
+                    unsigned W, unsigned T, unsigned atom_step, const double* enuml, uint32_t* bestk,
+                    uint32_t* bestd, uint32_t* dsize, uint32_t* weights, uint8_t* modes, uint8_t* joined,
+                    uint32_t* dict_tiles, uint64_t* stream_match, uint64_t* stream_nomatch, size_t cap_words,
+                    uint64_t* stats);
+/* Tiles bic_dict_encode resolves per block (every value gives the same result): 0 (default) = automatic,
+ * else that many, at most 1024 and at most 4096 / W' with W' = W rounded up to a multiple of 8 (what the
+ * resolving workgroup keeps in LDS). */
+int bic_set_dict_block(bic_ctx* ctx, unsigned tiles);
+
 /* log2 C(n, r) (enumerative_codelength, coding.cpp:19-22) computed without GSL, and the tile
  * length table lentab[w] = (uint64)(2 + log2 C(W*W, w)) for w = 0..W*W (host memory, W*W+1
  * entries) that bic_patch_encode takes. Host-side helpers; no device needed. */

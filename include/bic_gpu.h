@@ -63,6 +63,18 @@ struct MatchResult {
   uint64_t matches = 0, L = 0;                // L: sum of the chosen lengths (before the bitcounts)
 };
 
+// Result of the growing-dictionary tile loop of compress2_test.cpp / compress3_test.cpp
+// (Device::dict_encode), per tile in raster order over ceil(rows/W) x ceil(cols/W).
+struct DictResult {
+  std::vector<uint32_t> bestk, bestd;   // the search: first atom at least distance; (0, W*W) when none beats W*W
+  std::vector<uint32_t> dsize;          // |D| as the tile saw it
+  std::vector<uint32_t> weights;        // the coded value: bestd (match) or the tile's weight
+  std::vector<uint8_t> modes, joined;   // 'x' (match) or 'o'; 1 iff the tile was pushed
+  std::vector<uint32_t> dict_tiles;     // the tile index of every atom, dictionary order (the final |D| entries)
+  Stream stream_match, stream_nomatch;  // variant 3: golomb_match / golomb_nomatch codewords
+  uint64_t matches = 0, L = 0;          // L: sum of the chosen lengths (before the bitcounts)
+};
+
 class Device {
  public:
   explicit Device(int ordinal = 0);
@@ -109,6 +121,14 @@ class Device {
   int match_encode(binary_matrix& I, unsigned W, unsigned T, unsigned R, MatchResult* out,
                    GolombCoder* golomb_match = nullptr, GolombCoder* golomb_nomatch = nullptr,
                    const double* enuml = nullptr);
+
+  // compress2_test.cpp:79-129 (variant 2) / compress3_test.cpp:87-149 (variant 3, T as its argv[3]) with W
+  // as argv[2], any rows and cols (bic.h bic_dict_encode). atom_step 1: the drivers (atom windows at the
+  // pixel of the tile's index pair); W: the tile itself. I is only read. Variant 3: golomb_match /
+  // golomb_nomatch (fresh) end in the state the driver's coders end in. enuml as for match_encode.
+  int dict_encode(const binary_matrix& I, int variant, unsigned W, unsigned T, unsigned atom_step, DictResult* out,
+                  GolombCoder* golomb_match = nullptr, GolombCoder* golomb_nomatch = nullptr,
+                  const double* enuml = nullptr);
 
   // bsvd.cpp:399-460 / 463-527 / 1215-1244 (bic.h "binary dictionary learning"): E and X n x m, D p x m,
   // A n x p, 1 <= m, p <= 4096. The matrices are uploaded, the step runs on the device, and what it
