@@ -1,4 +1,4 @@
-// bic_bsvd.hip -- the two steps of the reference's binary dictionary learning on the device
+// bic_bsvd.hip -- the steps of the reference's binary dictionary learning on the device
 // (include/bic.h "binary dictionary learning"):
 //
 //  * bsvd.cpp:399-460 update_coefficients_basic (= :1029-1107 _omp, rows are independent): greedy
@@ -6,6 +6,8 @@
 //    equals (:423-437, strict <), XORed in while it lowers the row's weight (:439-447);
 //  * bsvd.cpp:463-527 update_dictionary_steepest: atom by atom, in order, the per-column majority over
 //    the rows that use the atom (:486-506), the change carried into those rows of E (:512-520);
+//  * bsvd.cpp:530-735 update_dictionary_proximus (= :822-1027 _omp, the same text): per atom, rounds of that
+//    vote for the one atom and a vote of every row's coefficient against the atom, until a round changes nothing;
 //  * bsvd.cpp:1220 add(E, X, E) after mul(A, D, E): the word-wise XOR.
 //
 // Matrices are in the plane layout (bic.h): row-major u64 words, column j at bit 63 - j % 64 of word
@@ -202,20 +204,58 @@ __device__ __forceinline__ void bsvd_flush(uint64_t (&pl)[kBsvdPlanes], uint32_t
   for (int q = 0; q < kBsvdPlanes; ++q) pl[q] = 0;
 }
 
-// misc: [0] U, [1] ticket, [2] delta != 0
+// misc: [0] U, [1] ticket, [2] delta != 0; the PROXIMUS schedule's words (below): [3], [4] `again` by round
+// parity, [5] `stalled` (atom + 1, sticky), [6] the atom's bits changed in an earlier round, [8..9] u64 rounds
+// run, [12..13] u64 atoms changed
+constexpr uint32_t kProxAgain = 3, kProxStalled = 5, kProxKch = 6, kProxRounds = 8, kProxChanged = 12;
+static_assert(kProxStalled * 4 == kBsvdProxStalled && kProxRounds * 4 == kBsvdProxRounds &&
+              kProxChanged * 4 == kBsvdProxChanged, "the host reads these words back");
+constexpr uint32_t kProxCheckPrev = 1, kProxFresh = 2, kProxPrevParity = 4;
+
+__device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Whether a launch of the PROXIMUS schedule leaves at once (the same answer in every workgroup: the words it
+// reads are written by earlier launches only, or, `stalled`, by this launch where `again` already says leave).
+// Round pr > 0 leaves when round pr - 1 moved nothing. The atom half of round 0 looks at the atom before: if
+// its last budgeted round still moved something, that atom is recorded in `stalled`, and every later launch
+// leaves until the host has read the word, cleared it and enqueued from that atom again.
+template <bool ATOM>
+__device__ __forceinline__ bool prox_leaves(uint32_t* misc, uint32_t k, uint32_t pr, uint32_t pflags) {
+  if (ld_agent(&misc[kProxStalled])) return true;
+  if (pr == 0) {
+    if (!ATOM || !(pflags & kProxCheckPrev)) return false;
+    if (!ld_agent(&misc[kProxAgain + ((pflags & kProxPrevParity) ? 1 : 0)])) return false;
+    if (blockIdx.x == 0 && threadIdx.x == 0) st_agent(&misc[kProxStalled], k);  // atom k - 1, plus one
+    return true;
+  }
+  if (ld_agent(&misc[kProxAgain + ((pr - 1) & 1u)])) return false;
+  if (ATOM && blockIdx.x == 0 && threadIdx.x == 0) st_agent(&misc[kProxAgain + (pr & 1u)], 0u);
+  return true;
+}
+
+// PROX: the atom half of one PROXIMUS round (bsvd.cpp:628-671) for atom k_lo = k_hi, round pr of the budget:
+// the same counts and the same vote, but the change is left to k_bsvd_prox_coef (which passes over every
+// row anyway), the atom is counted in *changed once however many rounds change it, and the round is counted.
+template <bool PROX>
 __global__ __launch_bounds__(256) void k_bsvd_dict(uint64_t* __restrict__ E, uint32_t m, uint32_t mw, uint32_t lg,
                                                    uint32_t e_wpr, uint64_t* __restrict__ D, uint32_t p,
                                                    uint32_t d_wpr, const uint64_t* __restrict__ At, uint32_t atw,
                                                    uint32_t wpb, uint32_t k_lo, uint32_t k_hi, uint32_t* cnt,
-                                                   uint64_t* delta, uint32_t* misc, unsigned long long* changed) {
+                                                   uint64_t* delta, uint32_t* misc, unsigned long long* changed,
+                                                   uint32_t pr, uint32_t pflags) {
   __shared__ uint32_t lcnt[64 * 64];
   __shared__ uint32_t s_users, s_last, s_u, s_any;
   const uint32_t t = threadIdx.x, lane = lane_id(), wave = wave_id();
+  if constexpr (PROX) {
+    if (prox_leaves<true>(misc, k_lo, pr, pflags) || k_lo >= p) return;  // (k_lo = p: the last atom's stall check)
+  }
   const uint32_t w = t & ((1u << lg) - 1u), slot = t >> lg, nslots = 256u >> lg;
   const uint32_t a0 = blockIdx.x * wpb, a1 = min(a0 + wpb, atw);
   const bool mine = w < mw;
   for (uint32_t k = k_lo; k <= k_hi; ++k) {
-    if (k > 0 && ld_agent(&misc[2])) {  // atom k - 1 changed: carry it into its users' rows
+    if (!PROX && k > 0 && ld_agent(&misc[2])) {  // atom k - 1 changed: carry it into its users' rows
       const uint64_t dl = mine ? ld_agent(&delta[w]) : 0ull;
       const uint64_t* at = At + (uint64_t)(k - 1) * atw;
       for (uint32_t a = a0 + slot; a < a1; a += nslots) {
@@ -300,7 +340,15 @@ __global__ __launch_bounds__(256) void k_bsvd_dict(uint64_t* __restrict__ E, uin
     __syncthreads();
     if (t == 0) {
       __hip_atomic_store(&misc[2], s_any, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (s_any) atomicAdd(changed, 1ull);
+      if constexpr (PROX) {
+        st_agent(&misc[kProxAgain + (pr & 1u)], s_any);  // the coefficient half ORs its flips in
+        atomicAdd(reinterpret_cast<unsigned long long*>(&misc[kProxRounds]), 1ull);
+        const uint32_t before = (pflags & kProxFresh) ? 0u : ld_agent(&misc[kProxKch]);
+        if (s_any && !before) atomicAdd(changed, 1ull);  // bsvd.cpp:659, 724: once per atom
+        st_agent(&misc[kProxKch], before | s_any);
+      } else {
+        if (s_any) atomicAdd(changed, 1ull);
+      }
     }
     __threadfence();
     __syncthreads();
@@ -350,8 +398,97 @@ void launch_bsvd_dict_atoms(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, 
   uint32_t lg = 0;
   while ((1u << lg) < mw) ++lg;
   const uint32_t grid = bsvd_dict_blocks(n), wpb = (atw + grid - 1) / grid;
-  k_bsvd_dict<<<grid, 256, 0, s>>>(E, m, mw, lg, e_wpr, D, p, d_wpr, ar.At, atw, wpb, k_lo, k_hi, ar.cnt, ar.delta,
-                                   ar.misc, reinterpret_cast<unsigned long long*>(changed));
+  k_bsvd_dict<false><<<grid, 256, 0, s>>>(E, m, mw, lg, e_wpr, D, p, d_wpr, ar.At, atw, wpb, k_lo, k_hi, ar.cnt,
+                                          ar.delta, ar.misc, reinterpret_cast<unsigned long long*>(changed), 0u, 0u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// PROXIMUS (bsvd.cpp:530-735). Per atom, rounds of two launches: k_bsvd_dict<true>, the atom half, and
+// k_bsvd_prox_coef, the coefficient half (:676-719) over ALL rows, one row per lane:
+//
+//   1. a user takes the atom half's pending change, E_i ^= delta (whole words; delta is 0 past m);
+//   2. c = |E_i & D_k| over j < m (D_k's last word masked); |S| = |D_k| over j < m;
+//   3. Aw = c for a non-user, |S| - c for a user; the new A(i,k) is Aw > |S| / 2 (|S| = 0: no vote);
+//   4. where it differs, A(i,k) flips and E_i ^= D_k for j < m;
+//   5. the wave's ballot of the new bits is its word of row k of At, which the next atom half reads:
+//      A and At agree after every launch.
+//
+// `again` (by round parity) is the atom half's "delta != 0" ORed with "some coefficient flipped": the next
+// round runs if it is set, the launches of the rounds after a round that moved nothing leave at once
+// (prox_leaves). No workgroup waits for another; the order is the stream's.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_bsvd_prox_coef(uint64_t* __restrict__ E, uint32_t n, uint32_t m, uint32_t mw,
+                                                        uint32_t e_wpr, const uint64_t* __restrict__ D,
+                                                        uint32_t d_wpr, uint64_t* __restrict__ A, uint32_t a_wpr,
+                                                        uint64_t* __restrict__ At, uint32_t atw, uint32_t k,
+                                                        uint32_t pr, uint32_t* misc, const uint64_t* delta) {
+  __shared__ uint64_t s_dm[64], s_dl[64];
+  if (prox_leaves<false>(misc, k, pr, 0u)) return;
+  const uint32_t t = threadIdx.x, lane = lane_id(), wave = wave_id();
+  const bool pend = ld_agent(&misc[2]) != 0;
+  if (t < mw) {
+    uint64_t dk = D[(uint64_t)k * d_wpr + t];
+    if (t == mw - 1 && (m & 63u)) dk &= ~0ull << (64 - (m & 63u));  // j < m only (bsvd.cpp:681)
+    s_dm[t] = dk;
+    s_dl[t] = pend ? ld_agent(&delta[t]) : 0ull;
+  }
+  __syncthreads();
+  uint32_t S = 0;
+  for (uint32_t w = 0; w < mw; ++w) S += (uint32_t)__popcll(s_dm[w]);
+  uint64_t* atk = At + (uint64_t)k * atw;
+  for (uint32_t wv = blockIdx.x * 4 + wave; wv < atw; wv += gridDim.x * 4) {  // wave-uniform
+    const uint64_t aw = atk[wv];
+    if (!S && !(pend && aw)) continue;  // no vote (:694) and no user with a change to take
+    const uint64_t i = (uint64_t)wv * 64 + lane;
+    const bool live = i < n;
+    const bool a = (aw >> (63 - lane)) & 1ull;  // (At's bits past n are 0)
+    uint64_t* row = E + i * e_wpr;
+    uint32_t c = 0;
+    if (live)
+      for (uint32_t w = 0; w < mw; ++w) c += (uint32_t)__popcll((row[w] ^ (a ? s_dl[w] : 0ull)) & s_dm[w]);
+    const bool nb = S ? (live && (a ? S - c : c) > S / 2) : a;
+    const bool flip = nb != a;
+    if (live && ((a && pend) || flip))
+      for (uint32_t w = 0; w < mw; ++w) {
+        const uint64_t x = (a ? s_dl[w] : 0ull) ^ (flip ? s_dm[w] : 0ull);
+        if (x) row[w] ^= x;
+      }
+    if (flip) A[i * a_wpr + (k >> 6)] ^= BIC_MSB >> (k & 63u);
+    const uint64_t nw = __builtin_bitreverse64(__builtin_amdgcn_ballot_w64(nb));
+    if (nw != aw && lane == 0) {
+      atk[wv] = nw;
+      atomicOr(&misc[kProxAgain + (pr & 1u)], 1u);
+    }
+  }
+}
+
+// (launch_bsvd_dict_prepare's fill covers the schedule's words)
+void launch_bsvd_prox_clear_stall(hipStream_t s, void* scratch) {
+  launch_fill(s, dict_arena(scratch).misc + kProxStalled, 0, 4);
+}
+
+void launch_bsvd_prox_atom(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, uint64_t* D,
+                           uint32_t p, uint32_t d_wpr, void* scratch, uint32_t k, uint32_t r, uint32_t budget,
+                           bool check_prev, bool fresh) {
+  const DictArena ar = dict_arena(scratch);
+  const uint32_t mw = (m + 63) / 64, atw = (n + 63) / 64;
+  uint32_t lg = 0;
+  while ((1u << lg) < mw) ++lg;
+  const uint32_t blocks = bsvd_dict_blocks(n), wpb = (atw + blocks - 1) / blocks;
+  // (the previous atom's last budgeted round is round budget - 1: that is the parity of its `again`)
+  const uint32_t pflags = (check_prev ? kProxCheckPrev : 0u) | (fresh ? kProxFresh : 0u) |
+                          (((budget - 1) & 1u) ? kProxPrevParity : 0u);
+  k_bsvd_dict<true><<<k < p ? blocks : 1u, 256, 0, s>>>(
+      E, m, mw, lg, e_wpr, D, p, d_wpr, ar.At, atw, wpb, k, k, ar.cnt, ar.delta, ar.misc,
+      reinterpret_cast<unsigned long long*>(ar.misc + kProxChanged), r, pflags);
+}
+
+void launch_bsvd_prox_coef(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* D,
+                           uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, void* scratch, uint32_t k, uint32_t r) {
+  const DictArena ar = dict_arena(scratch);
+  const uint32_t mw = (m + 63) / 64, atw = (n + 63) / 64;
+  const uint32_t grid = std::min<uint32_t>((atw + 3) / 4, 2048);
+  k_bsvd_prox_coef<<<grid, 256, 0, s>>>(E, n, m, mw, e_wpr, D, d_wpr, A, a_wpr, ar.At, atw, k, r, ar.misc, ar.delta);
 }
 
 // E ^= X over the first mw words of every row (add(E, X, E), binmat.cpp:463-480)

@@ -2,6 +2,7 @@
 #include "bic_ctx.h"
 
 #include <algorithm>
+#include <cstring>
 
 namespace {
 
@@ -61,6 +62,111 @@ int bsvd_dict(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint6
     for (uint32_t k = 0; k <= (uint32_t)p; ++k) atoms(k, k);
   }
   BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
+// update_dictionary_proximus (bsvd.cpp:530-735). All p atoms are enqueued up front, `budget` rounds of
+// (atom half, coefficient half) each; the launches of the rounds an atom does not need leave at once, and an
+// atom that needs more than its budget stops the batch (every later launch leaves), is read back here and is
+// enqueued again with everything after it. One read-back per batch: the call blocks. The automatic budget
+// is the one of 1, 2, 4, 8 that was fastest from a sparse-coding step's output, where nearly every atom takes
+// two rounds (DESIGN.md §3 "PROXIMUS"): a launch that leaves at once still costs 1.7 us.
+constexpr unsigned kBsvdProxAutoRounds = 2;
+
+int bsvd_prox(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr,
+              uint64_t* A, size_t a_wpr, uint64_t* changed, uint64_t* h_changed, size_t* rounds) {
+  if (h_changed) *h_changed = 0;
+  if (rounds) *rounds = 0;
+  if (!n) {
+    if (changed) bic::launch_fill(ctx->cur, changed, 0, 8);
+    BIC_HIP(hipGetLastError());
+    BIC_HIP(hipStreamSynchronize(ctx->cur));
+    return BIC_OK;
+  }
+  int rc = ensure_scratch(ctx, bic::bsvd_dict_scratch_bytes((uint32_t)n, (uint32_t)p));
+  if (rc) return rc;
+  timed(ctx, "bsvd_dict_prepare",
+        [&] { bic::launch_bsvd_dict_prepare(ctx->cur, (uint32_t)n, (uint32_t)p, A, (uint32_t)a_wpr, ctx->scratch); });
+  BIC_HIP(hipGetLastError());
+  const uint32_t budget = ctx->bsvd_rounds ? ctx->bsvd_rounds : kBsvdProxAutoRounds, np = (uint32_t)p;
+  auto atom = [&](uint32_t k, uint32_t r, bool check_prev, bool fresh) {
+    timed(ctx, "bsvd_prox_atom", [&] {
+      bic::launch_bsvd_prox_atom(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, np, (uint32_t)d_wpr,
+                                 ctx->scratch, k, r, budget, check_prev, fresh);
+    });
+  };
+  uint8_t* arena = static_cast<uint8_t*>(ctx->scratch);
+  uint32_t words[16] = {0};
+  for (uint32_t k0 = 0, resumed = 0;; resumed = 1) {
+    for (uint32_t k = k0; k < np; ++k)
+      for (uint32_t r = 0; r < budget; ++r) {
+        atom(k, r, r == 0 && k > k0, r == 0 && !(resumed && k == k0));
+        timed(ctx, "bsvd_prox_coef", [&] {
+          bic::launch_bsvd_prox_coef(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, (uint32_t)d_wpr, A,
+                                     (uint32_t)a_wpr, ctx->scratch, k, r);
+        });
+      }
+    atom(np, 0, true, false);  // the last atom's stall
+    BIC_HIP(hipGetLastError());
+    BIC_HIP(hipMemcpyAsync(words, arena, sizeof(words), hipMemcpyDeviceToHost, ctx->cur));
+    BIC_HIP(hipStreamSynchronize(ctx->cur));
+    const uint32_t stalled = words[bic::kBsvdProxStalled / 4];
+    if (!stalled) break;
+    k0 = stalled - 1;
+    bic::launch_bsvd_prox_clear_stall(ctx->cur, ctx->scratch);
+  }
+  uint64_t h[2];
+  std::memcpy(&h[0], &words[bic::kBsvdProxChanged / 4], 8);
+  std::memcpy(&h[1], &words[bic::kBsvdProxRounds / 4], 8);
+  if (changed) {
+    BIC_HIP(hipMemcpyAsync(changed, arena + bic::kBsvdProxChanged, 8, hipMemcpyDeviceToDevice, ctx->cur));
+    BIC_HIP(hipStreamSynchronize(ctx->cur));
+  }
+  if (h_changed) *h_changed = h[0];
+  if (rounds) *rounds = (size_t)h[1];
+  return BIC_OK;
+}
+
+// learn_model_traditional (bsvd.cpp:1215-1244) with either dictionary rule: E = A D ^ X, then the two steps
+// until neither changes anything. The counts are read back every iteration: the call blocks.
+int bsvd_learn(bic_ctx* ctx, int du, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m, size_t e_wpr,
+               uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter, size_t* iters) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || x_wpr < (m + 63) / 64 || x_wpr > 0xffffffffu ||
+      (n && (!X || !E || !D || !A)))
+    return BIC_EINVAL;
+  if (iters) *iters = 0;
+  // mul_AB as bic_gf2_mul launches it, in chunks of the rows one launch's grid can hold
+  const uint32_t mw = (uint32_t)((m + 63) / 64);
+  timed(ctx, "gf2_mul", [&] {
+    for (size_t r0 = 0; r0 < n; r0 += bic::kGf2MaxRows)
+      bic::launch_gf2_ab(ctx->cur, A + r0 * a_wpr, (uint32_t)std::min<size_t>(n - r0, bic::kGf2MaxRows), (uint32_t)a_wpr,
+                         (uint32_t)p, D, (uint32_t)d_wpr, mw, E + r0 * e_wpr, (uint32_t)e_wpr, mw * 64u);
+  });
+  timed(ctx, "bsvd_xor", [&] {
+    bic::launch_bsvd_xor(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, X, (uint32_t)x_wpr);
+  });
+  BIC_HIP(hipGetLastError());
+  // the counts live in the dictionary step's arena, which is sized here once (n = 0 still needs them)
+  if ((rc = ensure_scratch(ctx, bic::bsvd_dict_scratch_bytes((uint32_t)n, (uint32_t)p)))) return rc;
+  size_t it = 0;
+  for (;;) {
+    ++it;
+    uint64_t* counts = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->scratch) + bic::kBsvdDictCounts);
+    if ((rc = bsvd_coef(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, counts))) return rc;
+    uint64_t h[2] = {0, 0};
+    if (du == BIC_BSVD_DU_PROXIMUS) {  // (blocks itself; the sparse-coding count is read after it)
+      if ((rc = bsvd_prox(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, nullptr, &h[1], nullptr))) return rc;
+      BIC_HIP(hipMemcpyAsync(h, counts, 8, hipMemcpyDeviceToHost, ctx->cur));
+    } else {
+      if ((rc = bsvd_dict(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, counts + 1))) return rc;
+      BIC_HIP(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, ctx->cur));
+    }
+    BIC_HIP(hipStreamSynchronize(ctx->cur));
+    if (h[0] + h[1] == 0 || (max_iter && it >= max_iter)) break;
+  }
+  if (iters) *iters = it;
   return BIC_OK;
 }
 
@@ -165,41 +271,30 @@ int bic_bsvd_update_dictionary(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, si
   return bsvd_dict(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed);
 }
 
-// learn_model_traditional (bsvd.cpp:1215-1244): E = A D ^ X, then the two steps until neither changes
-// anything. The two counts are read back every iteration: the call blocks.
 int bic_bsvd_learn(bic_ctx* ctx, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m, size_t e_wpr,
                    uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter, size_t* iters) {
+  return bsvd_learn(ctx, BIC_BSVD_DU_STEEPEST, X, x_wpr, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, max_iter, iters);
+}
+
+int bic_bsvd_learn_du(bic_ctx* ctx, int du, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m,
+                      size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter,
+                      size_t* iters) {
+  if (du != BIC_BSVD_DU_STEEPEST && du != BIC_BSVD_DU_PROXIMUS) return BIC_EINVAL;
+  return bsvd_learn(ctx, du, X, x_wpr, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, max_iter, iters);
+}
+
+int bic_bsvd_update_dictionary_proximus(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D,
+                                        size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* changed,
+                                        size_t* rounds) {
   int rc = bind(ctx);
   if (rc) return rc;
-  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || x_wpr < (m + 63) / 64 || x_wpr > 0xffffffffu ||
-      (n && (!X || !E || !D || !A)))
-    return BIC_EINVAL;
-  if (iters) *iters = 0;
-  // mul_AB as bic_gf2_mul launches it, in chunks of the rows one launch's grid can hold
-  const uint32_t mw = (uint32_t)((m + 63) / 64);
-  timed(ctx, "gf2_mul", [&] {
-    for (size_t r0 = 0; r0 < n; r0 += bic::kGf2MaxRows)
-      bic::launch_gf2_ab(ctx->cur, A + r0 * a_wpr, (uint32_t)std::min<size_t>(n - r0, bic::kGf2MaxRows), (uint32_t)a_wpr,
-                         (uint32_t)p, D, (uint32_t)d_wpr, mw, E + r0 * e_wpr, (uint32_t)e_wpr, mw * 64u);
-  });
-  timed(ctx, "bsvd_xor", [&] {
-    bic::launch_bsvd_xor(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, X, (uint32_t)x_wpr);
-  });
-  BIC_HIP(hipGetLastError());
-  // the counts live in the dictionary step's arena, which is sized here once (n = 0 still needs them)
-  if ((rc = ensure_scratch(ctx, bic::bsvd_dict_scratch_bytes((uint32_t)n, (uint32_t)p)))) return rc;
-  size_t it = 0;
-  for (;;) {
-    ++it;
-    uint64_t* counts = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->scratch) + bic::kBsvdDictCounts);
-    if ((rc = bsvd_coef(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, counts))) return rc;
-    if ((rc = bsvd_dict(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, counts + 1))) return rc;
-    uint64_t h[2] = {0, 0};
-    BIC_HIP(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, ctx->cur));
-    BIC_HIP(hipStreamSynchronize(ctx->cur));
-    if (h[0] + h[1] == 0 || (max_iter && it >= max_iter)) break;
-  }
-  if (iters) *iters = it;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || (n && (!E || !D || !A))) return BIC_EINVAL;
+  return bsvd_prox(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed, nullptr, rounds);
+}
+
+int bic_set_bsvd_rounds(bic_ctx* ctx, unsigned rounds) {
+  if (!ctx || rounds > 64) return BIC_EINVAL;
+  ctx->bsvd_rounds = rounds;
   return BIC_OK;
 }
 

@@ -90,6 +90,7 @@ struct bic_ctx {
   size_t rbuf_bytes = 0;
   unsigned match_parts = 0;       // bic_set_match_parts: workgroups per tile (0 = by region size)
   unsigned dict_block = 0;        // bic_set_dict_block: tiles resolved per block (0 = automatic)
+  unsigned bsvd_rounds = 0;       // bic_set_bsvd_rounds: PROXIMUS rounds enqueued per atom (0 = automatic)
   // kernel timing (bic_prof_*): HIP events recorded on the launch stream around each kernel
   bool prof_on = false;
   std::string prof_only;  // bic_prof_only: bracket only launches of this name ("" = all)

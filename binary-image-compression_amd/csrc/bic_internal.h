@@ -351,6 +351,19 @@ void launch_bsvd_dict_atoms(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, 
                             uint64_t* changed);
 void launch_bsvd_xor(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* X,
                      uint32_t x_wpr);
+// PROXIMUS (bsvd.cpp:530-735) after launch_bsvd_dict_prepare: round r of atom k's budget is the atom-half
+// launch and then the coefficient-half launch. check_prev: atom k - 1 was enqueued before with `budget`
+// rounds (its stall is noted here); fresh: atom k's first round of this call (false when a stalled atom is
+// enqueued again). k = p in launch_bsvd_prox_atom only notes atom p - 1's stall. The schedule's words are the
+// u32 of the arena's first 64 bytes: kBsvdProxStalled (atom + 1, or 0), u64 rounds at kBsvdProxRounds, u64
+// atoms changed at kBsvdProxChanged (byte offsets).
+constexpr size_t kBsvdProxStalled = 20, kBsvdProxRounds = 32, kBsvdProxChanged = 48;
+void launch_bsvd_prox_atom(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, uint64_t* D,
+                           uint32_t p, uint32_t d_wpr, void* scratch, uint32_t k, uint32_t r, uint32_t budget,
+                           bool check_prev, bool fresh);
+void launch_bsvd_prox_coef(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* D,
+                           uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, void* scratch, uint32_t k, uint32_t r);
+void launch_bsvd_prox_clear_stall(hipStream_t s, void* scratch);
 
 // The growing-dictionary tile coder of compress2_test.cpp:79-129 / compress3_test.cpp:87-149 (bic_dict.hip).
 // The plane is only read. Everything below `arena` is carved from the scratch by dict_carve, which also

@@ -396,7 +396,7 @@ int Device::dict_encode(const binary_matrix& I, int variant, unsigned W, unsigne
 }
 
 int Device::bsvd_run(int step, const binary_matrix* X, binary_matrix& E, binary_matrix& D, binary_matrix& A,
-                     size_t max_iter, idx_t* result) {
+                     size_t max_iter, idx_t* result, int du, idx_t* rounds) {
   BIC_TRY(status_);
   const idx_t n = E.get_rows(), m = E.get_cols(), p = D.get_rows();
   if (D.get_cols() != m || A.get_rows() != n || A.get_cols() != p || (X && !same_shape(*X, E))) return BIC_EINVAL;
@@ -419,8 +419,13 @@ int Device::bsvd_run(int step, const binary_matrix* X, binary_matrix& E, binary_
     uint64_t* d_X = static_cast<uint64_t*>(in_.p);
     BIC_TRY(upload(*X, d_X));
     size_t it = 0;
-    BIC_TRY(bic_bsvd_learn(ctx_, d_X, ew, d_E, n, m, ew, d_D, p, dw, d_A, aw, max_iter, &it));
+    BIC_TRY(bic_bsvd_learn_du(ctx_, du, d_X, ew, d_E, n, m, ew, d_D, p, dw, d_A, aw, max_iter, &it));
     res = it;
+  } else if (step == 3) {
+    size_t r = 0;
+    BIC_TRY(bic_bsvd_update_dictionary_proximus(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch, &r));
+    BIC_TRY(bic_memcpy_d2h(ctx_, &res, d_ch, 8));
+    if (rounds) *rounds = r;
   } else {
     if (step == 0) BIC_TRY(bic_bsvd_update_coefficients(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch));
     else BIC_TRY(bic_bsvd_update_dictionary(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch));
@@ -428,7 +433,7 @@ int Device::bsvd_run(int step, const binary_matrix* X, binary_matrix& E, binary_
   }
   BIC_TRY(download(d_E, E));
   if (step != 0) BIC_TRY(download(d_D, D));
-  if (step != 1) BIC_TRY(download(d_A, A));
+  if (step != 1) BIC_TRY(download(d_A, A));  // (step 3 changes all three)
   if (result) *result = res;
   return BIC_OK;
 }
@@ -444,6 +449,16 @@ int Device::bsvd_update_dictionary(binary_matrix& E, binary_matrix& D, const bin
 int Device::bsvd_learn(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A, size_t max_iter,
                        idx_t* iters) {
   return bsvd_run(2, &X, E, D, A, max_iter, iters);
+}
+
+int Device::bsvd_learn(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A, int du, size_t max_iter,
+                       idx_t* iters) {
+  return bsvd_run(2, &X, E, D, A, max_iter, iters, du);
+}
+
+int Device::bsvd_update_dictionary_proximus(binary_matrix& E, binary_matrix& D, binary_matrix& A, idx_t* changed,
+                                            idx_t* rounds) {
+  return bsvd_run(3, nullptr, E, D, A, 0, changed, BIC_BSVD_DU_PROXIMUS, rounds);
 }
 
 Device& default_device() {
@@ -484,6 +499,18 @@ idx_t update_dictionary_steepest(binary_matrix& E, binary_matrix& D, binary_matr
   idx_t changed = 0;
   const int rc = bic::default_device().bsvd_update_dictionary(E, D, A, &changed);
   return bsvd_or_abort("update_dictionary_steepest", rc, changed);
+}
+
+idx_t update_dictionary_proximus(binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  idx_t changed = 0;
+  const int rc = bic::default_device().bsvd_update_dictionary_proximus(E, D, A, &changed);
+  return bsvd_or_abort("update_dictionary_proximus", rc, changed);
+}
+
+idx_t update_dictionary_proximus_omp(binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  idx_t changed = 0;
+  const int rc = bic::default_device().bsvd_update_dictionary_proximus(E, D, A, &changed);
+  return bsvd_or_abort("update_dictionary_proximus_omp", rc, changed);
 }
 
 idx_t learn_model_traditional(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {

@@ -34,7 +34,11 @@ EXPORTS = [
     "bic_encode_pbm", "bic_encode_pbm_packed", "bic_decode_pbm",
     "bic_bsvd_update_coefficients", "bic_bsvd_update_dictionary", "bic_bsvd_learn",
     "bic_dict_encode", "bic_set_dict_block",
+    "bic_bsvd_update_dictionary_proximus", "bic_bsvd_learn_du", "bic_set_bsvd_rounds",
 ]
+
+# bic_bsvd_learn_du rules (include/bic.h)
+BSVD_DU_STEEPEST, BSVD_DU_PROXIMUS = 0, 1
 
 # bic_gf2_mul ops (include/bic.h)
 GF2_AB, GF2_ATB, GF2_ABT, GF2_ATBT = 0, 1, 2, 3
@@ -137,6 +141,9 @@ def load(path=LIB_PATH):
     sig("bic_bsvd_update_coefficients", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_update_dictionary", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_learn", i32, [vp, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
+    sig("bic_bsvd_update_dictionary_proximus", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp, C.POINTER(sz)])
+    sig("bic_bsvd_learn_du", i32, [vp, i32, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
+    sig("bic_set_bsvd_rounds", i32, [vp, u32])
     _lib = L
     return L
 
@@ -781,13 +788,36 @@ class Context:
         return self._bsvd_step(self.lib.bic_bsvd_update_dictionary, "bic_bsvd_update_dictionary", E, m, D, A, p,
                                changed)
 
-    def bsvd_learn(self, X, E, m, D, A, p, max_iter=0):
-        """E = A D ^ X, then both steps until nothing changes (or max_iter iterations) -> iterations run.
-        Blocks (bic_bsvd_learn reads its counts back every iteration)."""
+    def bsvd_update_dictionary_proximus(self, E, m, D, A, p, changed=None):
+        """the PROXIMUS dictionary update in place on E, D and A, atoms in order, rounds of (atom vote,
+        coefficient vote over every row) until a round changes nothing -> (atoms whose bits changed, rounds
+        run); with `changed`, a device int64[1], -> (changed, rounds) without reading it. Blocks either way."""
+        ch = self.empty_i64(1) if changed is None else changed
+        rounds = C.c_size_t(0)
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_update_dictionary_proximus(
+            self.h, _p(E), E.shape[0], m, E.shape[1], _p(D), p, D.shape[1], _p(A), A.shape[1], _p(ch),
+            C.byref(rounds)), "bic_bsvd_update_dictionary_proximus")
+        return (int(as_u64(ch)[0]) if changed is None else changed), rounds.value
+
+    def set_bsvd_rounds(self, rounds):
+        """PROXIMUS rounds enqueued per atom before the host looks (0: automatic, else 1 .. 64); every value
+        gives the same result"""
+        self._chk(self.lib.bic_set_bsvd_rounds(self.h, rounds), "bic_set_bsvd_rounds")
+
+    def bsvd_learn(self, X, E, m, D, A, p, max_iter=0, du=0):
+        """E = A D ^ X, then both steps until nothing changes (or max_iter iterations) -> iterations run; du
+        chooses the dictionary rule (BSVD_DU_STEEPEST, BSVD_DU_PROXIMUS). Blocks (the counts are read back
+        every iteration)."""
         it = C.c_size_t(0)
         self._bind_stream()
-        self._chk(self.lib.bic_bsvd_learn(self.h, _p(X), X.shape[1], _p(E), E.shape[0], m, E.shape[1], _p(D), p,
-                                          D.shape[1], _p(A), A.shape[1], max_iter, C.byref(it)), "bic_bsvd_learn")
+        if du == BSVD_DU_STEEPEST:
+            self._chk(self.lib.bic_bsvd_learn(self.h, _p(X), X.shape[1], _p(E), E.shape[0], m, E.shape[1], _p(D), p,
+                                              D.shape[1], _p(A), A.shape[1], max_iter, C.byref(it)), "bic_bsvd_learn")
+        else:
+            self._chk(self.lib.bic_bsvd_learn_du(self.h, du, _p(X), X.shape[1], _p(E), E.shape[0], m, E.shape[1],
+                                                 _p(D), p, D.shape[1], _p(A), A.shape[1], max_iter, C.byref(it)),
+                      "bic_bsvd_learn_du")
         return it.value
 
     def pack_streams(self, slots, plane_bits, dst_words=None):

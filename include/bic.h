@@ -533,6 +533,47 @@ int bic_bsvd_update_dictionary(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, si
 int bic_bsvd_learn(bic_ctx* ctx, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m, size_t e_wpr,
                    uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter, size_t* iters);
 
+/* bic_bsvd_update_dictionary_proximus = update_dictionary_proximus (bsvd.cpp:530-735; _omp, :822-1027,
+ * is the same text), the rank-one refinement that moves an atom and its coefficients together.
+ * Layout, domain, BIC_EINVAL cases and whole-word conventions are those of
+ * bic_bsvd_update_dictionary; A is updated too. For every atom k = 0 .. p - 1 in order, rounds of two
+ * halves until a round changes nothing:
+ *   atom half (:628-671): the steepest step for this atom alone (U = 0 skips it); if D_k changes,
+ *     its users get E_i ^= D_k ^ new over whole words.
+ *   coefficient half (:676-719): S = the set bits of D_k for j < m (|S| = 0 skips it, so a zero atom
+ *     keeps its users); for EVERY row, Aw_i = the bits j in S with E(i,j) ^ A(i,k) set; the new
+ *     A(i,k) is Aw_i > |S| / 2 (integer division: a tie gives 0); where it differs, A(i,k) flips
+ *     and E_i ^= D_k for j < m only (D_k's padding bits are not carried into E here).
+ * An atom without users can recruit some in its coefficient half. changed (device u64, nullable,
+ * written) receives the reference's return value: the atoms whose D_k changed in some round; an atom
+ * whose users changed while its bits did not is not counted (bsvd.cpp:706 is commented out). rounds
+ * (HOST pointer, nullable) receives the number of rounds run over all atoms. The reference's `#if 0`
+ * correlation initialisation (:566-620) is not built. n = 0 is BIC_OK with changed = 0, rounds = 0.
+ *
+ * The number of rounds depends on the data and the atoms are ordered, so the host has to learn how
+ * far the device got: per atom a budget of rounds is enqueued (two launches each; those of the
+ * rounds an atom does not need leave at once), all atoms up front, and what the device reports is
+ * read back once per batch; an atom that needs more than its budget is enqueued again with the atoms
+ * after it. bic_bsvd_update_dictionary_proximus therefore blocks: it returns after the work has
+ * completed and cannot be stream-captured. No workgroup ever waits for another. bic_set_bsvd_rounds
+ * sets the budget (0 = automatic, else 1 .. 64; other values BIC_EINVAL); every value gives the
+ * same result.
+ *
+ * bic_bsvd_learn_du is bic_bsvd_learn with the dictionary rule chosen: BIC_BSVD_DU_STEEPEST gives
+ * bic_bsvd_learn itself (the same launches, the same result), BIC_BSVD_DU_PROXIMUS sums the
+ * sparse-coding count and bic_bsvd_update_dictionary_proximus's changed count (so the loop may stop
+ * after a call that moved only coefficients, as the reference's does); any other du is BIC_EINVAL.
+ * It blocks and cannot be stream-captured, as bic_bsvd_learn. */
+#define BIC_BSVD_DU_STEEPEST 0
+#define BIC_BSVD_DU_PROXIMUS 1
+int bic_bsvd_update_dictionary_proximus(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D,
+                                        size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* changed,
+                                        size_t* rounds);
+int bic_bsvd_learn_du(bic_ctx* ctx, int du, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m,
+                      size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter,
+                      size_t* iters);
+int bic_set_bsvd_rounds(bic_ctx* ctx, unsigned rounds);
+
 /* ---- kernel timing ------------------------------------------------------------------------
  * When enabled, every kernel launch of this ctx is bracketed by HIP events on the launch stream.
  * bic_prof_collect syncs, writes one line per kernel name ("name launches total_ms\n") into buf

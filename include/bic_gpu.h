@@ -138,6 +138,12 @@ class Device {
   int bsvd_update_dictionary(binary_matrix& E, binary_matrix& D, const binary_matrix& A, idx_t* changed = nullptr);
   int bsvd_learn(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A, size_t max_iter = 0,
                  idx_t* iters = nullptr);
+  // bsvd.cpp:530-735, the second dictionary rule (E, D and A all change; rounds: the rounds run over all
+  // atoms), and the loop with the rule chosen: du = BIC_BSVD_DU_STEEPEST (the call above) or BIC_BSVD_DU_PROXIMUS.
+  int bsvd_update_dictionary_proximus(binary_matrix& E, binary_matrix& D, binary_matrix& A, idx_t* changed = nullptr,
+                                      idx_t* rounds = nullptr);
+  int bsvd_learn(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A, int du, size_t max_iter = 0,
+                 idx_t* iters = nullptr);
 
  private:
   struct Buf {
@@ -148,9 +154,9 @@ class Device {
   int upload(const binary_matrix& M, uint64_t* dst);
   int download(uint64_t* src, binary_matrix& M);
   int fetch_stream(const uint64_t* slot, uint64_t bits, Stream* s);
-  // step: 0 coefficients, 1 dictionary, 2 learn (X then non-null)
+  // step: 0 coefficients, 1 dictionary, 2 learn (X then non-null) with the rule du, 3 the PROXIMUS dictionary step
   int bsvd_run(int step, const binary_matrix* X, binary_matrix& E, binary_matrix& D, binary_matrix& A,
-               size_t max_iter, idx_t* result);
+               size_t max_iter, idx_t* result, int du = 0, idx_t* rounds = nullptr);
 
   bic_ctx* ctx_ = nullptr;
   int status_ = BIC_ENODEV;

@@ -7,7 +7,7 @@
 // The model is X = A D + E over GF(2): X (n x m) holds one sample per row, D (p x m) one atom per
 // row, A (n x p) says which atoms a sample uses and E (n x m) is what they leave unexplained.
 // m and p are limited to 1 .. 4096 here. The caller fills D and A; the reference's model
-// initialisers, its other update rules and its model-order searches are not part of this build
+// initialisers, its role-switching learners and its model-order searches are not part of this build
 // (DESIGN.md lists them).
 #ifndef BSVD_H
 #define BSVD_H
@@ -27,6 +27,16 @@ idx_t update_coefficients_omp(binary_matrix& E, const binary_matrix& D, binary_m
 // the samples that use the atom want it once the atom is taken out of their residual, else 0. D and
 // the residual rows of those samples are updated in place. Returns the number of atoms that changed.
 idx_t update_dictionary_steepest(binary_matrix& E, binary_matrix& D, binary_matrix& A);
+
+// The second dictionary rule, a rank-one refinement: for every atom, in D's order, rounds of two halves until
+// a round changes nothing. First the atom is voted as above; then every sample (not only the atom's users)
+// takes or drops the atom according to whether more than half (integer half) of the atom's set bits are set
+// in its residual once the atom is taken out of it. E, D and A are updated in place. Returns the number of
+// atoms whose bits changed (an atom whose users alone changed is not counted, as in the reference).
+idx_t update_dictionary_proximus(binary_matrix& E, binary_matrix& D, binary_matrix& A);
+
+// The same step; both names run the same device kernels and give the same result.
+idx_t update_dictionary_proximus_omp(binary_matrix& E, binary_matrix& D, binary_matrix& A);
 
 // Sets E = A D + X and then alternates the two steps above until neither changes anything.
 // Returns the number of iterations run.
