@@ -8,7 +8,9 @@
 //    the rows that use the atom (:486-506), the change carried into those rows of E (:512-520);
 //  * bsvd.cpp:530-735 update_dictionary_proximus (= :822-1027 _omp, the same text): per atom, rounds of that
 //    vote for the one atom and a vote of every row's coefficient against the atom, until a round changes nothing;
-//  * bsvd.cpp:1220 add(E, X, E) after mul(A, D, E): the word-wise XOR.
+//  * bsvd.cpp:1220 add(E, X, E) after mul(A, D, E): the word-wise XOR;
+//  * bsvd.cpp:99-267 initialize_model_neighbor / _partition / _random_centroids / _random_centroids_xor: D and A
+//    from the data, every atom a vote over its member rows (these mask E's last word: see there).
 //
 // Matrices are in the plane layout (bic.h): row-major u64 words, column j at bit 63 - j % 64 of word
 // j / 64. Distances, weights and XORs run over the mw = ceil(m / 64) whole words of a row, as dist,
@@ -508,6 +510,276 @@ void launch_bsvd_xor(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_
   const uint64_t total = (uint64_t)n * mw;
   const uint32_t grid = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
   if (grid) k_bsvd_xor<<<grid, 256, 0, s>>>(E, e_wpr, X, x_wpr, total, mw);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Model initialisers (bsvd.cpp:99-267; bic.h "model initialisers"). Every atom is a vote over a set of
+// member rows of E, and the atoms are independent: workgroup (k, s) takes atom k and the s-th share of
+// the rows. As in k_bsvd_dict the thread (slot, w) holds word w of the row its slot is at, the rows go
+// kInitAhead at a time so that their loads are in flight together, a member row is added to the
+// bit-sliced carry-save planes (flushed into the workgroup's LDS counts every 31 rows), and the LDS
+// counts go to the atom's global ones with atomicAdd. Who is a member:
+//
+//   kInitNeighbor   the rows that meet the pick row sel[k] (E_j & E_pick != 0 over j < m), each added
+//                   masked with the pick; the threads of a row learn "some word met" from the wave's ballot;
+//   kInitPartition  the rows with the pivot column sel[k] set (k < nsel; the other atoms are stored zero);
+//   kInitCentroids  the rows with sel[j] = k; kInitXor the same, with one XOR word in place of counts;
+//   kInitColw       every row below n (the host passes the sampled row count): the column weights that
+//                   col_weight (binmat.cpp:80-92) sees, left in the counts for k_bsvd_init_rank.
+//
+// E's last word is masked (get_block, binmat.h:188-190). The workgroup that takes the atom's last ticket
+// reads the counts and u back (atomicExch: they are zero again afterwards), forms the atom by the mode's
+// rule and stores its first mw words. No workgroup waits for another.
+// ------------------------------------------------------------------------------------------------
+constexpr int kInitNeighbor = 0, kInitPartition = 1, kInitCentroids = 2, kInitXor = 3, kInitColw = 4;
+constexpr uint32_t kInitAhead = 4;
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_bsvd_init(const uint64_t* __restrict__ E, uint32_t n, uint32_t m, uint32_t mw,
+                                                   uint32_t lg, uint32_t e_wpr, uint64_t* __restrict__ D,
+                                                   uint32_t d_wpr, const uint32_t* __restrict__ sel, uint32_t nsel,
+                                                   uint32_t chunk, uint32_t* cnt, uint32_t* ucnt, uint32_t* tick) {
+  __shared__ uint32_t lcnt[64 * 64];
+  __shared__ uint64_t s_pick[64];  // kInitNeighbor: the pick row, masked; kInitXor: the workgroup's XOR
+  __shared__ uint32_t s_users, s_last, s_u;
+  const uint32_t t = threadIdx.x, lane = lane_id(), wave = wave_id();
+  const uint32_t k = blockIdx.x;
+  const uint32_t w = t & ((1u << lg) - 1u), slot = t >> lg, nslots = 256u >> lg;
+  const bool mine = w < mw;
+  const uint64_t wmask = (w == mw - 1 && (m & 63u)) ? ~0ull << (64 - (m & 63u)) : ~0ull;
+  // what a member is tested against: the atom itself, or the pick row / pivot column the atom was given
+  uint32_t key = k;
+  if constexpr (MODE == kInitNeighbor || MODE == kInitPartition) key = k < nsel ? sel[k] : ~0u;
+  if constexpr (MODE == kInitPartition) {
+    if (k >= nsel) {  // "the other atoms are left uninitialized" (:216): they keep D.clear()'s zero
+      if (blockIdx.y == 0 && t < mw) D[(uint64_t)k * d_wpr + t] = 0ull;
+      return;
+    }
+  }
+  for (uint32_t j = t; j < mw * 64; j += 256) lcnt[j] = 0;
+  if (t < 64) s_pick[t] = 0ull;
+  if (t == 0) s_users = 0;
+  __syncthreads();
+  if constexpr (MODE == kInitNeighbor) {  // (a pick >= n is skipped: no row meets a zero pick, the atom stays zero)
+    if (key < n && slot == 0 && mine) s_pick[w] = E[(uint64_t)key * e_wpr + w] & wmask;
+    __syncthreads();
+  }
+  const uint64_t pick = (MODE == kInitNeighbor && mine) ? s_pick[w] : 0ull;
+  const uint32_t gsh = lane & ~((1u << lg) - 1u);  // the first lane of this row's threads
+  const uint64_t gmask = lg == 6 ? ~0ull : ((1ull << (1u << lg)) - 1ull);
+  const uint64_t r0 = (uint64_t)blockIdx.y * chunk, r1 = r0 + chunk < n ? r0 + chunk : (uint64_t)n;
+  uint64_t pl[kBsvdPlanes];
+#pragma unroll
+  for (int q = 0; q < kBsvdPlanes; ++q) pl[q] = 0;
+  uint64_t xr = 0;
+  uint32_t nacc = 0, users = 0;
+  for (uint64_t base = r0; base < r1; base += (uint64_t)nslots * kInitAhead) {  // (uniform over the workgroup)
+    uint64_t x[kInitAhead];
+    bool mem[kInitAhead];
+#pragma unroll
+    for (uint32_t a = 0; a < kInitAhead; ++a) {
+      const uint64_t j = base + (uint64_t)a * nslots + slot;
+      const bool live = j < r1;
+      x[a] = (live && mine) ? E[j * e_wpr + w] & wmask : 0ull;
+      if constexpr (MODE == kInitNeighbor) x[a] &= pick;
+      if constexpr (MODE == kInitPartition)
+        mem[a] = live && ((E[j * e_wpr + (key >> 6)] >> (63u - (key & 63u))) & 1ull);
+      if constexpr (MODE == kInitCentroids || MODE == kInitXor) mem[a] = live && sel[j] == key;
+      if constexpr (MODE == kInitColw) mem[a] = live;
+    }
+    if constexpr (MODE == kInitNeighbor) {  // (every lane of the wave is here: the ballots come before any branch)
+#pragma unroll
+      for (uint32_t a = 0; a < kInitAhead; ++a)
+        mem[a] = ((__builtin_amdgcn_ballot_w64(x[a] != 0ull) >> gsh) & gmask) != 0ull;
+    }
+#pragma unroll
+    for (uint32_t a = 0; a < kInitAhead; ++a) {
+      if (!mem[a]) continue;
+      if (w == 0) ++users;
+      if (!mine) continue;
+      if constexpr (MODE == kInitXor) {
+        xr ^= x[a];
+      } else {
+        uint64_t carry = x[a];
+#pragma unroll
+        for (int q = 0; q < kBsvdPlanes; ++q) {
+          const uint64_t c2 = pl[q] & carry;
+          pl[q] ^= carry;
+          carry = c2;
+        }
+        if (++nacc == kBsvdFlush) {
+          bsvd_flush(pl, lcnt + w * 64);
+          nacc = 0;
+        }
+      }
+    }
+  }
+  if constexpr (MODE == kInitXor) {
+    if (mine && xr) atomicXor(reinterpret_cast<unsigned long long*>(&s_pick[w]), (unsigned long long)xr);
+  } else {
+    if (mine && nacc) bsvd_flush(pl, lcnt + w * 64);
+  }
+  if (users) atomicAdd(&s_users, users);
+  __syncthreads();
+  if constexpr (MODE == kInitXor) {  // (two u32 halves of the atom's XOR: cnt[2 w], cnt[2 w + 1])
+    auto* gx = reinterpret_cast<unsigned long long*>(cnt) + (uint64_t)k * mw;
+    if (t < mw && s_pick[t]) atomicXor(&gx[t], (unsigned long long)s_pick[t]);
+  } else {
+    uint32_t* gc = cnt + (uint64_t)k * mw * 64;
+    for (uint32_t j = t; j < mw * 64; j += 256)
+      if (lcnt[j]) atomicAdd(&gc[j], lcnt[j]);
+  }
+  if constexpr (MODE == kInitColw) return;  // the counts are the result
+  if (t == 0 && s_users) atomicAdd(&ucnt[k], s_users);
+  __threadfence();
+  __syncthreads();
+  if (t == 0) s_last = atomicAdd(&tick[k], 1u) == gridDim.y - 1 ? 1u : 0u;
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  if (t == 0) {
+    s_u = atomicExch(&ucnt[k], 0u);
+    atomicExch(&tick[k], 0u);
+  }
+  __syncthreads();
+  const uint32_t U = s_u;
+  if constexpr (MODE == kInitXor) {
+    auto* gx = reinterpret_cast<unsigned long long*>(cnt) + (uint64_t)k * mw;
+    if (t < mw) D[(uint64_t)k * d_wpr + t] = atomicExch(&gx[t], 0ull);
+  } else {
+    uint32_t* gc = cnt + (uint64_t)k * mw * 64;
+    for (uint32_t wi = wave; wi < mw; wi += 4) {  // wave-uniform: one word of the atom per wave
+      const uint32_t j = wi * 64 + lane;
+      const uint32_t c = atomicExch(&gc[j], 0u);
+      bool nb;
+      if constexpr (MODE == kInitCentroids) nb = 2u * c >= U;            // :161, a tie sets the bit, U = 0: all ones
+      else if constexpr (MODE == kInitNeighbor) nb = U && c >= U / 2;    // :258-260 (U = 0: a zero or skipped pick)
+      else nb = c >= U / 2;                                             // :214, U <= 1: all ones
+      const uint64_t nw = __builtin_bitreverse64(__builtin_amdgcn_ballot_w64(nb && j < m));
+      if (lane == 0) D[(uint64_t)k * d_wpr + wi] = nw;
+    }
+  }
+}
+
+// A.clear() over the first pw words of every row, and, with sel, A.set(i, sel[i]) (:118, :152); an index >= p is
+// skipped (the row stays zero). One thread per word.
+__global__ __launch_bounds__(256) void k_bsvd_init_coef(uint64_t* __restrict__ A, uint32_t n, uint32_t p, uint32_t pw,
+                                                        uint32_t a_wpr, const uint32_t* __restrict__ sel) {
+  const uint64_t total = (uint64_t)n * pw;
+  for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (uint64_t)gridDim.x * 256) {
+    const uint64_t i = idx / pw;
+    const uint32_t w = (uint32_t)(idx - i * pw);
+    uint64_t v = 0;
+    if (sel) {
+      const uint32_t k = sel[i];
+      if (k < p && (k >> 6) == w) v = BIC_MSB >> (k & 63u);
+    }
+    A[i * a_wpr + w] = v;
+  }
+}
+
+// counting_sort + ranking[m - k - 1] (util.cpp:7-51, bsvd.cpp:195-201): the k-th pivot is the column of rank k
+// by (weight descending, column ascending); one workgroup, every column counts the columns before it.
+__global__ __launch_bounds__(1024) void k_bsvd_init_rank(const uint32_t* __restrict__ colw, uint32_t m,
+                                                         uint32_t* __restrict__ pivots) {
+  __shared__ uint32_t s_w[4096];
+  for (uint32_t c = threadIdx.x; c < m; c += 1024) s_w[c] = colw[c];
+  __syncthreads();
+  for (uint32_t c = threadIdx.x; c < m; c += 1024) {
+    const uint32_t wc = s_w[c];
+    uint32_t rank = 0;
+    for (uint32_t o = 0; o < m; ++o) {
+      const uint32_t wo = s_w[o];
+      rank += (wo > wc || (wo == wc && o < c)) ? 1u : 0u;
+    }
+    pivots[rank] = c;
+  }
+}
+
+// bit 63 - i % 64 of word i / 64: row i of E is non-zero over j < m. One row per lane.
+__global__ __launch_bounds__(256) void k_bsvd_init_nonzero(const uint64_t* __restrict__ E, uint32_t n, uint32_t m,
+                                                           uint32_t mw, uint32_t e_wpr, uint64_t* __restrict__ bitmap) {
+  const uint32_t lane = lane_id(), nwords = (n + 63) / 64;
+  const uint64_t last = (m & 63u) ? ~0ull << (64 - (m & 63u)) : ~0ull;
+  for (uint32_t wv = blockIdx.x * 4 + wave_id(); wv < nwords; wv += gridDim.x * 4) {  // wave-uniform
+    const uint64_t i = (uint64_t)wv * 64 + lane;
+    uint64_t any = 0;
+    if (i < n) {
+      for (uint32_t w = 0; w + 1 < mw; ++w) any |= E[i * e_wpr + w];
+      any |= E[i * e_wpr + mw - 1] & last;
+    }
+    const uint64_t bits = __builtin_bitreverse64(__builtin_amdgcn_ballot_w64(any != 0ull));
+    if (lane == 0) bitmap[wv] = bits;
+  }
+}
+
+namespace {
+struct InitArena {
+  uint32_t *tick, *ucnt, *colw, *pivots, *cnt;
+  size_t zero_bytes;  // the counters from the arena's start
+};
+InitArena init_arena(void* scratch, uint32_t m, uint32_t p) {
+  uint32_t* base = static_cast<uint32_t*>(scratch);
+  const size_t mw = (m + 63) / 64;
+  return {base, base + 4096, base + 2 * 4096, base + 3 * 4096, base + 4 * 4096, (4 * 4096 + (size_t)p * mw * 64) * 4};
+}
+}  // namespace
+
+size_t bsvd_init_scratch_bytes(uint32_t n, uint32_t m, uint32_t p) {
+  // the counters; then what bic_bsvd_initialize keeps: n or p indices, or the bitmap of non-zero rows
+  return init_arena(nullptr, m, p).zero_bytes + (size_t)std::max(n, p) * 4 + 8;
+}
+
+void* bsvd_init_scratch_tail(void* scratch, uint32_t m, uint32_t p) {
+  return static_cast<uint8_t*>(scratch) + init_arena(nullptr, m, p).zero_bytes;
+}
+
+void launch_bsvd_init(hipStream_t s, int mi, const uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, uint64_t* D,
+                      uint32_t p, uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, const uint32_t* sel, void* scratch) {
+  const InitArena ar = init_arena(scratch, m, p);
+  const uint32_t mw = (m + 63) / 64, pw = (p + 63) / 64;
+  uint32_t lg = 0;
+  while ((1u << lg) < mw) ++lg;
+  launch_fill(s, scratch, 0, ar.zero_bytes);
+  const bool cent = mi == kInitCentroids || mi == kInitXor;
+  const uint64_t awords = (uint64_t)n * pw;
+  k_bsvd_init_coef<<<(uint32_t)std::min<uint64_t>((awords + 255) / 256, 4096), 256, 0, s>>>(A, n, p, pw, a_wpr,
+                                                                                          cent ? sel : nullptr);
+  // shares of at least 1,024 rows, about 2,048 workgroups in all (at most 65,535 shares: gridDim.y)
+  auto shares = [&](uint32_t rows, uint32_t atoms, uint32_t* chunk) {
+    const uint32_t want = std::max(1u, std::min((2048u + atoms - 1) / atoms, (rows + 1023u) / 1024u));
+    *chunk = (rows + want - 1) / want;
+    return (rows + *chunk - 1) / *chunk;
+  };
+  uint32_t chunk = 0;
+  if (mi == kInitPartition) {
+    const uint32_t nsamp = (n + mw - 1) / mw, nsel = std::min(p, m);
+    const uint32_t sy = shares(nsamp, 1, &chunk);
+    k_bsvd_init<kInitColw><<<dim3(1, sy), 256, 0, s>>>(E, nsamp, m, mw, lg, e_wpr, D, d_wpr, nullptr, 0, chunk,
+                                                        ar.colw, ar.ucnt, ar.tick);
+    k_bsvd_init_rank<<<1, 1024, 0, s>>>(ar.colw, m, ar.pivots);
+    const uint32_t gy = shares(n, nsel, &chunk);
+    k_bsvd_init<kInitPartition><<<dim3(p, gy), 256, 0, s>>>(E, n, m, mw, lg, e_wpr, D, d_wpr, ar.pivots, nsel, chunk,
+                                                             ar.cnt, ar.ucnt, ar.tick);
+    return;
+  }
+  const uint32_t gy = shares(n, p, &chunk);
+  const dim3 grid(p, gy);
+  if (mi == kInitNeighbor)
+    k_bsvd_init<kInitNeighbor><<<grid, 256, 0, s>>>(E, n, m, mw, lg, e_wpr, D, d_wpr, sel, p, chunk, ar.cnt, ar.ucnt,
+                                                    ar.tick);
+  else if (mi == kInitCentroids)
+    k_bsvd_init<kInitCentroids><<<grid, 256, 0, s>>>(E, n, m, mw, lg, e_wpr, D, d_wpr, sel, p, chunk, ar.cnt, ar.ucnt,
+                                                     ar.tick);
+  else
+    k_bsvd_init<kInitXor><<<grid, 256, 0, s>>>(E, n, m, mw, lg, e_wpr, D, d_wpr, sel, p, chunk, ar.cnt, ar.ucnt,
+                                               ar.tick);
+}
+
+void launch_bsvd_init_nonzero(hipStream_t s, const uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr,
+                              uint64_t* bitmap) {
+  const uint32_t nwords = (n + 63) / 64;
+  k_bsvd_init_nonzero<<<std::min<uint32_t>((nwords + 3) / 4, 2048), 256, 0, s>>>(E, n, m, (m + 63) / 64, e_wpr, bitmap);
 }
 
 }  // namespace bic

@@ -170,6 +170,41 @@ int bsvd_learn(bic_ctx* ctx, int du, const uint64_t* X, size_t x_wpr, uint64_t* 
   return BIC_OK;
 }
 
+// ---- the model initialisers (bsvd.cpp:99-267) ----
+// gsl_rng_rand48: x = (0x5DEECE66D x + 0xB) mod 2^48, the output its upper 32 bits
+constexpr uint64_t kRand48Mask = (1ull << 48) - 1;
+inline uint32_t rand48_next(uint64_t& x) {
+  x = (0x5DEECE66Dull * x + 0xBull) & kRand48Mask;
+  return (uint32_t)(x >> 16);
+}
+// gsl_rng_uniform_int: scale = range / bound, draw until output / scale < bound (a rejected output is used up)
+inline uint32_t rand48_uniform(uint64_t& x, uint32_t bound) {
+  const uint32_t scale = 0xFFFFFFFFu / bound;
+  uint32_t k;
+  do k = rand48_next(x) / scale;
+  while (k >= bound);
+  return k;
+}
+
+// the initialisers' domain: n = 0 is refused (nothing can be initialised from no data)
+bool bsvd_init_geom(const uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D, size_t p, size_t d_wpr,
+                    const uint64_t* A, size_t a_wpr) {
+  return n >= 1 && bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) && E && D && A;
+}
+
+// one explicit entry: the arena, then the launches (no host synchronisation)
+int bsvd_init(bic_ctx* ctx, int mi, const uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p,
+              size_t d_wpr, uint64_t* A, size_t a_wpr, const uint32_t* sel) {
+  int rc = ensure_scratch(ctx, bic::bsvd_init_scratch_bytes((uint32_t)n, (uint32_t)m, (uint32_t)p));
+  if (rc) return rc;
+  timed(ctx, "bsvd_init", [&] {
+    bic::launch_bsvd_init(ctx->cur, mi, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, (uint32_t)p, (uint32_t)d_wpr, A,
+                          (uint32_t)a_wpr, sel, ctx->scratch);
+  });
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -290,6 +325,86 @@ int bic_bsvd_update_dictionary_proximus(bic_ctx* ctx, uint64_t* E, size_t n, siz
   if (rc) return rc;
   if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || (n && (!E || !D || !A))) return BIC_EINVAL;
   return bsvd_prox(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed, nullptr, rounds);
+}
+
+int bic_bsvd_rng_seed(uint64_t seed, uint64_t* state) {
+  if (!state) return BIC_EINVAL;
+  const uint64_t s = seed & 0xFFFFFFFFull;  // gsl_rng_set takes an unsigned long, rand48_set its low 32 bits
+  *state = s ? (s << 16) | 0x330Eull : 0x1234ABCD330Eull;
+  return BIC_OK;
+}
+
+int bic_bsvd_rng_uniform(uint64_t* state, uint32_t bound, size_t count, uint32_t* out) {
+  if (!state || !bound || (count && !out)) return BIC_EINVAL;
+  uint64_t x = *state & kRand48Mask;
+  for (size_t i = 0; i < count; ++i) out[i] = rand48_uniform(x, bound);
+  *state = x;
+  return BIC_OK;
+}
+
+int bic_bsvd_init_neighbor(bic_ctx* ctx, const uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p,
+                           size_t d_wpr, uint64_t* A, size_t a_wpr, const uint32_t* rows) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_init_geom(E, n, m, e_wpr, D, p, d_wpr, A, a_wpr) || !rows) return BIC_EINVAL;
+  return bsvd_init(ctx, BIC_BSVD_MI_NEIGHBOR, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, rows);
+}
+
+int bic_bsvd_init_partition(bic_ctx* ctx, const uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p,
+                            size_t d_wpr, uint64_t* A, size_t a_wpr) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_init_geom(E, n, m, e_wpr, D, p, d_wpr, A, a_wpr)) return BIC_EINVAL;
+  return bsvd_init(ctx, BIC_BSVD_MI_PARTITION, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, nullptr);
+}
+
+int bic_bsvd_init_centroids(bic_ctx* ctx, int mi, const uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D,
+                            size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, const uint32_t* atom_of_row) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if ((mi != BIC_BSVD_MI_CENTROIDS && mi != BIC_BSVD_MI_CENTROIDS_XOR) ||
+      !bsvd_init_geom(E, n, m, e_wpr, D, p, d_wpr, A, a_wpr) || !atom_of_row)
+    return BIC_EINVAL;
+  return bsvd_init(ctx, mi, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, atom_of_row);
+}
+
+int bic_bsvd_initialize(bic_ctx* ctx, int mi, const uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D,
+                        size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* state) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (mi < BIC_BSVD_MI_NEIGHBOR || mi > BIC_BSVD_MI_CENTROIDS_XOR ||
+      !bsvd_init_geom(E, n, m, e_wpr, D, p, d_wpr, A, a_wpr) || (mi != BIC_BSVD_MI_PARTITION && !state))
+    return BIC_EINVAL;
+  if (mi == BIC_BSVD_MI_PARTITION) return bsvd_init(ctx, mi, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, nullptr);
+  // the drawn indices travel through the arena's tail, which the explicit entry leaves alone
+  if ((rc = ensure_scratch(ctx, bic::bsvd_init_scratch_bytes((uint32_t)n, (uint32_t)m, (uint32_t)p)))) return rc;
+  void* tail = bic::bsvd_init_scratch_tail(ctx->scratch, (uint32_t)m, (uint32_t)p);
+  uint64_t x = *state & kRand48Mask;
+  std::vector<uint32_t> sel;
+  if (mi == BIC_BSVD_MI_NEIGHBOR) {
+    std::vector<uint64_t> nz((n + 63) / 64);
+    timed(ctx, "bsvd_init_nonzero", [&] {
+      bic::launch_bsvd_init_nonzero(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr,
+                                    static_cast<uint64_t*>(tail));
+    });
+    BIC_HIP(hipGetLastError());
+    BIC_HIP(hipMemcpyAsync(nz.data(), tail, nz.size() * 8, hipMemcpyDeviceToHost, ctx->cur));
+    BIC_HIP(hipStreamSynchronize(ctx->cur));
+    if (std::all_of(nz.begin(), nz.end(), [](uint64_t w) { return w == 0; })) return BIC_EINVAL;  // (:243 would spin)
+    sel.resize(p);
+    for (size_t k = 0; k < p;) {  // :239-243: a zero row is drawn again and uses up its draw
+      const uint32_t i = rand48_uniform(x, (uint32_t)n);
+      if ((nz[i >> 6] >> (63u - (i & 63u))) & 1ull) sel[k++] = i;
+    }
+  } else {
+    sel.resize(n);
+    for (size_t i = 0; i < n; ++i) sel[i] = rand48_uniform(x, (uint32_t)p);  // :117, :151
+  }
+  *state = x;
+  BIC_HIP(hipMemcpyAsync(tail, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, ctx->cur));
+  if ((rc = bsvd_init(ctx, mi, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, static_cast<const uint32_t*>(tail)))) return rc;
+  BIC_HIP(hipStreamSynchronize(ctx->cur));  // (sel leaves scope: the call blocks)
+  return BIC_OK;
 }
 
 int bic_set_bsvd_rounds(bic_ctx* ctx, unsigned rounds) {

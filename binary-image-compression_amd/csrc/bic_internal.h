@@ -364,6 +364,18 @@ void launch_bsvd_prox_atom(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, u
 void launch_bsvd_prox_coef(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* D,
                            uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, void* scratch, uint32_t k, uint32_t r);
 void launch_bsvd_prox_clear_stall(hipStream_t s, void* scratch);
+// The model initialisers (bsvd.cpp:99-267), mi one of BIC_BSVD_MI_*: A cleared (and set from sel for the two
+// centroid rules), every atom's first ceil(m/64) words written. sel (device): p pick rows (NEIGHBOR), n atom
+// indices (CENTROIDS, CENTROIDS_XOR), unused for PARTITION; an index out of range is skipped, never
+// dereferenced. n >= 1. The arena holds bsvd_init_scratch_bytes: the counters, which the call clears first, and
+// after them (bsvd_init_scratch_tail) room for max(n, p) u32 that bic_bsvd_initialize fills: the indices it
+// draws, before that the bitmap of launch_bsvd_init_nonzero (bit 63 - i % 64 of word i / 64: row i != 0 over j < m).
+size_t bsvd_init_scratch_bytes(uint32_t n, uint32_t m, uint32_t p);
+void* bsvd_init_scratch_tail(void* scratch, uint32_t m, uint32_t p);
+void launch_bsvd_init(hipStream_t s, int mi, const uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, uint64_t* D,
+                      uint32_t p, uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, const uint32_t* sel, void* scratch);
+void launch_bsvd_init_nonzero(hipStream_t s, const uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr,
+                              uint64_t* bitmap);
 
 // The growing-dictionary tile coder of compress2_test.cpp:79-129 / compress3_test.cpp:87-149 (bic_dict.hip).
 // The plane is only read. Everything below `arena` is carved from the scratch by dict_carve, which also

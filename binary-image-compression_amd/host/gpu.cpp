@@ -461,6 +461,27 @@ int Device::bsvd_update_dictionary_proximus(binary_matrix& E, binary_matrix& D, 
   return bsvd_run(3, nullptr, E, D, A, 0, changed, BIC_BSVD_DU_PROXIMUS, rounds);
 }
 
+int Device::bsvd_initialize(int mi, const binary_matrix& E, binary_matrix& D, binary_matrix& A, uint64_t* state) {
+  BIC_TRY(status_);
+  const idx_t n = E.get_rows(), m = E.get_cols(), p = D.get_rows();
+  if (D.get_cols() != m || A.get_rows() != n || A.get_cols() != p) return BIC_EINVAL;
+  if (!n || !p || !E.raw_blocks() || !A.raw_blocks() || !D.raw_blocks()) return BIC_EINVAL;
+  const idx_t ew = E.get_blocks_per_row(), dw = D.get_blocks_per_row(), aw = A.get_blocks_per_row();
+  BIC_TRY(ensure(out_a_, n * ew * 8 + 8));
+  BIC_TRY(ensure(out_b_, p * dw * 8 + 8));
+  BIC_TRY(ensure(aux_, n * aw * 8 + 8));
+  uint64_t* d_E = static_cast<uint64_t*>(out_a_.p);
+  uint64_t* d_D = static_cast<uint64_t*>(out_b_.p);
+  uint64_t* d_A = static_cast<uint64_t*>(aux_.p);
+  BIC_TRY(upload(E, d_E));
+  if (dw > (m + 63) / 64) BIC_TRY(upload(D, d_D));  // (words past a row's own are not written: they come back as sent)
+  if (aw > (p + 63) / 64) BIC_TRY(upload(A, d_A));
+  BIC_TRY(bic_bsvd_initialize(ctx_, mi, d_E, n, m, ew, d_D, p, dw, d_A, aw, state));
+  BIC_TRY(download(d_D, D));  // (waits for the work)
+  BIC_TRY(download(d_A, A));
+  return BIC_OK;
+}
+
 Device& default_device() {
   static Device* dev = new Device(0);
   if (dev->status() != BIC_OK) {
@@ -482,6 +503,38 @@ idx_t bsvd_or_abort(const char* what, int rc, idx_t value) {
   return value;
 }
 }  // namespace
+
+// the reference's process-wide generator (get_rng, bsvd.cpp:8-15): seeded from random_seed at the first draw
+long random_seed = 34503498;
+mi_algorithm_t initialize_model = initialize_model_neighbor;
+
+namespace {
+void bsvd_initialize_or_abort(const char* what, int mi, const binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  static uint64_t state = 0;
+  static bool seeded = false;
+  if (mi != BIC_BSVD_MI_PARTITION && !seeded) {
+    bic_bsvd_rng_seed((uint64_t)random_seed, &state);
+    seeded = true;
+  }
+  bsvd_or_abort(what, bic::default_device().bsvd_initialize(mi, E, D, A, &state), 0);
+}
+}  // namespace
+
+void initialize_model_neighbor(const binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  bsvd_initialize_or_abort("initialize_model_neighbor", BIC_BSVD_MI_NEIGHBOR, E, D, A);
+}
+
+void initialize_model_partition(const binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  bsvd_initialize_or_abort("initialize_model_partition", BIC_BSVD_MI_PARTITION, E, D, A);
+}
+
+void initialize_model_random_centroids(const binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  bsvd_initialize_or_abort("initialize_model_random_centroids", BIC_BSVD_MI_CENTROIDS, E, D, A);
+}
+
+void initialize_model_random_centroids_xor(const binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  bsvd_initialize_or_abort("initialize_model_random_centroids_xor", BIC_BSVD_MI_CENTROIDS_XOR, E, D, A);
+}
 
 idx_t update_coefficients_basic(binary_matrix& E, const binary_matrix& D, binary_matrix& A) {
   idx_t changed = 0;

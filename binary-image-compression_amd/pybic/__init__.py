@@ -35,13 +35,37 @@ EXPORTS = [
     "bic_bsvd_update_coefficients", "bic_bsvd_update_dictionary", "bic_bsvd_learn",
     "bic_dict_encode", "bic_set_dict_block",
     "bic_bsvd_update_dictionary_proximus", "bic_bsvd_learn_du", "bic_set_bsvd_rounds",
+    "bic_bsvd_rng_seed", "bic_bsvd_rng_uniform", "bic_bsvd_init_neighbor", "bic_bsvd_init_partition",
+    "bic_bsvd_init_centroids", "bic_bsvd_initialize",
 ]
 
 # bic_bsvd_learn_du rules (include/bic.h)
 BSVD_DU_STEEPEST, BSVD_DU_PROXIMUS = 0, 1
 
+# bic_bsvd_initialize rules (include/bic.h)
+BSVD_MI_NEIGHBOR, BSVD_MI_PARTITION, BSVD_MI_CENTROIDS, BSVD_MI_CENTROIDS_XOR = 0, 1, 2, 3
+
 # bic_gf2_mul ops (include/bic.h)
 GF2_AB, GF2_ATB, GF2_ABT, GF2_ATBT = 0, 1, 2, 3
+
+
+def bsvd_rng_seed(seed):
+    """gsl_rng_set on gsl_rng_rand48 -> the 48-bit state (host only)"""
+    st = C.c_uint64(0)
+    rc = load().bic_bsvd_rng_seed(seed, C.byref(st))
+    if rc != BIC_OK:
+        raise BicError(rc, "bic_bsvd_rng_seed")
+    return st.value
+
+
+def bsvd_rng_uniform(state, bound, count):
+    """count draws of gsl_rng_uniform_int(bound) from `state` -> (uint32 array, the state afterwards); host only"""
+    st = C.c_uint64(state)
+    out = np.empty(count, np.uint32)
+    rc = load().bic_bsvd_rng_uniform(C.byref(st), bound, count, out.ctypes.data_as(C.c_void_p))
+    if rc != BIC_OK:
+        raise BicError(rc, "bic_bsvd_rng_uniform")
+    return out, st.value
 
 
 class PnmInfo(C.Structure):
@@ -144,6 +168,12 @@ def load(path=LIB_PATH):
     sig("bic_bsvd_update_dictionary_proximus", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp, C.POINTER(sz)])
     sig("bic_bsvd_learn_du", i32, [vp, i32, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
     sig("bic_set_bsvd_rounds", i32, [vp, u32])
+    sig("bic_bsvd_rng_seed", i32, [u64, C.POINTER(u64)])
+    sig("bic_bsvd_rng_uniform", i32, [C.POINTER(u64), C.c_uint32, sz, vp])
+    sig("bic_bsvd_init_neighbor", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
+    sig("bic_bsvd_init_partition", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz])
+    sig("bic_bsvd_init_centroids", i32, [vp, i32, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
+    sig("bic_bsvd_initialize", i32, [vp, i32, vp, sz, sz, sz, vp, sz, sz, vp, sz, C.POINTER(u64)])
     _lib = L
     return L
 
@@ -819,6 +849,36 @@ class Context:
                                                  _p(D), p, D.shape[1], _p(A), A.shape[1], max_iter, C.byref(it)),
                       "bic_bsvd_learn_du")
         return it.value
+
+    def bsvd_init_neighbor(self, E, m, D, A, p, rows):
+        """initialize_model_neighbor from the p pick rows `rows` (device int32): D [p, d_wpr] and A [n, a_wpr]
+        (int64 device tensors) are written from the data E [n, e_wpr]. Enqueues only."""
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_init_neighbor(self.h, _p(E), E.shape[0], m, E.shape[1], _p(D), p, D.shape[1],
+                                                  _p(A), A.shape[1], _p(rows)), "bic_bsvd_init_neighbor")
+
+    def bsvd_init_partition(self, E, m, D, A, p):
+        """initialize_model_partition. Enqueues only."""
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_init_partition(self.h, _p(E), E.shape[0], m, E.shape[1], _p(D), p, D.shape[1],
+                                                   _p(A), A.shape[1]), "bic_bsvd_init_partition")
+
+    def bsvd_init_centroids(self, mi, E, m, D, A, p, atom_of_row):
+        """initialize_model_random_centroids (BSVD_MI_CENTROIDS) or _xor (BSVD_MI_CENTROIDS_XOR) from the n atom
+        indices `atom_of_row` (device int32). Enqueues only."""
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_init_centroids(self.h, mi, _p(E), E.shape[0], m, E.shape[1], _p(D), p, D.shape[1],
+                                                   _p(A), A.shape[1], _p(atom_of_row)), "bic_bsvd_init_centroids")
+
+    def bsvd_initialize(self, mi, E, m, D, A, p, state=None):
+        """the reference's initialize_model call with the rule mi (BSVD_MI_*), drawing on the host from the
+        generator state `state` (bsvd_rng_seed; None only for BSVD_MI_PARTITION) -> the state afterwards."""
+        st = None if state is None else C.c_uint64(state)
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_initialize(self.h, mi, _p(E), E.shape[0], m, E.shape[1], _p(D), p, D.shape[1],
+                                               _p(A), A.shape[1], None if st is None else C.byref(st)),
+                  "bic_bsvd_initialize")
+        return None if st is None else st.value
 
     def pack_streams(self, slots, plane_bits, dst_words=None):
         n, slot_words = slots.shape

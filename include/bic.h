@@ -496,8 +496,8 @@ int bic_gf2_mul(bic_ctx* ctx, int op, const uint64_t* A, size_t a_rows, size_t a
  * per launch) the rows go in chunks. Padding bits are not masked: as the
  * reference's dist, weight and add (binmat.cpp:57-67, 463-512) the kernels run over the first
  * ceil(m/64) whole words of a row; the padding bits of D and A are never changed; words past a
- * row's own (the pitch) are neither read nor written. The caller supplies D and A (the reference's
- * model initialisers are not part of this build).
+ * row's own (the pitch) are neither read nor written. The caller supplies D and A, its own or those
+ * of the model initialisers below (bic_bsvd_initialize).
  *
  * bic_bsvd_update_coefficients = update_coefficients_basic / _omp (bsvd.cpp:399-460, 1029-1107; the
  * same result, rows are independent): for each row i, repeat: w = weight(E_i), d_k = dist(E_i, D_k)
@@ -573,6 +573,77 @@ int bic_bsvd_learn_du(bic_ctx* ctx, int du, const uint64_t* X, size_t x_wpr, uin
                       size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter,
                       size_t* iters);
 int bic_set_bsvd_rounds(bic_ctx* ctx, unsigned rounds);
+
+/* ---- model initialisers (bsvd.cpp:99-267) -----------------------------------------------------
+ * The four rules the reference starts a dictionary from: D (p x m) and A (n x p) are made from the data
+ * E (n x m, const), which the driver passes as E = X before learning (bsvd_test.cpp:114-119).
+ * initialize_model_graph_grow and the file-static initialize_model_random are not built. Layout and
+ * pitches as above. Domain: 1 <= m, p <= 4096, 1 <= n < 2^31, pitches at least the row's words, no null
+ * matrix; anything else is BIC_EINVAL, n = 0 too: nothing can be initialised from no data.
+ *
+ * Padding differs from the steps above: every read of E here is masked at the trailing word, as get(i, j)
+ * with j < m, weight(), bool_and and add are (they go through get_block, binmat.h:188-190), so E's
+ * padding bits are ignored. All four rules start with A.clear() and D.clear(): the first ceil(m/64) words of
+ * every row of D and the first ceil(p/64) words of every row of A are written, with zero padding bits;
+ * words past a row's own (the pitch) are neither read nor written.
+ *
+ * BIC_BSVD_MI_NEIGHBOR (:227-267), bic_bsvd_init_neighbor with rows (DEVICE, p row indices), atom k from
+ * the pick i = rows[k]: N = the rows j, i among them, with E_j & E_i != 0 over columns < m, u = |N|,
+ * s_c = the rows of N with bit c of E_j & E_i set; D(k, c) = (s_c >= u / 2) for c < m, integer division.
+ * So u = 1 gives an all-ones atom (0 >= 0 in every column), u = 2 or 3 gives E_i, and for u >= 2 the atom
+ * lies inside the pick's support. The same row may be picked twice. A stays zero. A pick whose masked
+ * weight is 0 leaves its atom zero (the reference never makes such a pick), and so does an index >= n,
+ * which is skipped, never dereferenced.
+ *
+ * BIC_BSVD_MI_PARTITION (:173-219), bic_bsvd_init_partition: w_c = col_weight(c) as written
+ * (binmat.cpp:80-92): it counts bit c over rows 0 .. ceil(n / ceil(m/64)) - 1 only, all rows only when
+ * m <= 64. The columns are ranked by (w_c descending, c ascending), which is what counting_sort
+ * (util.cpp:7-51) and ranking[m-k-1] yield. For k < min(p, m) the pivot is the k-th ranked column, the
+ * members are ALL rows with E(i, pivot) set, u their number, s_c their count of bit c;
+ * D(k, c) = (s_c >= u / 2), so u = 0 or 1 gives all ones. Atoms k >= m stay zero. A stays zero. No random
+ * numbers are used.
+ *
+ * BIC_BSVD_MI_CENTROIDS (:128-166), bic_bsvd_init_centroids with atom_of_row (DEVICE, n entries < p):
+ * A(i, atom_of_row[i]) = 1; u_k = the rows of atom k, s_kc their count of bit c;
+ * D(k, c) = (2 s_kc >= u_k): a tie sets the bit and an atom without rows is all ones.
+ * BIC_BSVD_MI_CENTROIDS_XOR (:99-126): the same A; D_k = the XOR of the masked rows of atom k, an atom
+ * without rows is zero. An entry >= p is skipped: its row of A stays zero and it joins no atom.
+ *
+ * The three explicit entries only enqueue device work on the ctx stream: a fixed number of launches
+ * whatever n and p (the rows are walked in shares), no host synchronisation, no workgroup ever waits for
+ * another. Their counters live in the ctx scratch and are cleared by the call itself; the scratch is
+ * sized on first use, as for bic_bsvd_update_dictionary.
+ *
+ * The generator is GSL's gsl_rng_rand48, the Unix rand48 sequence, with its state explicit (the
+ * reference keeps one per process, seeded with random_seed = 34503498 on first use). bic_bsvd_rng_seed
+ * (host only): state = (s << 16) | 0x330E with s the low 32 bits of seed, 0x1234ABCD330E for s = 0. One
+ * output: state = (0x5DEECE66D state + 0xB) mod 2^48, the output is state >> 16. bic_bsvd_rng_uniform
+ * (host only) is gsl_rng_uniform_int, count times: scale = 0xFFFFFFFF / bound, k = output / scale is drawn
+ * until k < bound, and a rejected output is used up; out (HOST) receives count values; bound = 0, a
+ * null state or a null out with count > 0 is BIC_EINVAL.
+ *
+ * bic_bsvd_initialize is the reference's call: it draws on the host from *state (HOST, in and out; may
+ * be NULL for PARTITION, otherwise NULL is BIC_EINVAL), uploads what it drew and runs the explicit
+ * entry. NEIGHBOR: one kernel writes the bitmap "row is non-zero over j < m" into the ctx scratch, the
+ * host reads its n / 8 bytes back and draws p picks with bic_bsvd_rng_uniform's rule and bound n, where
+ * a zero row is drawn again and uses up its draw (:243); if no row is non-zero it returns BIC_EINVAL
+ * with *state unchanged (the reference would loop forever). CENTROIDS and CENTROIDS_XOR: n draws with
+ * bound p, in row order. NEIGHBOR and both CENTROIDS kinds block: they return after the work has
+ * completed and cannot be stream-captured. PARTITION does not block. Any other mi is BIC_EINVAL. */
+#define BIC_BSVD_MI_NEIGHBOR 0
+#define BIC_BSVD_MI_PARTITION 1
+#define BIC_BSVD_MI_CENTROIDS 2
+#define BIC_BSVD_MI_CENTROIDS_XOR 3
+int bic_bsvd_rng_seed(uint64_t seed, uint64_t* state);
+int bic_bsvd_rng_uniform(uint64_t* state, uint32_t bound, size_t count, uint32_t* out);
+int bic_bsvd_init_neighbor(bic_ctx* ctx, const uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p,
+                           size_t d_wpr, uint64_t* A, size_t a_wpr, const uint32_t* rows);
+int bic_bsvd_init_partition(bic_ctx* ctx, const uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p,
+                            size_t d_wpr, uint64_t* A, size_t a_wpr);
+int bic_bsvd_init_centroids(bic_ctx* ctx, int mi, const uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D,
+                            size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, const uint32_t* atom_of_row);
+int bic_bsvd_initialize(bic_ctx* ctx, int mi, const uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D,
+                        size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* state);
 
 /* ---- kernel timing ------------------------------------------------------------------------
  * When enabled, every kernel launch of this ctx is bracketed by HIP events on the launch stream.

@@ -144,6 +144,10 @@ class Device {
                                       idx_t* rounds = nullptr);
   int bsvd_learn(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A, int du, size_t max_iter = 0,
                  idx_t* iters = nullptr);
+  // bsvd.cpp:99-267, the model initialisers (bic.h "model initialisers"): E is uploaded, D and A are made on the
+  // device by the rule mi (BIC_BSVD_MI_*) and downloaded. state: the generator's state (bic_bsvd_rng_seed), read
+  // and advanced by the rules that draw; may be null for BIC_BSVD_MI_PARTITION. E needs at least one row.
+  int bsvd_initialize(int mi, const binary_matrix& E, binary_matrix& D, binary_matrix& A, uint64_t* state);
 
  private:
   struct Buf {

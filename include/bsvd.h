@@ -1,18 +1,40 @@
 // bsvd.h -- the part of the reference's binary dictionary learning API that this build implements,
-// with the reference's signatures, so code written against it links: the greedy sparse-coding step,
-// the majority-vote dictionary step and the loop that alternates them. Each function hands its
-// matrices to bic::default_device() (bic_gpu.h), which runs the step in the HIP kernels behind bic.h
-// and copies the results back; a failing device call prints its reason and aborts, as med() does.
+// with the reference's signatures, so code written against it links: four model initialisers, the
+// greedy sparse-coding step, the two dictionary steps and the loop that alternates them. Each function
+// hands its matrices to bic::default_device() (bic_gpu.h), which runs the step in the HIP kernels behind
+// bic.h and copies the results back; a failing device call prints its reason and aborts, as med() does.
 //
 // The model is X = A D + E over GF(2): X (n x m) holds one sample per row, D (p x m) one atom per
 // row, A (n x p) says which atoms a sample uses and E (n x m) is what they leave unexplained.
-// m and p are limited to 1 .. 4096 here. The caller fills D and A; the reference's model
-// initialisers, its role-switching learners and its model-order searches are not part of this build
-// (DESIGN.md lists them).
+// m and p are limited to 1 .. 4096 here. A model is started as the reference's driver does it: E = X,
+// initialize_model(E, D, A), then learn_model_traditional(X, E, D, A). The reference's
+// initialize_model_graph_grow, learn_model_setup and its catalogs, its role-switching learners and its
+// model-order searches are not part of this build (DESIGN.md lists them).
 #ifndef BSVD_H
 #define BSVD_H
 
 #include "binmat.h"
+
+// The model initialisers: D and A are cleared and then made from the data E, which needs at least one
+// row; E's padding bits are ignored. The three that draw share one process-wide generator (GSL's rand48
+// sequence), seeded from random_seed at the first draw, so consecutive calls continue one sequence.
+//
+// neighbor: every atom is the centroid of the rows that share a set bit with a randomly picked non-zero
+// row (a bit is set where at least half, integer half, of those rows have it in common with the pick);
+// aborts when E has no non-zero row, where the reference would not return. A stays zero.
+void initialize_model_neighbor(const binary_matrix& E, binary_matrix& D, binary_matrix& A);
+// partition: atom k is the centroid of the rows that have the k-th heaviest column set (column weights as
+// the reference's col_weight samples them); atoms past the number of columns stay zero. A stays zero.
+void initialize_model_partition(const binary_matrix& E, binary_matrix& D, binary_matrix& A);
+// random centroids: every row is assigned to a random atom (its coefficient in A is set) and every atom is
+// the majority of its rows, a tie setting the bit and an atom without rows being all ones.
+void initialize_model_random_centroids(const binary_matrix& E, binary_matrix& D, binary_matrix& A);
+// the same assignment; every atom is the XOR of its rows, an atom without rows zero.
+void initialize_model_random_centroids_xor(const binary_matrix& E, binary_matrix& D, binary_matrix& A);
+
+typedef void (*mi_algorithm_t)(const binary_matrix& E, binary_matrix& D, binary_matrix& A);
+extern mi_algorithm_t initialize_model;  // initialize_model_neighbor unless assigned
+extern long random_seed;                 // 34503498; read once, at the first draw
 
 // For every row of E: take the atom nearest to it (the first such atom in D's order) while doing
 // so lowers the row's weight, toggling that atom's coefficient in A each time. E and A are updated
