@@ -10,38 +10,55 @@ bool gf2_geom(size_t rows, size_t cols, size_t wpr) {
   return rows <= 0x7fffffffu && cols <= 0x7fffff00u && wpr >= (cols + 63) / 64 && wpr <= 0xffffffffu;
 }
 
-// E (n x m), D (p x m), A (n x p): the domain and the pitches
-bool bsvd_geom(size_t n, size_t m, size_t e_wpr, size_t p, size_t d_wpr, size_t a_wpr) {
-  if (m < 1 || m > 4096 || p < 1 || p > 4096 || n > 0x7fffffffu) return false;
+// E (n x m), D (p x m), A (n x p): the domain and the pitches. A row of the narrow kernels (bic_bsvd.hip) has at
+// most kBsvdNarrow bits, one of the wide ones (bic_bsvd_wide.hip) at most kBsvdWide.
+constexpr size_t kBsvdNarrow = 4096, kBsvdWide = 1048576;
+bool bsvd_geom(size_t n, size_t m, size_t e_wpr, size_t p, size_t d_wpr, size_t a_wpr, size_t max_m = kBsvdNarrow) {
+  if (m < 1 || m > max_m || p < 1 || p > 4096 || n > 0x7fffffffu) return false;
   const size_t mw = (m + 63) / 64, pw = (p + 63) / 64;
   return e_wpr >= mw && d_wpr >= mw && a_wpr >= pw && e_wpr <= 0xffffffffu && d_wpr <= 0xffffffffu &&
          a_wpr <= 0xffffffffu;
 }
 
-// the two steps without their argument checks; `changed` a device u64 that is written
+// the two steps without their argument checks; `changed` a device u64 that is written; wide: the kernels of
+// bic_bsvd_wide.hip (any m of the wide domain), otherwise those of bic_bsvd.hip (m <= kBsvdNarrow)
 int bsvd_coef(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D, size_t p, size_t d_wpr,
-              uint64_t* A, size_t a_wpr, uint64_t* changed) {
-  timed(ctx, "bsvd_coef", [&] {
+              uint64_t* A, size_t a_wpr, uint64_t* changed, bool wide = false) {
+  timed(ctx, wide ? "bsvd_wide_coef" : "bsvd_coef", [&] {
     if (changed) bic::launch_fill(ctx->cur, changed, 0, 8);
     if (n)
-      bic::launch_bsvd_coef(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, (uint32_t)p, (uint32_t)d_wpr, A,
-                            (uint32_t)a_wpr, changed);
+      (wide ? bic::launch_bsvd_wide_coef : bic::launch_bsvd_coef)(ctx->cur, E, (uint32_t)n, (uint32_t)m,
+                                                                  (uint32_t)e_wpr, D, (uint32_t)p, (uint32_t)d_wpr, A,
+                                                                  (uint32_t)a_wpr, changed);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
 }
 
 int bsvd_dict(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr,
-              const uint64_t* A, size_t a_wpr, uint64_t* changed) {
+              const uint64_t* A, size_t a_wpr, uint64_t* changed, bool wide = false) {
   if (!n) {
     if (changed) bic::launch_fill(ctx->cur, changed, 0, 8);
     BIC_HIP(hipGetLastError());
     return BIC_OK;
   }
-  int rc = ensure_scratch(ctx, bic::bsvd_dict_scratch_bytes((uint32_t)n, (uint32_t)p));
+  int rc = ensure_scratch(ctx, bic::bsvd_wide_scratch_bytes((uint32_t)n, (uint32_t)p));
   if (rc) return rc;
   uint8_t* arena = static_cast<uint8_t*>(ctx->scratch);
   if (!changed) changed = reinterpret_cast<uint64_t*>(arena + bic::kBsvdDictCounts + 16);
+  if (wide) {  // every column chunk walks the p atoms by itself: one launch, and one that counts the flags
+    timed(ctx, "bsvd_dict_prepare", [&] {
+      bic::launch_fill(ctx->cur, changed, 0, 8);
+      bic::launch_bsvd_wide_prepare(ctx->cur, (uint32_t)n, (uint32_t)p, A, (uint32_t)a_wpr, ctx->scratch);
+    });
+    BIC_HIP(hipGetLastError());
+    timed(ctx, "bsvd_wide_dict", [&] {
+      bic::launch_bsvd_wide_dict(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, (uint32_t)p,
+                                 (uint32_t)d_wpr, ctx->scratch, changed);
+    });
+    BIC_HIP(hipGetLastError());
+    return BIC_OK;
+  }
   timed(ctx, "bsvd_dict_prepare", [&] {
     bic::launch_fill(ctx->cur, changed, 0, 8);
     bic::launch_bsvd_dict_prepare(ctx->cur, (uint32_t)n, (uint32_t)p, A, (uint32_t)a_wpr, ctx->scratch);
@@ -74,7 +91,7 @@ int bsvd_dict(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint6
 constexpr unsigned kBsvdProxAutoRounds = 2;
 
 int bsvd_prox(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr,
-              uint64_t* A, size_t a_wpr, uint64_t* changed, uint64_t* h_changed, size_t* rounds) {
+              uint64_t* A, size_t a_wpr, uint64_t* changed, uint64_t* h_changed, size_t* rounds, bool wide = false) {
   if (h_changed) *h_changed = 0;
   if (rounds) *rounds = 0;
   if (!n) {
@@ -83,16 +100,17 @@ int bsvd_prox(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint6
     BIC_HIP(hipStreamSynchronize(ctx->cur));
     return BIC_OK;
   }
-  int rc = ensure_scratch(ctx, bic::bsvd_dict_scratch_bytes((uint32_t)n, (uint32_t)p));
+  int rc = ensure_scratch(ctx, bic::bsvd_wide_scratch_bytes((uint32_t)n, (uint32_t)p));
   if (rc) return rc;
   timed(ctx, "bsvd_dict_prepare",
         [&] { bic::launch_bsvd_dict_prepare(ctx->cur, (uint32_t)n, (uint32_t)p, A, (uint32_t)a_wpr, ctx->scratch); });
   BIC_HIP(hipGetLastError());
   const uint32_t budget = ctx->bsvd_rounds ? ctx->bsvd_rounds : kBsvdProxAutoRounds, np = (uint32_t)p;
   auto atom = [&](uint32_t k, uint32_t r, bool check_prev, bool fresh) {
-    timed(ctx, "bsvd_prox_atom", [&] {
-      bic::launch_bsvd_prox_atom(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, np, (uint32_t)d_wpr,
-                                 ctx->scratch, k, r, budget, check_prev, fresh);
+    timed(ctx, wide ? "bsvd_wide_prox_atom" : "bsvd_prox_atom", [&] {
+      (wide ? bic::launch_bsvd_wide_prox_atom : bic::launch_bsvd_prox_atom)(
+          ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, np, (uint32_t)d_wpr, ctx->scratch, k, r, budget,
+          check_prev, fresh);
     });
   };
   uint8_t* arena = static_cast<uint8_t*>(ctx->scratch);
@@ -101,9 +119,10 @@ int bsvd_prox(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint6
     for (uint32_t k = k0; k < np; ++k)
       for (uint32_t r = 0; r < budget; ++r) {
         atom(k, r, r == 0 && k > k0, r == 0 && !(resumed && k == k0));
-        timed(ctx, "bsvd_prox_coef", [&] {
-          bic::launch_bsvd_prox_coef(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, (uint32_t)d_wpr, A,
-                                     (uint32_t)a_wpr, ctx->scratch, k, r);
+        timed(ctx, wide ? "bsvd_wide_prox_coef" : "bsvd_prox_coef", [&] {
+          (wide ? bic::launch_bsvd_wide_prox_coef : bic::launch_bsvd_prox_coef)(
+              ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, D, (uint32_t)d_wpr, A, (uint32_t)a_wpr,
+              ctx->scratch, k, r);
         });
       }
     atom(np, 0, true, false);  // the last atom's stall
@@ -127,17 +146,17 @@ int bsvd_prox(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint6
   return BIC_OK;
 }
 
-// learn_model_traditional (bsvd.cpp:1215-1244) with either dictionary rule: E = A D ^ X, then the two steps
-// until neither changes anything. The counts are read back every iteration: the call blocks.
-int bsvd_learn(bic_ctx* ctx, int du, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m, size_t e_wpr,
-               uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter, size_t* iters) {
-  int rc = bind(ctx);
-  if (rc) return rc;
-  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || x_wpr < (m + 63) / 64 || x_wpr > 0xffffffffu ||
-      (n && (!X || !E || !D || !A)))
-    return BIC_EINVAL;
-  if (iters) *iters = 0;
-  // mul_AB as bic_gf2_mul launches it, in chunks of the rows one launch's grid can hold
+// What the learners share. The arena's head is the dictionary step's (sized once for the largest step of
+// the call, so that no step's own ensure_scratch moves it); the counts live in it at kBsvdDictCounts.
+struct BsvdMat {
+  uint64_t* w;
+  size_t rows, cols, wpr;
+};
+
+// mul(A, false, D, false, E); add(E, X, E) (bsvd.cpp:1219-1220): mul_AB as bic_gf2_mul launches it, in chunks of
+// the rows one launch's grid can hold
+int bsvd_residual(bic_ctx* ctx, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m, size_t e_wpr,
+                  const uint64_t* D, size_t p, size_t d_wpr, const uint64_t* A, size_t a_wpr) {
   const uint32_t mw = (uint32_t)((m + 63) / 64);
   timed(ctx, "gf2_mul", [&] {
     for (size_t r0 = 0; r0 < n; r0 += bic::kGf2MaxRows)
@@ -148,25 +167,153 @@ int bsvd_learn(bic_ctx* ctx, int du, const uint64_t* X, size_t x_wpr, uint64_t* 
     bic::launch_bsvd_xor(ctx->cur, E, (uint32_t)n, (uint32_t)m, (uint32_t)e_wpr, X, (uint32_t)x_wpr);
   });
   BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
+// update_coefficients(E, D, A) if `coef`, then update_dictionary(E, D, A) by the rule du; each by the narrow
+// kernels where E's rows have at most kBsvdNarrow bits, by the wide ones above. The two counts are read back:
+// the call blocks.
+int bsvd_pass(bic_ctx* ctx, int du, bool coef, const BsvdMat& E, const BsvdMat& D, const BsvdMat& A, uint64_t* h_coef,
+              uint64_t* h_dict) {
+  const size_t n = E.rows, m = E.cols, p = D.rows;
+  const bool wide = m > kBsvdNarrow;
+  uint64_t* counts = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->scratch) + bic::kBsvdDictCounts);
+  int rc;
+  uint64_t h[2] = {0, 0};
+  if (coef && (rc = bsvd_coef(ctx, E.w, n, m, E.wpr, D.w, p, D.wpr, A.w, A.wpr, counts, wide))) return rc;
+  if (du == BIC_BSVD_DU_PROXIMUS) {  // (blocks itself; the sparse-coding count is read after it)
+    if ((rc = bsvd_prox(ctx, E.w, n, m, E.wpr, D.w, p, D.wpr, A.w, A.wpr, nullptr, &h[1], nullptr, wide))) return rc;
+    if (coef) BIC_HIP(hipMemcpyAsync(h, counts, 8, hipMemcpyDeviceToHost, ctx->cur));
+  } else {
+    if ((rc = bsvd_dict(ctx, E.w, n, m, E.wpr, D.w, p, D.wpr, A.w, A.wpr, counts + 1, wide))) return rc;
+    if (coef) BIC_HIP(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, ctx->cur));
+    else BIC_HIP(hipMemcpyAsync(h + 1, counts + 1, 8, hipMemcpyDeviceToHost, ctx->cur));
+  }
+  BIC_HIP(hipStreamSynchronize(ctx->cur));
+  *h_coef = h[0];
+  *h_dict = h[1];
+  return BIC_OK;
+}
+
+// learn_model_traditional (bsvd.cpp:1215-1244) with either dictionary rule: E = A D ^ X, then the two steps
+// until neither changes anything. The counts are read back every iteration: the call blocks.
+int bsvd_learn(bic_ctx* ctx, int du, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m, size_t e_wpr,
+               uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter, size_t* iters,
+               size_t max_m = kBsvdNarrow) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr, max_m) || x_wpr < (m + 63) / 64 || x_wpr > 0xffffffffu ||
+      (n && (!X || !E || !D || !A)))
+    return BIC_EINVAL;
+  if (iters) *iters = 0;
+  if ((rc = bsvd_residual(ctx, X, x_wpr, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr))) return rc;
   // the counts live in the dictionary step's arena, which is sized here once (n = 0 still needs them)
-  if ((rc = ensure_scratch(ctx, bic::bsvd_dict_scratch_bytes((uint32_t)n, (uint32_t)p)))) return rc;
+  if ((rc = ensure_scratch(ctx, bic::bsvd_wide_scratch_bytes((uint32_t)n, (uint32_t)p)))) return rc;
+  const BsvdMat Em{E, n, m, e_wpr}, Dm{D, p, m, d_wpr}, Am{A, n, p, a_wpr};
   size_t it = 0;
   for (;;) {
     ++it;
-    uint64_t* counts = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->scratch) + bic::kBsvdDictCounts);
-    if ((rc = bsvd_coef(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, counts))) return rc;
-    uint64_t h[2] = {0, 0};
-    if (du == BIC_BSVD_DU_PROXIMUS) {  // (blocks itself; the sparse-coding count is read after it)
-      if ((rc = bsvd_prox(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, nullptr, &h[1], nullptr))) return rc;
-      BIC_HIP(hipMemcpyAsync(h, counts, 8, hipMemcpyDeviceToHost, ctx->cur));
-    } else {
-      if ((rc = bsvd_dict(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, counts + 1))) return rc;
-      BIC_HIP(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, ctx->cur));
-    }
-    BIC_HIP(hipStreamSynchronize(ctx->cur));
-    if (h[0] + h[1] == 0 || (max_iter && it >= max_iter)) break;
+    uint64_t hc = 0, hd = 0;
+    if ((rc = bsvd_pass(ctx, du, true, Em, Dm, Am, &hc, &hd))) return rc;
+    if (hc + hd == 0 || (max_iter && it >= max_iter)) break;
   }
   if (iters) *iters = it;
+  return BIC_OK;
+}
+
+// B (rows x cols) -> T (cols x rows), T's padding bits zero (transpose_to, binmat.cpp:199-208); words of T past
+// ceil(rows / 64) are not touched
+void bsvd_transpose(bic_ctx* ctx, const BsvdMat& B, const BsvdMat& T) {
+  timed(ctx, "gf2_transpose", [&] {
+    bic::launch_gf2_transpose(ctx->cur, B.w, (uint32_t)B.rows, (uint32_t)B.wpr, (uint32_t)((B.cols + 63) / 64),
+                              (uint32_t)B.cols, T.w, (uint32_t)T.wpr, (uint32_t)((B.rows + 63) / 64));
+  });
+}
+
+// learn_model_alter1 / 2 / 3 (bsvd.cpp:1247-1434) as written. In the exchanged role the calls are
+// update_coefficients(Et, At, Dt) and update_dictionary(Et, At, Dt): Et (m x n) the residual, At's p rows of n
+// bits the atoms, Dt (m x p) the coefficients. Et, At and Dt live in the arena after the steps' own part.
+// max_iter counts every iter++ of the text over the whole call; a pass that reaches it is finished (with its
+// transposes back) and the call returns.
+int bsvd_learn_alter(bic_ctx* ctx, int lm, int du, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m,
+                     size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter,
+                     size_t* iters) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr, kBsvdWide) || n < 1 || n > kBsvdWide || x_wpr < (m + 63) / 64 ||
+      x_wpr > 0xffffffffu || !X || !E || !D || !A)
+    return BIC_EINVAL;
+  if (iters) *iters = 0;
+  const size_t nw = (n + 63) / 64, pw = (p + 63) / 64;
+  const size_t head = (std::max(bic::bsvd_wide_scratch_bytes((uint32_t)n, (uint32_t)p),
+                                bic::bsvd_wide_scratch_bytes((uint32_t)m, (uint32_t)p)) + 255) & ~(size_t)255;
+  if ((rc = ensure_scratch(ctx, head + (m * nw + p * nw + m * pw) * 8))) return rc;
+  uint64_t* tw = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->scratch) + head);
+  const BsvdMat Em{E, n, m, e_wpr}, Dm{D, p, m, d_wpr}, Am{A, n, p, a_wpr};
+  const BsvdMat Et{tw, m, n, nw}, At{tw + m * nw, p, n, nw}, Dt{tw + m * nw + p * nw, m, p, pw};
+  auto there = [&] {  // A.transpose_to(At); D.transpose_to(Dt); E.transpose_to(Et)
+    bsvd_transpose(ctx, Am, At);
+    bsvd_transpose(ctx, Dm, Dt);
+    bsvd_transpose(ctx, Em, Et);
+  };
+  auto back = [&] {
+    bsvd_transpose(ctx, At, Am);
+    bsvd_transpose(ctx, Dt, Dm);
+    bsvd_transpose(ctx, Et, Em);
+  };
+  if ((rc = bsvd_residual(ctx, X, x_wpr, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr))) return rc;
+  size_t total = 0, iter = 0;
+  uint64_t hc = 0, hd = 0, changed = 1;
+  auto capped = [&] { return max_iter && total >= max_iter; };
+  if (lm == BIC_BSVD_LM_ALTER1) {
+    while (changed > 0) {  // :1271
+      ++iter, ++total;
+      if ((rc = bsvd_pass(ctx, du, true, Em, Dm, Am, &hc, &hd))) return rc;  // (its sum is overwritten below)
+      there();
+      if ((rc = bsvd_pass(ctx, du, true, Et, At, Dt, &hc, &hd))) return rc;
+      changed = hd;  // :1297: the transposed dictionary step alone
+      back();
+      if (capped()) break;
+    }
+  } else if (lm == BIC_BSVD_LM_ALTER2) {
+    uint64_t outer = 1;
+    bool stop = false;
+    while (outer > 0 && !stop) {  // :1337
+      outer = 0;
+      while (changed > 0) {  // :1339 (not reset for a second outer pass: skipped there)
+        ++iter, ++total;
+        if ((rc = bsvd_pass(ctx, du, true, Em, Dm, Am, &hc, &hd))) return rc;
+        changed = hc + hd;
+        outer += changed;
+        if ((stop = capped())) break;
+      }
+      if (stop) break;
+      there();
+      changed = 1;
+      iter = 0;  // :1359
+      while (changed > 0) {  // :1360
+        ++iter, ++total;
+        if ((rc = bsvd_pass(ctx, du, true, Et, At, Dt, &hc, &hd))) return rc;
+        changed = hc + hd;
+        outer += changed;
+        if ((stop = capped())) break;
+      }
+      back();
+    }
+  } else {
+    while (changed > 0) {  // :1408
+      ++iter, ++total;
+      there();
+      if ((rc = bsvd_pass(ctx, du, false, Et, At, Dt, &hc, &hd))) return rc;
+      back();
+      if ((rc = bsvd_pass(ctx, du, false, Em, Dm, Am, &hc, &hd))) return rc;
+      changed = hd;  // :1423: only the direct step decides
+      if (capped()) break;
+    }
+  }
+  BIC_HIP(hipGetLastError());
+  BIC_HIP(hipStreamSynchronize(ctx->cur));
+  if (iters) *iters = iter;
   return BIC_OK;
 }
 
@@ -325,6 +472,38 @@ int bic_bsvd_update_dictionary_proximus(bic_ctx* ctx, uint64_t* E, size_t n, siz
   if (rc) return rc;
   if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr) || (n && (!E || !D || !A))) return BIC_EINVAL;
   return bsvd_prox(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed, nullptr, rounds);
+}
+
+int bic_bsvd_update_coefficients_wide(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D,
+                                      size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* changed) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (!bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr, kBsvdWide) || (n && (!E || !D || !A))) return BIC_EINVAL;
+  return bsvd_coef(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed, true);
+}
+
+int bic_bsvd_update_dictionary_wide(bic_ctx* ctx, int du, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D,
+                                    size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* changed,
+                                    size_t* rounds) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if ((du != BIC_BSVD_DU_STEEPEST && du != BIC_BSVD_DU_PROXIMUS) ||
+      !bsvd_geom(n, m, e_wpr, p, d_wpr, a_wpr, kBsvdWide) || (n && (!E || !D || !A)))
+    return BIC_EINVAL;
+  if (du == BIC_BSVD_DU_PROXIMUS)
+    return bsvd_prox(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed, nullptr, rounds, true);
+  if (!n && rounds) *rounds = 0;
+  return bsvd_dict(ctx, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, changed, true);
+}
+
+int bic_bsvd_learn_lm(bic_ctx* ctx, int lm, int du, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m,
+                      size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter,
+                      size_t* iters) {
+  if (du != BIC_BSVD_DU_STEEPEST && du != BIC_BSVD_DU_PROXIMUS) return BIC_EINVAL;
+  if (lm == BIC_BSVD_LM_TRADITIONAL)
+    return bsvd_learn(ctx, du, X, x_wpr, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, max_iter, iters, kBsvdWide);
+  if (lm != BIC_BSVD_LM_ALTER1 && lm != BIC_BSVD_LM_ALTER2 && lm != BIC_BSVD_LM_ALTER3) return BIC_EINVAL;
+  return bsvd_learn_alter(ctx, lm, du, X, x_wpr, E, n, m, e_wpr, D, p, d_wpr, A, a_wpr, max_iter, iters);
 }
 
 int bic_bsvd_rng_seed(uint64_t seed, uint64_t* state) {

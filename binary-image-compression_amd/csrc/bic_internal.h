@@ -376,6 +376,22 @@ void launch_bsvd_init(hipStream_t s, int mi, const uint64_t* E, uint32_t n, uint
                       uint32_t p, uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, const uint32_t* sel, void* scratch);
 void launch_bsvd_init_nonzero(hipStream_t s, const uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr,
                               uint64_t* bitmap);
+// The same three steps for rows of any width, m in 1 .. 1,048,576 (bic_bsvd_wide.hip), with the narrow
+// launchers' arguments. The arena is the narrow dictionary update's plus a flag per atom
+// (bsvd_wide_scratch_bytes); launch_bsvd_wide_prepare stands for launch_bsvd_dict_prepare, and
+// launch_bsvd_wide_dict walks all p atoms and adds the atoms changed to *changed (not null). n >= 1.
+size_t bsvd_wide_scratch_bytes(uint32_t n, uint32_t p);
+void launch_bsvd_wide_coef(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* D,
+                           uint32_t p, uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, uint64_t* changed);
+void launch_bsvd_wide_prepare(hipStream_t s, uint32_t n, uint32_t p, const uint64_t* A, uint32_t a_wpr,
+                              void* scratch);
+void launch_bsvd_wide_dict(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, uint64_t* D,
+                           uint32_t p, uint32_t d_wpr, void* scratch, uint64_t* changed);
+void launch_bsvd_wide_prox_atom(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, uint64_t* D,
+                                uint32_t p, uint32_t d_wpr, void* scratch, uint32_t k, uint32_t r, uint32_t budget,
+                                bool check_prev, bool fresh);
+void launch_bsvd_wide_prox_coef(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* D,
+                                uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, void* scratch, uint32_t k, uint32_t r);
 
 // The growing-dictionary tile coder of compress2_test.cpp:79-129 / compress3_test.cpp:87-149 (bic_dict.hip).
 // The plane is only read. Everything below `arena` is carved from the scratch by dict_carve, which also

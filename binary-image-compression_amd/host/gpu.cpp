@@ -396,7 +396,7 @@ int Device::dict_encode(const binary_matrix& I, int variant, unsigned W, unsigne
 }
 
 int Device::bsvd_run(int step, const binary_matrix* X, binary_matrix& E, binary_matrix& D, binary_matrix& A,
-                     size_t max_iter, idx_t* result, int du, idx_t* rounds) {
+                     size_t max_iter, idx_t* result, int du, idx_t* rounds, int lm) {
   BIC_TRY(status_);
   const idx_t n = E.get_rows(), m = E.get_cols(), p = D.get_rows();
   if (D.get_cols() != m || A.get_rows() != n || A.get_cols() != p || (X && !same_shape(*X, E))) return BIC_EINVAL;
@@ -415,19 +415,30 @@ int Device::bsvd_run(int step, const binary_matrix* X, binary_matrix& E, binary_
   BIC_TRY(upload(D, d_D));
   BIC_TRY(upload(A, d_A));
   uint64_t res = 0;
+  const bool wide = m > 4096;  // the narrow entries' domain ends there: the wide ones give the same results
   if (step == 2) {
     uint64_t* d_X = static_cast<uint64_t*>(in_.p);
     BIC_TRY(upload(*X, d_X));
     size_t it = 0;
-    BIC_TRY(bic_bsvd_learn_du(ctx_, du, d_X, ew, d_E, n, m, ew, d_D, p, dw, d_A, aw, max_iter, &it));
+    if (wide || lm != BIC_BSVD_LM_TRADITIONAL)
+      BIC_TRY(bic_bsvd_learn_lm(ctx_, lm, du, d_X, ew, d_E, n, m, ew, d_D, p, dw, d_A, aw, max_iter, &it));
+    else
+      BIC_TRY(bic_bsvd_learn_du(ctx_, du, d_X, ew, d_E, n, m, ew, d_D, p, dw, d_A, aw, max_iter, &it));
     res = it;
   } else if (step == 3) {
     size_t r = 0;
-    BIC_TRY(bic_bsvd_update_dictionary_proximus(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch, &r));
+    if (wide)
+      BIC_TRY(bic_bsvd_update_dictionary_wide(ctx_, BIC_BSVD_DU_PROXIMUS, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch, &r));
+    else
+      BIC_TRY(bic_bsvd_update_dictionary_proximus(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch, &r));
     BIC_TRY(bic_memcpy_d2h(ctx_, &res, d_ch, 8));
     if (rounds) *rounds = r;
   } else {
-    if (step == 0) BIC_TRY(bic_bsvd_update_coefficients(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch));
+    if (step == 0 && wide) BIC_TRY(bic_bsvd_update_coefficients_wide(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch));
+    else if (step == 0) BIC_TRY(bic_bsvd_update_coefficients(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch));
+    else if (wide)
+      BIC_TRY(bic_bsvd_update_dictionary_wide(ctx_, BIC_BSVD_DU_STEEPEST, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch,
+                                              nullptr));
     else BIC_TRY(bic_bsvd_update_dictionary(ctx_, d_E, n, m, ew, d_D, p, dw, d_A, aw, d_ch));
     BIC_TRY(bic_memcpy_d2h(ctx_, &res, d_ch, 8));  // (waits for the step)
   }
@@ -454,6 +465,11 @@ int Device::bsvd_learn(binary_matrix& X, binary_matrix& E, binary_matrix& D, bin
 int Device::bsvd_learn(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A, int du, size_t max_iter,
                        idx_t* iters) {
   return bsvd_run(2, &X, E, D, A, max_iter, iters, du);
+}
+
+int Device::bsvd_learn(int lm, int du, binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A,
+                       size_t max_iter, idx_t* iters) {
+  return bsvd_run(2, &X, E, D, A, max_iter, iters, du, nullptr, lm);
 }
 
 int Device::bsvd_update_dictionary_proximus(binary_matrix& E, binary_matrix& D, binary_matrix& A, idx_t* changed,
@@ -507,6 +523,9 @@ idx_t bsvd_or_abort(const char* what, int rc, idx_t value) {
 // the reference's process-wide generator (get_rng, bsvd.cpp:8-15): seeded from random_seed at the first draw
 long random_seed = 34503498;
 mi_algorithm_t initialize_model = initialize_model_neighbor;
+cu_algorithm_t update_coefficients = update_coefficients_omp;
+// (the reference initialises this one with itself, i.e. null, and relies on learn_model_setup)
+du_algorithm_t update_dictionary = update_dictionary_steepest;
 
 namespace {
 void bsvd_initialize_or_abort(const char* what, int mi, const binary_matrix& E, binary_matrix& D, binary_matrix& A) {
@@ -566,8 +585,40 @@ idx_t update_dictionary_proximus_omp(binary_matrix& E, binary_matrix& D, binary_
   return bsvd_or_abort("update_dictionary_proximus_omp", rc, changed);
 }
 
-idx_t learn_model_traditional(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+namespace {
+// the device rule behind the global update_dictionary: one of the four dictionary functions of bsvd.h
+int bsvd_rule_or_abort(const char* what) {
+  if (update_dictionary == update_dictionary_steepest) return BIC_BSVD_DU_STEEPEST;
+  if (update_dictionary == update_dictionary_proximus || update_dictionary == update_dictionary_proximus_omp)
+    return BIC_BSVD_DU_PROXIMUS;
+  std::fprintf(stderr, "%s: update_dictionary is not one of this build's dictionary functions\n", what);
+  std::abort();
+}
+
+idx_t bsvd_learn_or_abort(const char* what, int lm, binary_matrix& X, binary_matrix& E, binary_matrix& D,
+                          binary_matrix& A) {
   idx_t iters = 0;
-  const int rc = bic::default_device().bsvd_learn(X, E, D, A, 0, &iters);
-  return bsvd_or_abort("learn_model_traditional", rc, iters);
+  const int du = bsvd_rule_or_abort(what);
+  // (the traditional loop with the steepest rule stays the call it has always been)
+  const int rc = (lm == BIC_BSVD_LM_TRADITIONAL && du == BIC_BSVD_DU_STEEPEST)
+                     ? bic::default_device().bsvd_learn(X, E, D, A, 0, &iters)
+                     : bic::default_device().bsvd_learn(lm, du, X, E, D, A, 0, &iters);
+  return bsvd_or_abort(what, rc, iters);
+}
+}  // namespace
+
+idx_t learn_model_traditional(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  return bsvd_learn_or_abort("learn_model_traditional", BIC_BSVD_LM_TRADITIONAL, X, E, D, A);
+}
+
+idx_t learn_model_alter1(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  return bsvd_learn_or_abort("learn_model_alter1", BIC_BSVD_LM_ALTER1, X, E, D, A);
+}
+
+idx_t learn_model_alter2(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  return bsvd_learn_or_abort("learn_model_alter2", BIC_BSVD_LM_ALTER2, X, E, D, A);
+}
+
+idx_t learn_model_alter3(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  return bsvd_learn_or_abort("learn_model_alter3", BIC_BSVD_LM_ALTER3, X, E, D, A);
 }

@@ -37,10 +37,14 @@ EXPORTS = [
     "bic_bsvd_update_dictionary_proximus", "bic_bsvd_learn_du", "bic_set_bsvd_rounds",
     "bic_bsvd_rng_seed", "bic_bsvd_rng_uniform", "bic_bsvd_init_neighbor", "bic_bsvd_init_partition",
     "bic_bsvd_init_centroids", "bic_bsvd_initialize",
+    "bic_bsvd_update_coefficients_wide", "bic_bsvd_update_dictionary_wide", "bic_bsvd_learn_lm",
 ]
 
 # bic_bsvd_learn_du rules (include/bic.h)
 BSVD_DU_STEEPEST, BSVD_DU_PROXIMUS = 0, 1
+
+# bic_bsvd_learn_lm learners (include/bic.h)
+BSVD_LM_TRADITIONAL, BSVD_LM_ALTER1, BSVD_LM_ALTER2, BSVD_LM_ALTER3 = 0, 1, 2, 3
 
 # bic_bsvd_initialize rules (include/bic.h)
 BSVD_MI_NEIGHBOR, BSVD_MI_PARTITION, BSVD_MI_CENTROIDS, BSVD_MI_CENTROIDS_XOR = 0, 1, 2, 3
@@ -168,6 +172,9 @@ def load(path=LIB_PATH):
     sig("bic_bsvd_update_dictionary_proximus", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp, C.POINTER(sz)])
     sig("bic_bsvd_learn_du", i32, [vp, i32, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
     sig("bic_set_bsvd_rounds", i32, [vp, u32])
+    sig("bic_bsvd_update_coefficients_wide", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
+    sig("bic_bsvd_update_dictionary_wide", i32, [vp, i32, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp, C.POINTER(sz)])
+    sig("bic_bsvd_learn_lm", i32, [vp, i32, i32, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
     sig("bic_bsvd_rng_seed", i32, [u64, C.POINTER(u64)])
     sig("bic_bsvd_rng_uniform", i32, [C.POINTER(u64), C.c_uint32, sz, vp])
     sig("bic_bsvd_init_neighbor", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
@@ -830,18 +837,42 @@ class Context:
             C.byref(rounds)), "bic_bsvd_update_dictionary_proximus")
         return (int(as_u64(ch)[0]) if changed is None else changed), rounds.value
 
+    def bsvd_update_coefficients_wide(self, E, m, D, A, p, changed=None):
+        """bsvd_update_coefficients by the wide-row kernels (m up to 1,048,576; the same result where both run)"""
+        return self._bsvd_step(self.lib.bic_bsvd_update_coefficients_wide, "bic_bsvd_update_coefficients_wide", E, m,
+                               D, A, p, changed)
+
+    def bsvd_update_dictionary_wide(self, E, m, D, A, p, du=0, changed=None):
+        """the dictionary update by the wide-row kernels (m up to 1,048,576): du = BSVD_DU_STEEPEST is
+        bsvd_update_dictionary -> atoms changed; du = BSVD_DU_PROXIMUS is bsvd_update_dictionary_proximus ->
+        (atoms changed, rounds run), and blocks. `changed` as for bsvd_update_coefficients."""
+        ch = self.empty_i64(1) if changed is None else changed
+        rounds = C.c_size_t(0)
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_update_dictionary_wide(
+            self.h, du, _p(E), E.shape[0], m, E.shape[1], _p(D), p, D.shape[1], _p(A), A.shape[1], _p(ch),
+            C.byref(rounds)), "bic_bsvd_update_dictionary_wide")
+        got = int(as_u64(ch)[0]) if changed is None else changed
+        return (got, rounds.value) if du == BSVD_DU_PROXIMUS else got
+
     def set_bsvd_rounds(self, rounds):
         """PROXIMUS rounds enqueued per atom before the host looks (0: automatic, else 1 .. 64); every value
         gives the same result"""
         self._chk(self.lib.bic_set_bsvd_rounds(self.h, rounds), "bic_set_bsvd_rounds")
 
-    def bsvd_learn(self, X, E, m, D, A, p, max_iter=0, du=0):
+    def bsvd_learn(self, X, E, m, D, A, p, max_iter=0, du=0, lm=0):
         """E = A D ^ X, then both steps until nothing changes (or max_iter iterations) -> iterations run; du
-        chooses the dictionary rule (BSVD_DU_STEEPEST, BSVD_DU_PROXIMUS). Blocks (the counts are read back
-        every iteration)."""
+        chooses the dictionary rule (BSVD_DU_STEEPEST, BSVD_DU_PROXIMUS), lm the learner (BSVD_LM_TRADITIONAL,
+        or the role-switching BSVD_LM_ALTER1 / 2 / 3, which return the reference's count and leave zero
+        padding in E, D and A). m above 4096 runs the wide-row steps. Blocks (the counts are read back every
+        iteration)."""
         it = C.c_size_t(0)
         self._bind_stream()
-        if du == BSVD_DU_STEEPEST:
+        if lm != BSVD_LM_TRADITIONAL or m > 4096:
+            self._chk(self.lib.bic_bsvd_learn_lm(self.h, lm, du, _p(X), X.shape[1], _p(E), E.shape[0], m, E.shape[1],
+                                                 _p(D), p, D.shape[1], _p(A), A.shape[1], max_iter, C.byref(it)),
+                      "bic_bsvd_learn_lm")
+        elif du == BSVD_DU_STEEPEST:
             self._chk(self.lib.bic_bsvd_learn(self.h, _p(X), X.shape[1], _p(E), E.shape[0], m, E.shape[1], _p(D), p,
                                               D.shape[1], _p(A), A.shape[1], max_iter, C.byref(it)), "bic_bsvd_learn")
         else:

@@ -574,6 +574,64 @@ int bic_bsvd_learn_du(bic_ctx* ctx, int du, const uint64_t* X, size_t x_wpr, uin
                       size_t* iters);
 int bic_set_bsvd_rounds(bic_ctx* ctx, unsigned rounds);
 
+/* ---- wide rows and the role-switching learners (bsvd.cpp:1247-1434) ----------------------------
+ * bic_bsvd_update_coefficients_wide and bic_bsvd_update_dictionary_wide are the three steps above for
+ * rows of any width. Domain: 1 <= m <= 1048576, 1 <= p <= 4096, n < 2^31; outside it BIC_EINVAL; n = 0
+ * is BIC_OK with changed = 0 and rounds = 0 (under either rule). The meaning is, word for word, that of
+ * bic_bsvd_update_coefficients, of bic_bsvd_update_dictionary (du = BIC_BSVD_DU_STEEPEST: rounds is
+ * not written, A is only read) and of bic_bsvd_update_dictionary_proximus (du = BIC_BSVD_DU_PROXIMUS),
+ * with every convention stated for them: whole words in distances, weights and XORs, D_k's last word
+ * masked in the PROXIMUS coefficient vote, the padding bits of D and A never changed, words past a
+ * row's own never touched, changed and rounds as defined there, bic_set_bsvd_rounds honoured with
+ * every budget giving the same result; any other du is BIC_EINVAL. These entries always run the wide
+ * kernels, whatever m, and give the narrow entries' outputs where m <= 4096.
+ *
+ * Sparse coding is one launch (a workgroup per row, repeated inside until no atom lowers the weight).
+ * The steepest rule is one launch in which every chunk of 1,024 columns walks the p atoms by itself
+ * (bit c of an atom depends on column c of E alone), and one that counts the atoms changed. PROXIMUS
+ * keeps the narrow entry's schedule and therefore blocks, as that entry does; the other two do not
+ * synchronise with the host. No workgroup ever waits for another. The scratch is the ctx's, sized on
+ * first use.
+ *
+ * bic_bsvd_learn_lm runs a learner of the reference's catalogue. lm = BIC_BSVD_LM_TRADITIONAL is
+ * bic_bsvd_learn_du for m up to 1048576: the same launches for m <= 4096, the wide steps above that.
+ * lm = BIC_BSVD_LM_ALTER1, _ALTER2, _ALTER3 are learn_model_alter1 / 2 / 3 exactly as written: they
+ * transpose A, D and E (bic_gf2_transpose, into the ctx scratch), run the same steps with the roles
+ * exchanged -- update_coefficients(Et, At, Dt), update_dictionary(Et, At, Dt): Et (m x n) the
+ * residual, At's p rows of n bits the atoms, Dt (m x p) the coefficients -- and transpose back. Kept
+ * as the text has them:
+ *   alter1 (:1247-1312): direct sparse coding and dictionary step, then the transposed pair; the loop
+ *     goes on only on the transposed dictionary step's count (:1297 overwrites the sums before it), so
+ *     it can stop with direct coefficient moves still pending.
+ *   alter2 (:1315-1385): a direct loop to convergence, then a transposed one, repeated while either
+ *     changed anything; `changed` is not reset before the direct loop of a second outer pass, so that
+ *     loop is skipped; iter is reset before every transposed loop, so the return value is the last
+ *     transposed loop's count.
+ *   alter3 (:1388-1434): no sparse coding at all; the transposed dictionary step, then the direct one,
+ *     and only the direct one's count decides.
+ * transpose_to clears the padding (binmat.cpp:199-208): the transposed matrices have zero padding, and
+ * after the transposes back the padding bits inside the words of E, D and A are zero (words past a
+ * row's own are untouched); the direct steps before the first switch still see the caller's padding.
+ * Domain for lm >= 1: 1 <= m <= 1048576, 1 <= n <= 1048576, 1 <= p <= 4096 (BIC_ENOMEM where the
+ * transposes do not fit the device). Each half uses the narrow kernels where its rows have at most
+ * 4096 bits and the wide ones above; the result is the same either way. max_iter (0 = none) caps the
+ * loop passes, every iter++ of the text, counted over the whole call: the pass that reaches the cap is
+ * finished, transposes back included, and the call returns BIC_OK. iters (HOST pointer, nullable)
+ * receives the reference's return value. The call blocks, as bic_bsvd_learn. Any other lm or du is
+ * BIC_EINVAL. */
+#define BIC_BSVD_LM_TRADITIONAL 0
+#define BIC_BSVD_LM_ALTER1 1
+#define BIC_BSVD_LM_ALTER2 2
+#define BIC_BSVD_LM_ALTER3 3
+int bic_bsvd_update_coefficients_wide(bic_ctx* ctx, uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D,
+                                      size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* changed);
+int bic_bsvd_update_dictionary_wide(bic_ctx* ctx, int du, uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D,
+                                    size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* changed,
+                                    size_t* rounds);
+int bic_bsvd_learn_lm(bic_ctx* ctx, int lm, int du, const uint64_t* X, size_t x_wpr, uint64_t* E, size_t n, size_t m,
+                      size_t e_wpr, uint64_t* D, size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, size_t max_iter,
+                      size_t* iters);
+
 /* ---- model initialisers (bsvd.cpp:99-267) -----------------------------------------------------
  * The four rules the reference starts a dictionary from: D (p x m) and A (n x p) are made from the data
  * E (n x m, const), which the driver passes as E = X before learning (bsvd_test.cpp:114-119).

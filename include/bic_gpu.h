@@ -131,7 +131,8 @@ class Device {
                   const double* enuml = nullptr);
 
   // bsvd.cpp:399-460 / 463-527 / 1215-1244 (bic.h "binary dictionary learning"): E and X n x m, D p x m,
-  // A n x p, 1 <= m, p <= 4096. The matrices are uploaded, the step runs on the device, and what it
+  // A n x p, 1 <= p <= 4096, 1 <= m <= 1048576: above m = 4096 the steps run the wide-row entries (bic.h "wide
+  // rows"), with the same results. The matrices are uploaded, the step runs on the device, and what it
   // may have changed is downloaded: E and A; E and D; E, D and A. changed / iters (nullable) receive the
   // reference functions' return values. max_iter = 0: no cap (the reference's loop).
   int bsvd_update_coefficients(binary_matrix& E, const binary_matrix& D, binary_matrix& A, idx_t* changed = nullptr);
@@ -144,6 +145,10 @@ class Device {
                                       idx_t* rounds = nullptr);
   int bsvd_learn(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A, int du, size_t max_iter = 0,
                  idx_t* iters = nullptr);
+  // bic_bsvd_learn_lm: the learner lm (BIC_BSVD_LM_*: the loop above, or learn_model_alter1 / 2 / 3 of
+  // bsvd.cpp:1247-1434, which leave zero padding in E, D and A) with the rule du
+  int bsvd_learn(int lm, int du, binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A,
+                 size_t max_iter = 0, idx_t* iters = nullptr);
   // bsvd.cpp:99-267, the model initialisers (bic.h "model initialisers"): E is uploaded, D and A are made on the
   // device by the rule mi (BIC_BSVD_MI_*) and downloaded. state: the generator's state (bic_bsvd_rng_seed), read
   // and advanced by the rules that draw; may be null for BIC_BSVD_MI_PARTITION. E needs at least one row.
@@ -160,7 +165,7 @@ class Device {
   int fetch_stream(const uint64_t* slot, uint64_t bits, Stream* s);
   // step: 0 coefficients, 1 dictionary, 2 learn (X then non-null) with the rule du, 3 the PROXIMUS dictionary step
   int bsvd_run(int step, const binary_matrix* X, binary_matrix& E, binary_matrix& D, binary_matrix& A,
-               size_t max_iter, idx_t* result, int du = 0, idx_t* rounds = nullptr);
+               size_t max_iter, idx_t* result, int du = 0, idx_t* rounds = nullptr, int lm = 0);
 
   bic_ctx* ctx_ = nullptr;
   int status_ = BIC_ENODEV;

@@ -1,14 +1,16 @@
 // bsvd.h -- the part of the reference's binary dictionary learning API that this build implements,
 // with the reference's signatures, so code written against it links: four model initialisers, the
-// greedy sparse-coding step, the two dictionary steps and the loop that alternates them. Each function
+// greedy sparse-coding step, the two dictionary steps, the loop that alternates them and the three
+// role-switching learners. Each function
 // hands its matrices to bic::default_device() (bic_gpu.h), which runs the step in the HIP kernels behind
 // bic.h and copies the results back; a failing device call prints its reason and aborts, as med() does.
 //
 // The model is X = A D + E over GF(2): X (n x m) holds one sample per row, D (p x m) one atom per
 // row, A (n x p) says which atoms a sample uses and E (n x m) is what they leave unexplained.
-// m and p are limited to 1 .. 4096 here. A model is started as the reference's driver does it: E = X,
-// initialize_model(E, D, A), then learn_model_traditional(X, E, D, A). The reference's
-// initialize_model_graph_grow, learn_model_setup and its catalogs, its role-switching learners and its
+// p is limited to 1 .. 4096 here; the steps and the learners take m up to 1048576 (the role-switching
+// learners n up to 1048576 as well), the model initialisers m up to 4096. A model is started as the
+// reference's driver does it: E = X, initialize_model(E, D, A), then a learner. The reference's
+// initialize_model_graph_grow, update_coefficients_fast, learn_model_setup and its catalogs and its
 // model-order searches are not part of this build (DESIGN.md lists them).
 #ifndef BSVD_H
 #define BSVD_H
@@ -60,8 +62,32 @@ idx_t update_dictionary_proximus(binary_matrix& E, binary_matrix& D, binary_matr
 // The same step; both names run the same device kernels and give the same result.
 idx_t update_dictionary_proximus_omp(binary_matrix& E, binary_matrix& D, binary_matrix& A);
 
+typedef idx_t (*cu_algorithm_t)(binary_matrix& E, const binary_matrix& D, binary_matrix& A);
+typedef idx_t (*du_algorithm_t)(binary_matrix& E, binary_matrix& D, binary_matrix& A);
+typedef idx_t (*ml_algorithm_t)(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A);
+
+// The steps the learners below use. update_coefficients is update_coefficients_omp unless assigned (both
+// sparse-coding functions run the same kernel, so the learners do not look at it). update_dictionary chooses
+// the learners' dictionary rule: it must be one of the four dictionary functions above, anything else makes a
+// learner print a message and abort. The reference initialises update_dictionary with itself, i.e. null, and
+// crashes unless learn_model_setup ran; here it is update_dictionary_steepest unless assigned.
+extern cu_algorithm_t update_coefficients;
+extern du_algorithm_t update_dictionary;
+
 // Sets E = A D + X and then alternates the two steps above until neither changes anything.
 // Returns the number of iterations run.
 idx_t learn_model_traditional(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A);
+
+// The role-switching learners: like the loop above, but they also run the two steps on the transposed model,
+// where the atoms are the rows of A transposed (one bit per sample) and D transposed holds the coefficients,
+// and transpose back; E, D and A come back with zero padding bits. As the reference has them:
+// alter1 runs the direct pair and the transposed pair in every pass and goes on only while the transposed
+// dictionary step changes an atom; alter2 runs the direct loop to its end, then the transposed loop, and
+// repeats both while anything changed (its second direct loop never runs, and it returns the last transposed
+// loop's count); alter3 never recodes: the transposed dictionary step, then the direct one, while the direct
+// one changes an atom (the one meant for update_dictionary_proximus).
+idx_t learn_model_alter1(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A);
+idx_t learn_model_alter2(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A);
+idx_t learn_model_alter3(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A);
 
 #endif
