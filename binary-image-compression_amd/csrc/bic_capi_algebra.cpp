@@ -230,6 +230,24 @@ void bsvd_transpose(bic_ctx* ctx, const BsvdMat& B, const BsvdMat& T) {
   });
 }
 
+// the role-switching learners' arena: the steps' own part for either role, then Et, At and Dt
+size_t bsvd_alter_head_bytes(size_t n, size_t m, size_t p) {
+  return (std::max(bic::bsvd_wide_scratch_bytes((uint32_t)n, (uint32_t)p),
+                   bic::bsvd_wide_scratch_bytes((uint32_t)m, (uint32_t)p)) + 255) & ~(size_t)255;
+}
+
+}  // namespace
+
+// The arena bytes bic_bsvd_learn_lm takes for the learner lm (bic_ctx.h: a caller that keeps data of its own in the
+// arena across such calls sizes the arena for them first and puts its data after these bytes)
+size_t bsvd_learn_arena_bytes(int lm, size_t n, size_t m, size_t p) {
+  if (lm == BIC_BSVD_LM_TRADITIONAL) return bic::bsvd_wide_scratch_bytes((uint32_t)n, (uint32_t)p);
+  const size_t nw = (n + 63) / 64, pw = (p + 63) / 64;
+  return bsvd_alter_head_bytes(n, m, p) + (m * nw + p * nw + m * pw) * 8;
+}
+
+namespace {
+
 // learn_model_alter1 / 2 / 3 (bsvd.cpp:1247-1434) as written. In the exchanged role the calls are
 // update_coefficients(Et, At, Dt) and update_dictionary(Et, At, Dt): Et (m x n) the residual, At's p rows of n
 // bits the atoms, Dt (m x p) the coefficients. Et, At and Dt live in the arena after the steps' own part.
@@ -245,9 +263,8 @@ int bsvd_learn_alter(bic_ctx* ctx, int lm, int du, const uint64_t* X, size_t x_w
     return BIC_EINVAL;
   if (iters) *iters = 0;
   const size_t nw = (n + 63) / 64, pw = (p + 63) / 64;
-  const size_t head = (std::max(bic::bsvd_wide_scratch_bytes((uint32_t)n, (uint32_t)p),
-                                bic::bsvd_wide_scratch_bytes((uint32_t)m, (uint32_t)p)) + 255) & ~(size_t)255;
-  if ((rc = ensure_scratch(ctx, head + (m * nw + p * nw + m * pw) * 8))) return rc;
+  const size_t head = bsvd_alter_head_bytes(n, m, p);
+  if ((rc = ensure_scratch(ctx, bsvd_learn_arena_bytes(lm, n, m, p)))) return rc;
   uint64_t* tw = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->scratch) + head);
   const BsvdMat Em{E, n, m, e_wpr}, Dm{D, p, m, d_wpr}, Am{A, n, p, a_wpr};
   const BsvdMat Et{tw, m, n, nw}, At{tw + m * nw, p, n, nw}, Dt{tw + m * nw + p * nw, m, p, pw};

@@ -217,6 +217,9 @@ inline int ensure_rbuf(bic_ctx* ctx, size_t need) {
   return BIC_OK;
 }
 
+// bic_capi_algebra.cpp: the arena bytes one bic_bsvd_learn_lm call takes (from the arena's start)
+size_t bsvd_learn_arena_bytes(int lm, size_t n, size_t m, size_t p);
+
 inline bool geom_ok(size_t rows, size_t cols, size_t wpr) {
   if (cols == 0 || rows > 0x7fffffffu || cols > 0x7ffffffeu) return false;
   if (wpr < (cols + 63) / 64 || wpr > 0xffffffffu) return false;

@@ -392,6 +392,26 @@ void launch_bsvd_wide_prox_atom(hipStream_t s, uint64_t* E, uint32_t n, uint32_t
                                 bool check_prev, bool fresh);
 void launch_bsvd_wide_prox_coef(hipStream_t s, uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* D,
                                 uint32_t d_wpr, uint64_t* A, uint32_t a_wpr, void* scratch, uint32_t k, uint32_t r);
+// The MDL model-order searches' device side (bic_bsvd_mdl.hip), m in 1 .. 1,048,576, p <= 4096, n >= 1. Every read
+// of E, D and A is masked at the row's last word. launch_bsvd_mdl_weights: *we = |E|, wd[k] = |D_k|, wa[k] = the
+// users of atom k (p = 0: we alone, D and A not dereferenced). launch_bsvd_mdl_drop_weights: score[k] =
+// |E ^ A_k^t D_k| for k < p, p >= 1; scratch holds bsvd_mdl_drop_scratch_bytes. launch_bsvd_mdl_drop_atom takes row k
+// out of D and column k out of A in place (k < p), launch_bsvd_mdl_append_atom adds row p and column p (the caller
+// has room for them). launch_bsvd_mdl_copy: dst = src, rows x words.
+void launch_bsvd_mdl_weights(hipStream_t s, const uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr, const uint64_t* D,
+                             uint32_t p, uint32_t d_wpr, const uint64_t* A, uint32_t a_wpr, uint64_t* we, uint32_t* wd,
+                             uint32_t* wa);
+size_t bsvd_mdl_drop_scratch_bytes();
+void launch_bsvd_mdl_drop_weights(hipStream_t s, const uint64_t* E, uint32_t n, uint32_t m, uint32_t e_wpr,
+                                  const uint64_t* D, uint32_t p, uint32_t d_wpr, const uint64_t* A, uint32_t a_wpr,
+                                  uint64_t* score, void* scratch);
+void launch_bsvd_mdl_drop_atom(hipStream_t s, uint64_t* D, uint32_t p, uint32_t m, uint32_t d_wpr, uint64_t* A,
+                               uint32_t n, uint32_t a_wpr, uint32_t k);
+void launch_bsvd_mdl_append_atom(hipStream_t s, uint64_t* D, uint32_t p, uint32_t m, uint32_t d_wpr, uint64_t* A,
+                                 uint32_t n, uint32_t a_wpr, const uint64_t* atom, const uint64_t* coefs,
+                                 uint32_t c_wpr);
+void launch_bsvd_mdl_copy(hipStream_t s, uint64_t* dst, uint32_t d_wpr, const uint64_t* src, uint32_t s_wpr,
+                          uint32_t rows, uint32_t words);
 
 // The growing-dictionary tile coder of compress2_test.cpp:79-129 / compress3_test.cpp:87-149 (bic_dict.hip).
 // The plane is only read. Everything below `arena` is carved from the scratch by dict_carve, which also

@@ -6,6 +6,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <iostream>
 
 namespace bic {
 
@@ -498,6 +499,77 @@ int Device::bsvd_initialize(int mi, const binary_matrix& E, binary_matrix& D, bi
   return BIC_OK;
 }
 
+int Device::bsvd_model_codelength(const binary_matrix& E, const binary_matrix& D, const binary_matrix& A,
+                                  uint64_t* length) {
+  BIC_TRY(status_);
+  const idx_t n = E.get_rows(), m = E.get_cols(), p = D.get_rows();
+  if (!length || !n || !m || !E.raw_blocks()) return BIC_EINVAL;
+  if (p && (D.get_cols() != m || A.get_rows() != n || A.get_cols() != p || !D.raw_blocks() || !A.raw_blocks()))
+    return BIC_EINVAL;
+  const idx_t ew = E.get_blocks_per_row(), dw = p ? D.get_blocks_per_row() : 0, aw = p ? A.get_blocks_per_row() : 0;
+  BIC_TRY(ensure(out_a_, n * ew * 8 + 8));
+  BIC_TRY(ensure(out_b_, p * dw * 8 + 8));
+  BIC_TRY(ensure(aux_, n * aw * 8 + 8));
+  uint64_t* d_E = static_cast<uint64_t*>(out_a_.p);
+  uint64_t* d_D = static_cast<uint64_t*>(out_b_.p);
+  uint64_t* d_A = static_cast<uint64_t*>(aux_.p);
+  BIC_TRY(upload(E, d_E));
+  if (p) {
+    BIC_TRY(upload(D, d_D));
+    BIC_TRY(upload(A, d_A));
+  }
+  return bic_bsvd_model_codelength(ctx_, d_E, n, m, ew, p ? d_D : nullptr, p, dw, p ? d_A : nullptr, aw, length);
+}
+
+int Device::bsvd_learn_mdl(int search, int lmi, int du, int mi, binary_matrix& X, binary_matrix& E, binary_matrix& D,
+                           binary_matrix& A, uint64_t* state, MdlResult* out, size_t p_cap) {
+  BIC_TRY(status_);
+  const idx_t n = E.get_rows(), m = E.get_cols(), p = D.get_rows();
+  if (!out || D.get_cols() != m || A.get_rows() != n || A.get_cols() != p || !same_shape(X, E)) return BIC_EINVAL;
+  if (!n || !m || !p || !E.raw_blocks() || !A.raw_blocks() || !D.raw_blocks()) return BIC_EINVAL;
+  if (search != BIC_BSVD_MDL_FORWARD) p_cap = p;  // only the forward search grows the model
+  else if (!p_cap) p_cap = 4096;
+  if (p > p_cap || p_cap > 4096) return BIC_EINVAL;
+  const idx_t ew = E.get_blocks_per_row(), dw = D.get_blocks_per_row(), aw = A.get_blocks_per_row();
+  const idx_t cw = (p_cap + 63) / 64;  // A's pitch on the device
+  BIC_TRY(ensure(in_, n * ew * 8 + 8));
+  BIC_TRY(ensure(out_a_, n * ew * 8 + 8));
+  BIC_TRY(ensure(out_b_, p_cap * dw * 8 + 8));
+  BIC_TRY(ensure(aux_, n * cw * 8 + 8));
+  uint64_t* d_X = static_cast<uint64_t*>(in_.p);
+  uint64_t* d_E = static_cast<uint64_t*>(out_a_.p);
+  uint64_t* d_D = static_cast<uint64_t*>(out_b_.p);
+  uint64_t* d_A = static_cast<uint64_t*>(aux_.p);
+  BIC_TRY(upload(X, d_X));
+  BIC_TRY(upload(E, d_E));  // (the full search may leave it as it is)
+  BIC_TRY(upload(D, d_D));
+  std::vector<uint64_t> wide(n * cw, 0);
+  for (idx_t i = 0; i < n; ++i) std::memcpy(&wide[i * cw], A.raw_blocks() + i * aw, aw * 8);
+  BIC_TRY(bic_memcpy_h2d(ctx_, d_A, wide.data(), wide.size() * 8));
+  size_t atoms = 0, passes = 0;
+  uint64_t len = 0;
+  out->trace.assign(p_cap + 16, bic_bsvd_mdl_step{});  // (a search runs at most p_cap passes)
+  const int rc = bic_bsvd_learn_mdl(ctx_, search, lmi, du, mi, d_X, ew, d_E, n, m, ew, d_D, p, p_cap, dw, d_A, cw, state,
+                                    &atoms, &len, out->trace.data(), out->trace.size(), &passes);
+  out->trace.resize(std::min(passes, out->trace.size()));
+  if (rc != BIC_OK && rc != BIC_ENOSPC) return rc;
+  out->atoms = atoms;
+  out->length = len;
+  if (search == BIC_BSVD_MDL_FULL && atoms == 0) return rc;  // nothing was taken: E, D and A stay
+  BIC_TRY(download(d_E, E));
+  D.destroy();
+  A.destroy();
+  if (atoms) {
+    D.allocate(atoms, m);
+    A.allocate(n, atoms);
+    BIC_TRY(download(d_D, D));
+    BIC_TRY(bic_memcpy_d2h(ctx_, wide.data(), d_A, wide.size() * 8));
+    const idx_t rw = A.get_blocks_per_row();
+    for (idx_t i = 0; i < n; ++i) std::memcpy(A.raw_blocks() + i * rw, &wide[i * cw], rw * 8);
+  }
+  return rc;
+}
+
 Device& default_device() {
   static Device* dev = new Device(0);
   if (dev->status() != BIC_OK) {
@@ -528,14 +600,19 @@ cu_algorithm_t update_coefficients = update_coefficients_omp;
 du_algorithm_t update_dictionary = update_dictionary_steepest;
 
 namespace {
-void bsvd_initialize_or_abort(const char* what, int mi, const binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+// (seeded by the first rule that draws; the MDL searches share it)
+uint64_t* bsvd_rng_state(int mi) {
   static uint64_t state = 0;
   static bool seeded = false;
   if (mi != BIC_BSVD_MI_PARTITION && !seeded) {
     bic_bsvd_rng_seed((uint64_t)random_seed, &state);
     seeded = true;
   }
-  bsvd_or_abort(what, bic::default_device().bsvd_initialize(mi, E, D, A, &state), 0);
+  return &state;
+}
+
+void bsvd_initialize_or_abort(const char* what, int mi, const binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  bsvd_or_abort(what, bic::default_device().bsvd_initialize(mi, E, D, A, bsvd_rng_state(mi)), 0);
 }
 }  // namespace
 
@@ -621,4 +698,135 @@ idx_t learn_model_alter2(binary_matrix& X, binary_matrix& E, binary_matrix& D, b
 
 idx_t learn_model_alter3(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {
   return bsvd_learn_or_abort("learn_model_alter3", BIC_BSVD_LM_ALTER3, X, E, D, A);
+}
+
+// ---- the MDL model order (bsvd.cpp:1438-1717) ------------------------------------------------------
+ml_algorithm_t learn_model = learn_model_traditional;
+ml_algorithm_t learn_model_inner = learn_model_traditional;
+
+const char* mi_algorithm_names[] = {"Neighbor initialization", "Partition initialization",
+                                    "Random centroids initialization",
+                                    "Random centroids (in mod-2 algebra) initialization",
+                                    "Graph growing initialization", 0};
+const char* cu_algorithm_names[] = {"OpenMP basic coefficients update", "Basic coefficients update",
+                                    "Fast coefficients update (broken!)", 0};
+const char* du_algorithm_names[] = {"Steepest descent (a la MOD)  dictionary update", "Proximus-like dictionary update",
+                                    "Steepest descent (a la MOD)  dictionary update (OMP)",
+                                    "Proximus-like dictionary update (OMP)", 0};
+const char* lm_algorithm_names[] = {
+    "Model learning by traditional alternate descent",
+    "Role-switching learning 1: at each iteration, the role of A and D are switched",
+    "Role-switched learning 2: after convergence, the role of A and D are switched and traditional model is applied "
+    "again",
+    "Role switched learning 3: like RS1 but only update_dictionary is applied (for use with Proximus",
+    "MDL/forward selection",
+    "MDO/backward selection",
+    "MDL/full search",
+    0};
+
+namespace {
+const mi_algorithm_t kInitialisers[] = {initialize_model_neighbor, initialize_model_partition,
+                                        initialize_model_random_centroids, initialize_model_random_centroids_xor};
+const ml_algorithm_t kLearners[] = {learn_model_traditional,           learn_model_alter1,
+                                    learn_model_alter2,                learn_model_alter3,
+                                    learn_model_mdl_forward_selection, learn_model_mdl_backward_selection,
+                                    learn_model_mdl_full_search};
+
+void missing_piece(const char* which) {
+  std::cerr << which << " is not part of this build" << std::endl;
+  std::exit(-1);
+}
+
+void print_pass(const bic_bsvd_mdl_step& r) {
+  std::cout << "currK=" << r.K << " currL=" << r.currL << " bestK=" << r.bestK << " bestL=" << r.bestL
+            << " stuck=" << r.stuck << " dif=" << r.dif << " dev=" << r.dev << std::endl;
+}
+
+// one search on the default device with what the globals say, then the reference's stdout lines from the trace
+idx_t bsvd_mdl_or_abort(const char* what, int search, binary_matrix& X, binary_matrix& E, binary_matrix& D,
+                        binary_matrix& A) {
+  int lmi = -1, mi = -1;
+  for (int i = 0; i < 4; ++i) {
+    if (learn_model_inner == kLearners[i]) lmi = i;
+    if (initialize_model == kInitialisers[i]) mi = i;
+  }
+  if (lmi < 0) {
+    std::fprintf(stderr, "%s: learn_model_inner is not one of this build's four learners\n", what);
+    std::abort();
+  }
+  if (mi < 0 && search != BIC_BSVD_MDL_BACKWARD) {
+    std::fprintf(stderr, "%s: initialize_model is not one of this build's initialisers\n", what);
+    std::abort();
+  }
+  if (mi < 0) mi = BIC_BSVD_MI_PARTITION;  // (the backward search draws nothing)
+  const int du = bsvd_rule_or_abort(what);
+  bic::Device::MdlResult r;
+  const bool draws = search != BIC_BSVD_MDL_BACKWARD && mi != BIC_BSVD_MI_PARTITION;
+  const int rc = bic::default_device().bsvd_learn_mdl(search, lmi, du, mi, X, E, D, A,
+                                                      draws ? bsvd_rng_state(mi) : nullptr, &r);
+  if (search == BIC_BSVD_MDL_FULL) {
+    for (const bic_bsvd_mdl_step& s : r.trace) {
+      std::cout << "K=" << s.K;
+      for (int i = 0; i < 10; ++i) {
+        random_seed = (random_seed * 31) % 17;  // :1686 (changes no draw: the generator is seeded once)
+        std::cout << " " << s.lens[i];
+      }
+      std::cout << " " << s.currL << std::endl;
+    }
+    if (rc == BIC_OK) std::cout << "bestL=" << r.length << " bestk=" << r.atoms << std::endl;
+  } else {
+    for (const bic_bsvd_mdl_step& s : r.trace) print_pass(s);
+    if (rc == BIC_OK && search == BIC_BSVD_MDL_BACKWARD && r.atoms == 0) {
+      std::cout << "Resulted in empty model!" << std::endl;
+    } else if (rc == BIC_OK && !r.trace.empty()) {
+      // the last pass was rejected unless it made the model of K - 1 (forward: K + 1) atoms the best
+      const bic_bsvd_mdl_step& last = r.trace.back();
+      const uint64_t made = search == BIC_BSVD_MDL_FORWARD ? last.K + 1 : last.K - 1;
+      if (last.stuck == 9 && r.atoms != made) std::cout << "No further improvement." << std::endl;
+    }
+  }
+  return bsvd_or_abort(what, rc, r.length);
+}
+}  // namespace
+
+idx_t model_codelength(const binary_matrix& E, const binary_matrix& D, const binary_matrix& A) {
+  uint64_t len = 0;
+  const int rc = bic::default_device().bsvd_model_codelength(E, D, A, &len);
+  return bsvd_or_abort("model_codelength", rc, len);
+}
+
+idx_t learn_model_mdl_forward_selection(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  return bsvd_mdl_or_abort("learn_model_mdl_forward_selection", BIC_BSVD_MDL_FORWARD, X, E, D, A);
+}
+
+idx_t learn_model_mdl_backward_selection(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  return bsvd_mdl_or_abort("learn_model_mdl_backward_selection", BIC_BSVD_MDL_BACKWARD, X, E, D, A);
+}
+
+idx_t learn_model_mdl_full_search(binary_matrix& X, binary_matrix& E, binary_matrix& D, binary_matrix& A) {
+  return bsvd_mdl_or_abort("learn_model_mdl_full_search", BIC_BSVD_MDL_FULL, X, E, D, A);
+}
+
+void learn_model_setup(int mi_algo, int cu_algo, int du_algo, int lm_algo, int lmi_algo) {
+  // (bsvd.cpp:80-84: only the upper bounds are checked there; a negative index is refused here as well)
+  if (mi_algo < 0 || mi_algo > 4) { std::cerr << "Invalid model initialization algorithm (0-" << 4 << ')' << std::endl; std::exit(-1); }
+  if (cu_algo < 0 || cu_algo > 2) { std::cerr << "Invalid coefficients update algorithm (0-" << 2 << ')' << std::endl; std::exit(-1); }
+  if (du_algo < 0 || du_algo > 3) { std::cerr << "Invalid dictionary update algorithm (0-" << 3 << ')' << std::endl; std::exit(-1); }
+  if (lm_algo < 0 || lm_algo > 6) { std::cerr << "Invalid model learning algorithm (0-" << 6 << ')' << std::endl; std::exit(-1); }
+  if (lmi_algo < 0 || lmi_algo > 3) { std::cerr << "Invalid inner model learning algorithm (0-" << 3 << ')' << std::endl; std::exit(-1); }
+  if (mi_algo == 4) missing_piece("initialize_model_graph_grow (model initialization algorithm 4)");
+  if (cu_algo == 2) missing_piece("update_coefficients_fast (coefficients update algorithm 2)");
+  if (du_algo == 2) missing_piece("update_dictionary_steepest_omp (dictionary update algorithm 2)");
+  const du_algorithm_t rules[] = {update_dictionary_steepest, update_dictionary_proximus, nullptr,
+                                  update_dictionary_proximus_omp};
+  initialize_model = kInitialisers[mi_algo];
+  std::cout << "Using " << mi_algorithm_names[mi_algo] << std::endl;
+  update_coefficients = cu_algo == 0 ? update_coefficients_omp : update_coefficients_basic;
+  std::cout << "Using " << cu_algorithm_names[cu_algo] << std::endl;
+  update_dictionary = rules[du_algo];
+  std::cout << "Using " << du_algorithm_names[du_algo] << std::endl;
+  learn_model = kLearners[lm_algo];
+  std::cout << "Using " << lm_algorithm_names[lm_algo] << " for outer learning loop." << std::endl;
+  learn_model_inner = kLearners[lmi_algo];
+  std::cout << "Using " << lm_algorithm_names[lmi_algo] << " for inner learning." << std::endl;
 }

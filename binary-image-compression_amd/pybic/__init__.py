@@ -38,6 +38,8 @@ EXPORTS = [
     "bic_bsvd_rng_seed", "bic_bsvd_rng_uniform", "bic_bsvd_init_neighbor", "bic_bsvd_init_partition",
     "bic_bsvd_init_centroids", "bic_bsvd_initialize",
     "bic_bsvd_update_coefficients_wide", "bic_bsvd_update_dictionary_wide", "bic_bsvd_learn_lm",
+    "bic_universal_codelength", "bic_bsvd_model_weights", "bic_bsvd_drop_weights", "bic_bsvd_drop_atom",
+    "bic_bsvd_append_atom", "bic_bsvd_model_codelength", "bic_bsvd_learn_mdl",
 ]
 
 # bic_bsvd_learn_du rules (include/bic.h)
@@ -48,6 +50,9 @@ BSVD_LM_TRADITIONAL, BSVD_LM_ALTER1, BSVD_LM_ALTER2, BSVD_LM_ALTER3 = 0, 1, 2, 3
 
 # bic_bsvd_initialize rules (include/bic.h)
 BSVD_MI_NEIGHBOR, BSVD_MI_PARTITION, BSVD_MI_CENTROIDS, BSVD_MI_CENTROIDS_XOR = 0, 1, 2, 3
+
+# bic_bsvd_learn_mdl searches (include/bic.h)
+BSVD_MDL_FORWARD, BSVD_MDL_BACKWARD, BSVD_MDL_FULL = 0, 1, 2
 
 # bic_gf2_mul ops (include/bic.h)
 GF2_AB, GF2_ATB, GF2_ABT, GF2_ATBT = 0, 1, 2, 3
@@ -76,6 +81,18 @@ class PnmInfo(C.Structure):
     """include/bic.h bic_pnm_info"""
     _fields_ = [("type", C.c_int), ("rows", C.c_size_t), ("cols", C.c_size_t), ("maxval", C.c_int),
                 ("data_offset", C.c_size_t)]
+
+
+class MdlStep(C.Structure):
+    """include/bic.h bic_bsvd_mdl_step"""
+    _fields_ = [("K", C.c_uint64), ("currL", C.c_uint64), ("bestK", C.c_uint64), ("bestL", C.c_uint64),
+                ("stuck", C.c_uint64), ("dif", C.c_int32), ("dev", C.c_int32), ("atom", C.c_uint32),
+                ("reserved", C.c_uint32), ("lens", C.c_uint64 * 10)]
+
+    def astuple(self):
+        """(K, currL, bestK, bestL, stuck, dif, dev, atom, the ten lengths)"""
+        return (self.K, self.currL, self.bestK, self.bestL, self.stuck, self.dif, self.dev, self.atom,
+                tuple(self.lens))
 
 
 class BicError(RuntimeError):
@@ -175,6 +192,15 @@ def load(path=LIB_PATH):
     sig("bic_bsvd_update_coefficients_wide", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_update_dictionary_wide", i32, [vp, i32, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp, C.POINTER(sz)])
     sig("bic_bsvd_learn_lm", i32, [vp, i32, i32, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
+    sig("bic_universal_codelength", C.c_double, [u32, u32])
+    sig("bic_bsvd_model_weights", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp, vp, vp])
+    sig("bic_bsvd_drop_weights", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
+    sig("bic_bsvd_drop_atom", i32, [vp, vp, sz, sz, sz, vp, sz, sz, sz])
+    sig("bic_bsvd_append_atom", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp, sz])
+    sig("bic_bsvd_model_codelength", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, C.POINTER(u64)])
+    sig("bic_bsvd_learn_mdl", i32, [vp, i32, i32, i32, i32, vp, sz, vp, sz, sz, sz, vp, sz, sz, sz, vp, sz,
+                                    C.POINTER(u64), C.POINTER(sz), C.POINTER(u64), C.POINTER(MdlStep), sz,
+                                    C.POINTER(sz)])
     sig("bic_bsvd_rng_seed", i32, [u64, C.POINTER(u64)])
     sig("bic_bsvd_rng_uniform", i32, [C.POINTER(u64), C.c_uint32, sz, vp])
     sig("bic_bsvd_init_neighbor", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
@@ -910,6 +936,80 @@ class Context:
                                                _p(A), A.shape[1], None if st is None else C.byref(st)),
                   "bic_bsvd_initialize")
         return None if st is None else st.value
+
+    def bsvd_model_weights(self, E, m, D, A, p, out=None):
+        """the weights behind model_codelength, masked at every row's last word: out (device int64
+        [1 + p], made if None) receives |E| in out[0] and, as uint32 pairs in out[1:], |D_k| for k < p and then
+        the users of atom k for k < p. Enqueues only -> out (model_weights_host reads it)."""
+        out = self.empty_i64(1 + p) if out is None else out
+        self._bind_stream()
+        base = out.data_ptr()
+        self._chk(self.lib.bic_bsvd_model_weights(
+            self.h, _p(E), E.shape[0], m, E.shape[1], _p(D) if p else None, p, D.shape[1] if p else 0,
+            _p(A) if p else None, A.shape[1] if p else 0, C.c_void_p(base), C.c_void_p(base + 8) if p else None,
+            C.c_void_p(base + 8 + 4 * p) if p else None), "bic_bsvd_model_weights")
+        return out
+
+    @staticmethod
+    def model_weights_host(out, p):
+        """bsvd_model_weights' out -> (|E|, |D_k| array, users array); a host read"""
+        w = as_u64(out)
+        pairs = w[1:1 + p].view(np.uint32)
+        return int(w[0]), pairs[:p].copy(), pairs[p:2 * p].copy()
+
+    def bsvd_drop_weights(self, E, m, D, A, p, out=None):
+        """out[k] (device int64 [p], made if None) = the masked weight of E ^ (A_k^t D_k) for every atom k: the
+        backward search's removal scores. Enqueues only -> out."""
+        out = self.empty_i64(p) if out is None else out
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_drop_weights(self.h, _p(E), E.shape[0], m, E.shape[1], _p(D), p, D.shape[1],
+                                                 _p(A), A.shape[1], _p(out)), "bic_bsvd_drop_weights")
+        return out
+
+    def bsvd_drop_atom(self, D, m, A, p, k):
+        """atom k out of the model in place: row k of D and column k of A; the caller goes on with p - 1.
+        Enqueues only."""
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_drop_atom(self.h, _p(D), p, m, D.shape[1], _p(A), A.shape[0], A.shape[1], k),
+                  "bic_bsvd_drop_atom")
+
+    def bsvd_append_atom(self, D, m, A, p, atom, coefs):
+        """atom (device int64 [1, words]) becomes row p of D and coefs (device int64 [n, c_wpr], bit 63 of each
+        row) column p of A; D and A have room for them. Enqueues only."""
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_append_atom(self.h, _p(D), p, m, D.shape[1], _p(A), A.shape[0], A.shape[1],
+                                                _p(atom), atom.shape[-1], _p(coefs), coefs.shape[1]),
+                  "bic_bsvd_append_atom")
+
+    def bsvd_model_codelength(self, E, m, D, A, p):
+        """model_codelength(E, D, A) of the reference, with its truncations -> bits (blocks). p = 0: E alone."""
+        n = C.c_uint64(0)
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_model_codelength(
+            self.h, _p(E), E.shape[0], m, E.shape[1], _p(D) if p else None, p, D.shape[1] if p else 0,
+            _p(A) if p else None, A.shape[1] if p else 0, C.byref(n)), "bic_bsvd_model_codelength")
+        return n.value
+
+    def bsvd_learn_mdl(self, search, X, E, m, D, A, p, lmi=0, du=0, mi=0, state=None, trace_cap=4200, status=False):
+        """one MDL model-order search (BSVD_MDL_FORWARD / _BACKWARD / _FULL) from the model of p atoms in E, D
+        (its rows are the capacity) and A, with the inner learner lmi, the dictionary rule du and, for forward
+        and full search, the initialiser mi drawing from the generator state `state` -> (atoms of the result,
+        its code length, the trace as a list of MdlStep.astuple(), the state afterwards). E, D and A receive
+        the result. Blocks. status=True appends the return code and raises only on device errors (BIC_ENOSPC:
+        the forward search ran out of rows of D, the best model so far is in place)."""
+        st = C.c_uint64(0 if state is None else state)
+        p_out, best, nrec = C.c_size_t(0), C.c_uint64(0), C.c_size_t(0)
+        trace = (MdlStep * max(trace_cap, 1))()
+        self._bind_stream()
+        rc = self.lib.bic_bsvd_learn_mdl(self.h, search, lmi, du, mi, _p(X), X.shape[1], _p(E), E.shape[0], m,
+                                         E.shape[1], _p(D), p, D.shape[0], D.shape[1], _p(A), A.shape[1],
+                                         None if state is None else C.byref(st), C.byref(p_out), C.byref(best), trace,
+                                         trace_cap, C.byref(nrec))
+        if not status or rc not in (BIC_OK, BIC_EINVAL, BIC_ENOSPC):
+            self._chk(rc, "bic_bsvd_learn_mdl")
+        steps = [trace[i].astuple() for i in range(min(nrec.value, trace_cap))]
+        out = (p_out.value, best.value, steps, None if state is None else st.value)
+        return out + (rc,) if status else out
 
     def pack_streams(self, slots, plane_bits, dst_words=None):
         n, slot_words = slots.shape

@@ -703,6 +703,104 @@ int bic_bsvd_init_centroids(bic_ctx* ctx, int mi, const uint64_t* E, size_t n, s
 int bic_bsvd_initialize(bic_ctx* ctx, int mi, const uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D,
                         size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* state);
 
+/* ---- MDL model order (bsvd.cpp:1438-1717) -------------------------------------------------------
+ * model_codelength and the three searches that choose the number of atoms: learn_model_mdl_forward_selection,
+ * _backward_selection and _full_search. Layout and pitches as above; E (n x m), D (p x m), A (n x p).
+ *
+ * The four primitives only enqueue on the ctx stream: no host synchronisation, no workgroup ever waits for
+ * another, scratch from the ctx arena sized on first use, so they can be stream-captured after one warm-up call
+ * with the same sizes. Their sums are integer adds: results are run-to-run identical. Every read of E, D and A
+ * is masked at the row's trailing word, as weight() behind copy_row_to / copy_col_to and mul_AtB / add are (they
+ * go through get_block, binmat.h:188-190): dirty padding bits never count. Words past a row's own are neither
+ * read nor written. Domain: 1 <= m <= 1048576, 0 <= p <= 4096, 1 <= n < 2^31, pitches at least the row's
+ * words; anything else is BIC_EINVAL.
+ *
+ * bic_bsvd_model_weights: *we (DEVICE u64) = the weight of E over columns < m; wd[k] (DEVICE u32 x p) = the
+ * weight of D_k over columns < m; wa[k] (DEVICE u32 x p) = the rows with A(i, k) set. p = 0 writes we alone (D,
+ * A, wd and wa may be NULL).
+ * bic_bsvd_drop_weights (p >= 1): w[k] (DEVICE u64 x p) = the masked weight of E ^ (A_k^t D_k), the residual
+ * once atom k is taken out of its users (mul(Ak, true, Dk, false, AkDk); add(AkDk, E, nextE), :1580-1582): the
+ * weight of E plus, over the rows i with A(i, k) set, |E_i ^ D_k| - |E_i|. The work is proportional to A's set
+ * bits times the row's words; D is read where it lies, nothing is staged, so no p x m has to fit anywhere.
+ * bic_bsvd_drop_atom (1 <= p, k < p): in place, row k of D is removed (the rows after it move down one row,
+ * their ceil(m/64) words as they are; row p - 1 is left as it was) and column k of A is removed (in every row
+ * the columns after k move one place towards the MSB, across word boundaries); the vacated column p - 1 and
+ * all padding bits inside the row's ceil(p/64) words become 0. The caller goes on with p - 1.
+ * bic_bsvd_append_atom (0 <= p <= 4095): row p of D = atom (1 x m, DEVICE, masked at m: the new row's padding
+ * bits are zero), column p of A = bit 63 of every row of coefs (n x 1, DEVICE, pitch c_wpr >= 1), and A's
+ * bits after column p inside its ceil((p+1)/64) words are zero. The caller guarantees room: D has a row p and
+ * a_wpr >= ceil((p+1)/64). This is what allocate and two set_submatrix calls leave at :1497-1513, where the
+ * reference's padding is uninitialised memory; this build defines it as zero.
+ *
+ * bic_universal_codelength (host only) is coding.cpp's universal_codelength: n H(r/n) + log2(n)/2, and
+ * log2(n)/2 alone for r = 0 or r >= n. bic_bsvd_model_codelength blocks: it runs bic_bsvd_model_weights, reads
+ * the 1 + 2p numbers back and evaluates :1438-1461 as written: universal_codelength takes 32-bit arguments, so
+ * rows*cols and the weights are truncated to 32 bits (a product that truncates to 0 is BIC_EINVAL); LE is the
+ * double truncated to a u64; LD += double and LA += double convert the running sum to double, add, and truncate
+ * toward zero on every term. *len (HOST) = LE + LD + LA, LE alone for p = 0.
+ *
+ * bic_bsvd_learn_mdl runs one search and blocks. search: BIC_BSVD_MDL_FORWARD, _BACKWARD or _FULL; lmi the
+ * inner learner (BIC_BSVD_LM_*, bic_bsvd_learn_lm with max_iter 0); du its dictionary rule; mi the initialiser
+ * (BIC_BSVD_MI_*, forward and full search only, drawing from *rng_state as bic_bsvd_initialize). X (n x m,
+ * const); E, D (p_cap rows), A (a_wpr >= ceil(p_cap/64)) hold the caller's model of p atoms on entry and receive
+ * the reference's outputs: *p_out atoms (the first *p_out rows of D and ceil(*p_out/64) words of every row of
+ * A; what lies after them is left as it was, or holds the search's intermediate models), *best_len the
+ * reference's return value. All working copies live in the ctx arena. Domain: that of the parts a search uses:
+ * 1 <= p <= p_cap <= 4096; m <= 4096 where an initialiser runs (forward, full), else m <= 1048576; n < 2^31, and
+ * 1 <= n, m <= 1048576 for lmi >= 1; otherwise BIC_EINVAL. The text's behaviour is kept as written, what look
+ * like slips included:
+ *  - lengths and the stuck statistics are unsigned 64-bit (idx_t): sumStuck += currL - bestL wraps,
+ *    dev = int(sumStuck / allStuck) keeps the low 32 bits and is sign-extended in currL + dev < bestL, and
+ *    dif = int(currL) - int(bestL);
+ *  - forward (:1463-1546): the inner learner runs on the caller's model, then every pass initialises ONE atom
+ *    from the current residual (bic_bsvd_initialize with p = 1), appends it, learns and measures; the current
+ *    model grows every pass, accepted or not; ten consecutive rejected passes stop the search. The reference has
+ *    no bound on K: here a pass that would need K + 1 > p_cap stops the call with BIC_ENOSPC (its trace record is
+ *    still produced), and a neighbour rule that finds no non-zero row stops it with bic_bsvd_initialize's
+ *    BIC_EINVAL; either way the best model so far is in the outputs;
+ *  - backward (:1548-1663): the K removal scores of a pass use the caller-visible E, i.e. the BEST model's
+ *    residual and not the current one's, with the current D and A; the score of k is
+ *    model_codelength(E ^ A_k^t D_k, D, A), then -= universal_codelength(M, |D_k|), then -= universal_codelength(N,
+ *    |A_k|), each -= through double and truncated; the smallest k at the minimum wins (strict <) and the start
+ *    value is ~(1UL << (sizeof(idx_t) - 1)) = 0xFFFFFFFFFFFFFF7F; the current model shrinks every pass, accepted
+ *    or not. At K = 1 the candidate is the empty model, scored with the residual the k = 0 score left; if it is
+ *    accepted, *p_out = 0, E = X, and *best_len keeps its previous value (the break precedes the assignment);
+ *  - full search (:1665-1717): k = 20, 40, .. <= p; per k one initialise + learn whose result is thrown away (its
+ *    draws are used up), then 10 repetitions of initialise + learn + length; candL is the minimum of the ten, but
+ *    the model copied out on candL < bestL is the LAST repetition's, not the minimum's; bestL starts at 1 << 30;
+ *    p < 20 leaves E, D and A untouched, *p_out = 0 and *best_len = 1 << 30. (The random_seed arithmetic of
+ *    the loop changes no draw: the generator is seeded once.)
+ * trace (HOST, nullable) receives one bic_bsvd_mdl_step per pass, at most trace_cap of them; *trace_len is the
+ * number of passes run, even when trace_cap is smaller. A record holds what the reference prints at the start
+ * of the pass (K, currL, bestK, bestL, stuck, dif, dev); backward adds the atom it then chose. Full search: one
+ * record per k with K = k, currL = candL, bestK and bestL after the comparison, and the ten lengths in lens. */
+#define BIC_BSVD_MDL_FORWARD 0
+#define BIC_BSVD_MDL_BACKWARD 1
+#define BIC_BSVD_MDL_FULL 2
+typedef struct bic_bsvd_mdl_step {
+  uint64_t K, currL, bestK, bestL, stuck;
+  int32_t dif, dev;
+  uint32_t atom;      /* backward: the atom removed in this pass */
+  uint32_t reserved;
+  uint64_t lens[10];  /* full search: the ten lengths of this k */
+} bic_bsvd_mdl_step;
+double bic_universal_codelength(unsigned n, unsigned r);
+int bic_bsvd_model_weights(bic_ctx* ctx, const uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D,
+                           size_t p, size_t d_wpr, const uint64_t* A, size_t a_wpr, uint64_t* we, uint32_t* wd,
+                           uint32_t* wa);
+int bic_bsvd_drop_weights(bic_ctx* ctx, const uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D,
+                          size_t p, size_t d_wpr, const uint64_t* A, size_t a_wpr, uint64_t* w);
+int bic_bsvd_drop_atom(bic_ctx* ctx, uint64_t* D, size_t p, size_t m, size_t d_wpr, uint64_t* A, size_t n,
+                       size_t a_wpr, size_t k);
+int bic_bsvd_append_atom(bic_ctx* ctx, uint64_t* D, size_t p, size_t m, size_t d_wpr, uint64_t* A, size_t n,
+                         size_t a_wpr, const uint64_t* atom, size_t atom_wpr, const uint64_t* coefs, size_t c_wpr);
+int bic_bsvd_model_codelength(bic_ctx* ctx, const uint64_t* E, size_t n, size_t m, size_t e_wpr, const uint64_t* D,
+                              size_t p, size_t d_wpr, const uint64_t* A, size_t a_wpr, uint64_t* len);
+int bic_bsvd_learn_mdl(bic_ctx* ctx, int search, int lmi, int du, int mi, const uint64_t* X, size_t x_wpr,
+                       uint64_t* E, size_t n, size_t m, size_t e_wpr, uint64_t* D, size_t p, size_t p_cap,
+                       size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* rng_state, size_t* p_out,
+                       uint64_t* best_len, bic_bsvd_mdl_step* trace, size_t trace_cap, size_t* trace_len);
+
 /* ---- kernel timing ------------------------------------------------------------------------
  * When enabled, every kernel launch of this ctx is bracketed by HIP events on the launch stream.
  * bic_prof_collect syncs, writes one line per kernel name ("name launches total_ms\n") into buf

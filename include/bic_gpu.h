@@ -153,6 +153,21 @@ class Device {
   // device by the rule mi (BIC_BSVD_MI_*) and downloaded. state: the generator's state (bic_bsvd_rng_seed), read
   // and advanced by the rules that draw; may be null for BIC_BSVD_MI_PARTITION. E needs at least one row.
   int bsvd_initialize(int mi, const binary_matrix& E, binary_matrix& D, binary_matrix& A, uint64_t* state);
+  // bsvd.cpp:1438-1717, the MDL model order (bic.h "MDL model order"). bsvd_model_codelength: the code length of
+  // the model (E, D, A) in bits, with the reference's truncations; D and A may be empty (no atoms). bsvd_learn_mdl:
+  // one search (BIC_BSVD_MDL_*) with the inner learner lmi, the rule du and, for the forward and the full search,
+  // the initialiser mi drawing from *state. E receives the result's residual, D and A are re-allocated to the
+  // result's atoms where the reference does so: always by the forward and the backward search (an empty result
+  // destroys both), by the full search only when a candidate was taken. The forward search may grow the model
+  // up to p_cap atoms (0: 4096) and returns BIC_ENOSPC beyond, with the best model so far in E, D and A.
+  struct MdlResult {
+    idx_t atoms = 0;       // the result's atoms
+    uint64_t length = 0;   // the reference's return value
+    std::vector<bic_bsvd_mdl_step> trace;  // one record per pass (bic.h)
+  };
+  int bsvd_model_codelength(const binary_matrix& E, const binary_matrix& D, const binary_matrix& A, uint64_t* length);
+  int bsvd_learn_mdl(int search, int lmi, int du, int mi, binary_matrix& X, binary_matrix& E, binary_matrix& D,
+                     binary_matrix& A, uint64_t* state, MdlResult* out, size_t p_cap = 0);
 
  private:
   struct Buf {
