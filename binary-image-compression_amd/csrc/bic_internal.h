@@ -413,6 +413,17 @@ void launch_bsvd_mdl_append_atom(hipStream_t s, uint64_t* D, uint32_t p, uint32_
 void launch_bsvd_mdl_copy(hipStream_t s, uint64_t* dst, uint32_t d_wpr, const uint64_t* src, uint32_t s_wpr,
                           uint32_t rows, uint32_t words);
 
+// The driver's image mode (bic_patch.hip), one launch each: the W x W tiles of a plane as the rows of X (the plane
+// read with get_submatrix's flat word indexing, 1 <= W <= 1024), the rows of X back as tiles (every own word of
+// the plane written, zero padding), and render_mosaic's image of D (n rows as w x w tiles, gn tiles across, a
+// one-pixel gutter; every own word of the irows x icols image written).
+void launch_patches_gather(hipStream_t s, const uint64_t* plane, uint32_t rows, uint32_t cols, uint32_t wpr, uint32_t W,
+                           uint64_t* X, uint32_t x_wpr);
+void launch_patches_scatter(hipStream_t s, const uint64_t* X, uint32_t x_wpr, uint32_t W, uint64_t* plane,
+                            uint32_t rows, uint32_t cols, uint32_t wpr);
+void launch_mosaic(hipStream_t s, const uint64_t* D, uint32_t n, uint32_t d_wpr, uint32_t w, uint32_t gn, uint32_t irows,
+                   uint32_t icols, uint64_t* image, uint32_t i_wpr);
+
 // The growing-dictionary tile coder of compress2_test.cpp:79-129 / compress3_test.cpp:87-149 (bic_dict.hip).
 // The plane is only read. Everything below `arena` is carved from the scratch by dict_carve, which also
 // puts arena arrays in the place of null per-tile outputs.

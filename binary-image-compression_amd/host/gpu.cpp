@@ -570,6 +570,101 @@ int Device::bsvd_learn_mdl(int search, int lmi, int du, int mi, binary_matrix& X
   return rc;
 }
 
+namespace {
+// M as rows x cols, its storage kept where it already has that shape
+void reshape(binary_matrix& M, idx_t rows, idx_t cols) {
+  if (M.raw_blocks() && M.get_rows() == rows && M.get_cols() == cols) return;
+  M.destroy();
+  M.allocate(rows, cols);
+}
+}  // namespace
+
+int Device::patches(const binary_matrix& I, unsigned W, binary_matrix& X) {
+  BIC_TRY(status_);
+  const idx_t rows = I.get_rows(), cols = I.get_cols(), wpr = I.get_blocks_per_row();
+  if (!rows || !cols || !I.raw_blocks() || W < 1 || W > 1024) return BIC_EINVAL;
+  const idx_t n = ((W - 1 + rows) / W) * ((W - 1 + cols) / W), m = (idx_t)W * W;
+  reshape(X, n, m);
+  const idx_t xw = X.get_blocks_per_row();
+  BIC_TRY(ensure(in_, rows * wpr * 8));
+  BIC_TRY(ensure(out_a_, n * xw * 8));
+  uint64_t* d_I = static_cast<uint64_t*>(in_.p);
+  uint64_t* d_X = static_cast<uint64_t*>(out_a_.p);
+  BIC_TRY(upload(I, d_I));
+  BIC_TRY(bic_patches_gather(ctx_, d_I, rows, cols, wpr, W, d_X, xw));
+  return download(d_X, X);  // (waits for the work)
+}
+
+int Device::unpatch(const binary_matrix& X, unsigned W, binary_matrix& I) {
+  BIC_TRY(status_);
+  const idx_t rows = I.get_rows(), cols = I.get_cols(), wpr = I.get_blocks_per_row();
+  if (!rows || !cols || !I.raw_blocks() || !X.raw_blocks() || W < 1 || W > 1024) return BIC_EINVAL;
+  const idx_t n = ((W - 1 + rows) / W) * ((W - 1 + cols) / W), xw = X.get_blocks_per_row();
+  if (X.get_rows() != n || X.get_cols() != (idx_t)W * W) return BIC_EINVAL;
+  BIC_TRY(ensure(in_, n * xw * 8));
+  BIC_TRY(ensure(out_a_, rows * wpr * 8));
+  uint64_t* d_X = static_cast<uint64_t*>(in_.p);
+  uint64_t* d_I = static_cast<uint64_t*>(out_a_.p);
+  BIC_TRY(upload(X, d_X));
+  BIC_TRY(bic_patches_scatter(ctx_, d_X, xw, W, d_I, rows, cols, wpr));
+  return download(d_I, I);
+}
+
+int Device::mosaic(const binary_matrix& D, binary_matrix& image) {
+  BIC_TRY(status_);
+  const idx_t n = D.get_rows(), m = D.get_cols(), dw = D.get_blocks_per_row();
+  size_t irows = 0, icols = 0;
+  if (!D.raw_blocks()) return BIC_EINVAL;
+  BIC_TRY(bic_mosaic_dims(n, m, &irows, &icols));
+  reshape(image, irows, icols);
+  const idx_t iw = image.get_blocks_per_row();
+  BIC_TRY(ensure(in_, n * dw * 8));
+  BIC_TRY(ensure(out_a_, irows * iw * 8));
+  uint64_t* d_D = static_cast<uint64_t*>(in_.p);
+  uint64_t* d_img = static_cast<uint64_t*>(out_a_.p);
+  BIC_TRY(upload(D, d_D));
+  BIC_TRY(bic_mosaic(ctx_, d_D, n, m, dw, d_img, iw));
+  return download(d_img, image);
+}
+
+int Device::bsvd_learn_image(int mi, int lm, int du, const binary_matrix& I, unsigned W, idx_t p, binary_matrix& X,
+                             binary_matrix& E, binary_matrix& D, binary_matrix& A, uint64_t* state, size_t max_iter,
+                             idx_t* iters, binary_matrix* residual) {
+  BIC_TRY(status_);
+  const idx_t rows = I.get_rows(), cols = I.get_cols(), wpr = I.get_blocks_per_row();
+  if (!rows || !cols || !I.raw_blocks() || W < 1 || W > 64 || p < 1 || p > 4096) return BIC_EINVAL;
+  const idx_t n = ((W - 1 + rows) / W) * ((W - 1 + cols) / W), m = (idx_t)W * W;
+  reshape(X, n, m);
+  reshape(E, n, m);
+  reshape(D, p, m);
+  reshape(A, n, p);
+  if (residual) reshape(*residual, rows, cols);
+  const idx_t xw = X.get_blocks_per_row(), aw = A.get_blocks_per_row();
+  // the plane and, behind it, the residual image share one buffer
+  BIC_TRY(ensure(in_, 2 * rows * wpr * 8));
+  BIC_TRY(ensure(small_, n * xw * 8));
+  BIC_TRY(ensure(out_a_, n * xw * 8));
+  BIC_TRY(ensure(out_b_, p * xw * 8));
+  BIC_TRY(ensure(aux_, n * aw * 8));
+  uint64_t* d_I = static_cast<uint64_t*>(in_.p);
+  uint64_t* d_R = d_I + rows * wpr;
+  uint64_t* d_X = static_cast<uint64_t*>(small_.p);
+  uint64_t* d_E = static_cast<uint64_t*>(out_a_.p);
+  uint64_t* d_D = static_cast<uint64_t*>(out_b_.p);
+  uint64_t* d_A = static_cast<uint64_t*>(aux_.p);
+  BIC_TRY(upload(I, d_I));
+  size_t it = 0;
+  BIC_TRY(bic_bsvd_learn_image(ctx_, mi, lm, du, d_I, rows, cols, wpr, W, d_X, xw, d_E, xw, d_D, p, xw, d_A, aw, state,
+                               max_iter, &it, residual ? d_R : nullptr, wpr));
+  BIC_TRY(download(d_X, X));
+  BIC_TRY(download(d_E, E));
+  BIC_TRY(download(d_D, D));
+  BIC_TRY(download(d_A, A));
+  if (residual) BIC_TRY(download(d_R, *residual));
+  if (iters) *iters = it;
+  return BIC_OK;
+}
+
 Device& default_device() {
   static Device* dev = new Device(0);
   if (dev->status() != BIC_OK) {

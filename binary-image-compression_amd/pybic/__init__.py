@@ -40,6 +40,7 @@ EXPORTS = [
     "bic_bsvd_update_coefficients_wide", "bic_bsvd_update_dictionary_wide", "bic_bsvd_learn_lm",
     "bic_universal_codelength", "bic_bsvd_model_weights", "bic_bsvd_drop_weights", "bic_bsvd_drop_atom",
     "bic_bsvd_append_atom", "bic_bsvd_model_codelength", "bic_bsvd_learn_mdl",
+    "bic_patches_gather", "bic_patches_scatter", "bic_mosaic_dims", "bic_mosaic", "bic_bsvd_learn_image",
 ]
 
 # bic_bsvd_learn_du rules (include/bic.h)
@@ -207,6 +208,12 @@ def load(path=LIB_PATH):
     sig("bic_bsvd_init_partition", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz])
     sig("bic_bsvd_init_centroids", i32, [vp, i32, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_initialize", i32, [vp, i32, vp, sz, sz, sz, vp, sz, sz, vp, sz, C.POINTER(u64)])
+    sig("bic_patches_gather", i32, [vp, vp, sz, sz, sz, C.c_uint, vp, sz])
+    sig("bic_patches_scatter", i32, [vp, vp, sz, C.c_uint, vp, sz, sz, sz])
+    sig("bic_mosaic_dims", i32, [sz, sz, C.POINTER(sz), C.POINTER(sz)])
+    sig("bic_mosaic", i32, [vp, vp, sz, sz, sz, vp, sz])
+    sig("bic_bsvd_learn_image", i32, [vp, i32, i32, i32, vp, sz, sz, sz, C.c_uint, vp, sz, vp, sz, vp, sz, sz, vp, sz,
+                                      C.POINTER(u64), sz, C.POINTER(sz), vp, sz])
     _lib = L
     return L
 
@@ -936,6 +943,58 @@ class Context:
                                                _p(A), A.shape[1], None if st is None else C.byref(st)),
                   "bic_bsvd_initialize")
         return None if st is None else st.value
+
+    def patches_gather(self, plane, cols, W, out=None):
+        """int64 plane [rows, wpr] of `cols` columns -> its W x W tiles as the rows of X [Ny Nx, ceil(W^2/64)] (or
+        `out`, any pitch at least that): bsvd_test.cpp:89-97, the plane read with the flat word indexing.
+        Enqueues only."""
+        rows, wpr = plane.shape
+        if out is None:
+            out = self.empty_i64(((rows + W - 1) // W) * ((cols + W - 1) // W), (W * W + 63) // 64)
+        self._bind_stream()
+        self._chk(self.lib.bic_patches_gather(self.h, _p(plane), rows, cols, wpr, W, _p(out), out.shape[1]),
+                  "bic_patches_gather")
+        return out
+
+    def patches_scatter(self, X, W, rows, cols, out=None):
+        """the rows of X [Ny Nx, x_wpr] back as the W x W tiles of a rows x cols plane [rows, ceil(cols/64)] (or
+        `out`): bsvd_test.cpp:130-139, zero padding. Enqueues only."""
+        out = self.empty_i64(rows, (cols + 63) // 64) if out is None else out
+        self._bind_stream()
+        self._chk(self.lib.bic_patches_scatter(self.h, _p(X), X.shape[1], W, _p(out), rows, cols, out.shape[1]),
+                  "bic_patches_scatter")
+        return out
+
+    def mosaic_dims(self, n, m):
+        """the (rows, cols) of render_mosaic's image of an n x m matrix (host only)"""
+        r, c = C.c_size_t(0), C.c_size_t(0)
+        self._chk(self.lib.bic_mosaic_dims(n, m, C.byref(r), C.byref(c)), "bic_mosaic_dims")
+        return r.value, c.value
+
+    def mosaic(self, D, m, out=None):
+        """render_mosaic's image of D [n, d_wpr] (m bits per row) -> plane [rows, ceil(cols/64)] of mosaic_dims(n, m)
+        (or `out`). Enqueues only."""
+        n = D.shape[0]
+        if out is None:
+            r, c = self.mosaic_dims(n, m)
+            out = self.empty_i64(r, (c + 63) // 64)
+        self._bind_stream()
+        self._chk(self.lib.bic_mosaic(self.h, _p(D), n, m, D.shape[1], _p(out), out.shape[1]), "bic_mosaic")
+        return out
+
+    def bsvd_learn_image(self, plane, cols, W, X, E, D, A, p, mi=0, lm=0, du=0, state=None, max_iter=0, residual=None):
+        """the driver's image mode in one call: gather `plane` into X, E = X, bsvd_initialize(mi), bsvd_learn(lm, du)
+        and, with `residual` (a plane of the image's geometry), the scatter of E into it -> (iterations run, the
+        generator state afterwards or None). X, E [Ny Nx, >= ceil(W^2/64)], D [p, ..], A [Ny Nx, >= ceil(p/64)]."""
+        rows, wpr = plane.shape
+        st = None if state is None else C.c_uint64(state)
+        it = C.c_size_t(0)
+        self._bind_stream()
+        self._chk(self.lib.bic_bsvd_learn_image(
+            self.h, mi, lm, du, _p(plane), rows, cols, wpr, W, _p(X), X.shape[1], _p(E), E.shape[1], _p(D), p,
+            D.shape[1], _p(A), A.shape[1], None if st is None else C.byref(st), max_iter, C.byref(it), _p(residual),
+            0 if residual is None else residual.shape[1]), "bic_bsvd_learn_image")
+        return it.value, None if st is None else st.value
 
     def bsvd_model_weights(self, E, m, D, A, p, out=None):
         """the weights behind model_codelength, masked at every row's last word: out (device int64

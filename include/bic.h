@@ -801,6 +801,60 @@ int bic_bsvd_learn_mdl(bic_ctx* ctx, int search, int lmi, int du, int mi, const 
                        size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* rng_state, size_t* p_out,
                        uint64_t* best_len, bic_bsvd_mdl_step* trace, size_t trace_cap, size_t* trace_len);
 
+/* ---- image mode (bsvd_test.cpp:78-151, util.cpp:53-82) ------------------------------------------
+ * What the driver does around the learner when its input is an image: the W x W tiles of a plane become the
+ * samples, the residual's rows go back into an image, and D or E is drawn as a mosaic of small tiles. Plane
+ * layout and device memory as everywhere; pitches in words. Each of the three kernels is one launch whatever the
+ * size, enqueued on the ctx stream: no host synchronisation, no workgroup ever waits for another, no scratch, so
+ * they can be stream-captured. Domain: rows, cols, n >= 1, rows < 2^31, cols < 2^31 - 1, 1 <= W <= 1024 (W^2 <=
+ * 1048576, the steps' limit on m), 1 <= m <= 1048576, the number of patches and n < 2^31, every pitch at least
+ * the row's own words, no null pointer; anything else is BIC_EINVAL before any launch.
+ *
+ * bic_patches_gather = bsvd_test.cpp:89-97 (copy_submatrix_to + copy_vectorized_to + set_row). Ny = ceil(rows/W),
+ * Nx = ceil(cols/W); patch li = ti Nx + tj is row li of X (N x W^2, N = Ny Nx). Bit r W + c of that row (r, c < W)
+ * is the plane's FLAT bit at row ti W + r, column tj W + c, the flat read of get_submatrix (binmat.cpp:267-298)
+ * that bic_dict_encode and bic_patch_search use: a row is its first ceil(cols/64) words and the word after them
+ * is the next row's first word, so a tile that runs past the right edge continues with the next row's pixels,
+ * as far as it reaches; the pad bits of a row's last word are read as stored; anything past the last row reads
+ * 0; the words between ceil(cols/64) and wpr are never read. The first ceil(W^2/64) words of every row of X are
+ * written, with pad bits 0 (copy_vectorized_to reads its tile through get_block); words up to x_wpr are neither
+ * read nor written. The host binary_matrix of this build defines the reference's shift by 64 in
+ * copy_vectorized_to as 0; with that the three host calls give these words exactly.
+ *
+ * bic_patches_scatter = bsvd_test.cpp:130-139 (copy_row_to + set_vectorized + set_submatrix). Pixel (i, j) with
+ * i < rows, j < cols becomes bit (i mod W) W + (j mod W) of row (i / W) Nx + j / W of X; tile rows and columns
+ * past the image are dropped. Every pixel belongs to exactly one tile, so the plane is written, never read: the
+ * first ceil(cols/64) words of every row, with pad bits 0; the pitch words are left untouched. One difference
+ * from the host: set_submatrix leaves an edge tile's bits in the pad columns it covers (and keeps what the pad
+ * held elsewhere); this build writes zero padding, as the learners do. The valid pixels are the same.
+ *
+ * bic_mosaic_dims (host only) and bic_mosaic = render_mosaic's image (util.cpp:53-82) of D (n x m): w = the
+ * largest integer with w^2 <= m, gn = the smallest with gn^2 >= n, gm = ceil(n / gn), gw = w + 1; the image is
+ * gm gw rows x gn gw columns (*rows, *cols). Pixel (gw i + r, gw j + c) = D(i gn + j, r w + c) for r, c < w and
+ * i gn + j < n; every other bit of the rows' own words, pad bits included, is 0 (zero padding, as every output
+ * here); bits w^2 .. m - 1 of an atom are ignored; the image's pitch words are left untouched. The integer
+ * arithmetic gives what the reference's (idx_t)sqrt(double(m)), ceil(sqrt(double(n))) and ceil(double(n)/gn)
+ * give in this domain: doubles hold these integers exactly, sqrt is correctly rounded, and a quotient that is
+ * not an integer lies at least 2^-16 from one.
+ *
+ * bic_bsvd_learn_image is the body of bsvd_test.cpp:78-145 in image mode, in this order: bic_patches_gather into
+ * X; E = X (the rows' own words, device to device); bic_bsvd_initialize(mi, E, .., rng_state);
+ * bic_bsvd_learn_lm(lm, du, X, E, .., max_iter, iters); and, if residual is not NULL, bic_patches_scatter of E into
+ * it (rows x cols, pitch r_wpr). n = Ny Nx and m = W^2 follow from the image. Its results are bit for bit those of
+ * the five separate calls, *rng_state and *iters included. Its domain is the intersection of theirs: W <= 64 (the
+ * initialisers take m <= 4096), 1 <= p <= 4096, n <= 1048576 for lm >= 1, rng_state as bic_bsvd_initialize; anything
+ * else is BIC_EINVAL before any launch. It blocks where they block and adds no kernel of its own. */
+int bic_patches_gather(bic_ctx* ctx, const uint64_t* plane, size_t rows, size_t cols, size_t wpr, unsigned W,
+                       uint64_t* X, size_t x_wpr);
+int bic_patches_scatter(bic_ctx* ctx, const uint64_t* X, size_t x_wpr, unsigned W, uint64_t* plane, size_t rows,
+                        size_t cols, size_t wpr);
+int bic_mosaic_dims(size_t n, size_t m, size_t* rows, size_t* cols);
+int bic_mosaic(bic_ctx* ctx, const uint64_t* D, size_t n, size_t m, size_t d_wpr, uint64_t* image, size_t i_wpr);
+int bic_bsvd_learn_image(bic_ctx* ctx, int mi, int lm, int du, const uint64_t* plane, size_t rows, size_t cols,
+                         size_t wpr, unsigned W, uint64_t* X, size_t x_wpr, uint64_t* E, size_t e_wpr, uint64_t* D,
+                         size_t p, size_t d_wpr, uint64_t* A, size_t a_wpr, uint64_t* rng_state, size_t max_iter,
+                         size_t* iters, uint64_t* residual, size_t r_wpr);
+
 /* ---- kernel timing ------------------------------------------------------------------------
  * When enabled, every kernel launch of this ctx is bracketed by HIP events on the launch stream.
  * bic_prof_collect syncs, writes one line per kernel name ("name launches total_ms\n") into buf

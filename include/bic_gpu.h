@@ -168,6 +168,19 @@ class Device {
   int bsvd_model_codelength(const binary_matrix& E, const binary_matrix& D, const binary_matrix& A, uint64_t* length);
   int bsvd_learn_mdl(int search, int lmi, int du, int mi, binary_matrix& X, binary_matrix& E, binary_matrix& D,
                      binary_matrix& A, uint64_t* state, MdlResult* out, size_t p_cap = 0);
+  // bsvd_test.cpp:78-151, the driver's image mode (bic.h "image mode"). Each call re-allocates its outputs to
+  // the geometry they need, uploads, runs on the device and downloads. patches: the W x W tiles of I as the rows
+  // of X (ceil(rows/W) ceil(cols/W) x W^2), the loop of :89-97. unpatch: the rows of X back as the tiles of I,
+  // which must have its rows x cols on entry and is overwritten, the loop of :130-139 -- with zero padding, where
+  // set_submatrix leaves an edge tile's bits in the pad columns. mosaic: render_mosaic's image of D (util.cpp:53-82).
+  // bsvd_learn_image: :78-145 as one call (bic_bsvd_learn_image): X and E from I, D and A (p atoms) by the rule
+  // mi, the learner lm with the rule du; residual (nullable) receives E put back as an image of I's geometry.
+  int patches(const binary_matrix& I, unsigned W, binary_matrix& X);
+  int unpatch(const binary_matrix& X, unsigned W, binary_matrix& I);
+  int mosaic(const binary_matrix& D, binary_matrix& image);
+  int bsvd_learn_image(int mi, int lm, int du, const binary_matrix& I, unsigned W, idx_t p, binary_matrix& X,
+                       binary_matrix& E, binary_matrix& D, binary_matrix& A, uint64_t* state, size_t max_iter = 0,
+                       idx_t* iters = nullptr, binary_matrix* residual = nullptr);
 
  private:
   struct Buf {
