@@ -232,6 +232,10 @@ int bic_ctx_set_option(bic_ctx* ctx, int option, long value) {
       ctx->eg_src_off = value == 0;
       ctx->eg_src_one = value == 2;
       return BIC_OK;
+    case BIC_OPT_GRAY_CODE:
+      if (value != 0 && value != 1) return BIC_EINVAL;  // (the setting stays as it was)
+      ctx->gray_code = value == 1;
+      return BIC_OK;
     default: return BIC_EINVAL;
   }
 }

@@ -71,7 +71,8 @@ int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slo
                         (cols + 63) / 64, predict, p00, gray)) || !c.rows)
     return rc;
   c.sink = bic::DecodeCall::kGray;
-  c.gray = {static_cast<uint8_t*>(gray), (uint64_t)pitch, plane0, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0};
+  c.gray = {static_cast<uint8_t*>(gray), (uint64_t)pitch, plane0, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0,
+            ctx->gray_code ? 1 : 0};
   return run_decode(ctx, "decode_gray", c);
 }
 

@@ -14,7 +14,7 @@ int bic_bitplanes_u8_range(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size
   if (rows == 0) return BIC_OK;
   timed(ctx, "bitplanes_u8", [&] {
     bic::launch_bitplanes_u8(ctx->cur, gray, pitch, (uint32_t)rows, (uint32_t)cols, plane0, nplanes, planes,
-                             (uint32_t)wpr);
+                             (uint32_t)wpr, ctx->gray_code);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
@@ -31,7 +31,7 @@ int bic_bitplanes_u16(bic_ctx* ctx, const void* gray, size_t pitch, size_t rows,
   if (rows == 0) return BIC_OK;
   timed(ctx, "bitplanes_u16", [&] {
     bic::launch_raster_planes(ctx->cur, static_cast<const uint8_t*>(gray), 2, (uint32_t)rows, (uint32_t)cols, plane0,
-                              nplanes, planes, (uint32_t)wpr, (uint64_t)pitch, big_endian ? 1 : 0);
+                              nplanes, planes, (uint32_t)wpr, (uint64_t)pitch, big_endian ? 1 : 0, ctx->gray_code);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
@@ -86,7 +86,7 @@ int bic_planes_to_gray(bic_ctx* ctx, const uint64_t* planes, int plane0, int npl
   if (rows == 0) return BIC_OK;
   timed(ctx, "planes_to_gray", [&] {
     bic::launch_planes_gray(ctx->cur, planes, (uint32_t)rows, (uint32_t)cols, (uint32_t)wpr, plane0, nplanes,
-                            sample_bytes, static_cast<uint8_t*>(gray), (uint64_t)pitch);
+                            sample_bytes, static_cast<uint8_t*>(gray), (uint64_t)pitch, ctx->gray_code);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
@@ -102,7 +102,7 @@ int bic_pgm_bitplanes(bic_ctx* ctx, const uint8_t* raster, size_t rows, size_t c
   if (rows == 0) return BIC_OK;
   timed(ctx, "pgm_bitplanes", [&] {
     bic::launch_raster_planes(ctx->cur, raster, maxval < 256 ? 1 : 2, (uint32_t)rows, (uint32_t)cols, plane0, nplanes,
-                              planes, (uint32_t)wpr);
+                              planes, (uint32_t)wpr, 0, 1, ctx->gray_code);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;

@@ -854,7 +854,10 @@ struct GrayArgs {
   uint32_t sel0, sel1;  // blocks_to_samples' byte order (BPS 2)
   uint32_t omask;       // an output word's bits that some plane covers
 };
-template <int BPS, bool VEC, bool SCAN>
+// GC (BIC_OPT_GRAY_CODE): the planes are those of G(v) = v ^ (v >> 1). The accumulators stay G's (they
+// carry the column sums from row to row); the gathered blocks go through ungray_blocks, where the
+// sample bits no plane covers count as 0 before the XOR, not only after it.
+template <int BPS, bool VEC, bool SCAN, bool GC>
 __global__ __launch_bounds__(256) void k_col_apply_gray(GrayArgs a) {
   using T = typename SegWord<kGraySeg>::load;  // kGraySeg bits of a D word
   using RT = typename SegWord<kGraySeg>::reg;
@@ -909,6 +912,7 @@ __global__ __launch_bounds__(256) void k_col_apply_gray(GrayArgs a) {
           else TH[g] |= byte;
         }
       }
+      if constexpr (GC) ungray_blocks<BPS, NG>(TL, TH, ((1u << a.nplanes) - 1u) << a.plane0);
       uint32_t out[BPS * 2 * NG];  // the segment's samples in memory order
       blocks_to_samples<BPS, NG>(TL, TH, a.sel0, a.sel1, out);
 #pragma unroll
@@ -949,14 +953,20 @@ void launch_col_apply_gray(hipStream_t s, const uint64_t* D, const uint64_t* cto
   const uint64_t nt = (uint64_t)((rows + kColChunk - 1) / kColChunk) * ((cols + kGraySeg - 1) / kGraySeg);
   const uint32_t grid = (uint32_t)((nt + 255) / 256);
   const bool vec = reinterpret_cast<uintptr_t>(go.gray) % 16 == 0 && go.pitch % 16 == 0;
-#define BIC_CAG(B, V)                                                  \
-  do {                                                                 \
-    if (ctot) k_col_apply_gray<B, V, true><<<grid, 256, 0, s>>>(a);    \
-    else k_col_apply_gray<B, V, false><<<grid, 256, 0, s>>>(a);        \
+#define BIC_CAGG(B, V, G)                                                 \
+  do {                                                                    \
+    if (ctot) k_col_apply_gray<B, V, true, G><<<grid, 256, 0, s>>>(a);    \
+    else k_col_apply_gray<B, V, false, G><<<grid, 256, 0, s>>>(a);        \
+  } while (0)
+#define BIC_CAG(B, V)                          \
+  do {                                         \
+    if (go.gray_code) BIC_CAGG(B, V, true);    \
+    else BIC_CAGG(B, V, false);                \
   } while (0)
   if (go.bps == 1) { if (vec) BIC_CAG(1, true); else BIC_CAG(1, false); }
   else { if (vec) BIC_CAG(2, true); else BIC_CAG(2, false); }
 #undef BIC_CAG
+#undef BIC_CAGG
 }
 
 // k_col_apply with a P4 sink (bic_decode_pbm: k_col_apply and k_pbm_pack2 in one pass): a thread sums

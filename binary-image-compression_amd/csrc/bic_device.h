@@ -332,6 +332,37 @@ __device__ __forceinline__ void blocks_to_samples(const uint64_t (&TL)[NG], cons
   }
 }
 
+// BIC_OPT_GRAY_CODE on the way back: the blocks hold G's planes (byte b of TL = plane bit b, of TH = bit
+// 8 + b); sample bit b = XOR of G's bits k >= b, a suffix XOR over the blocks' bytes with the high block's
+// total carried into the low one. smask = the sample bits some plane covers (wave-uniform): the others
+// count as 0 before the XOR and are cleared after it.
+template <int BPS, int NG>
+__device__ __forceinline__ void ungray_blocks(uint64_t (&TL)[NG], uint64_t (&TH)[NG], uint32_t smask) {
+  uint64_t ml = 0, mh = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if ((smask >> j) & 1u) ml |= 0xffull << (8 * j);
+    if ((smask >> (8 + j)) & 1u) mh |= 0xffull << (8 * j);
+  }
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    uint64_t carry = 0;
+    if constexpr (BPS == 2) {
+      uint64_t h = TH[g] & mh;
+      h ^= h >> 8;
+      h ^= h >> 16;
+      h ^= h >> 32;
+      carry = (h & 0xffull) * 0x0101010101010101ull;
+      TH[g] = h & mh;
+    }
+    uint64_t l = TL[g] & ml;
+    l ^= l >> 8;
+    l ^= l >> 16;
+    l ^= l >> 32;
+    TL[g] = (l ^ carry) & ml;
+  }
+}
+
 // Bits of the Golomb codewords whose '1' lies in residual word w of a row (plus the end-of-row
 // codeword when eol) -- the length the row encoder's emission produces for that word -- without
 // forming any codeword. n = samples of the plane before the word's first 1, jp = column of the

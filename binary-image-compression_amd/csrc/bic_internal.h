@@ -44,7 +44,8 @@ ChunkScratch carve_chunk_scratch(void* base, const Geom& g);
 
 // Launchers (all asynchronous on `s`). flags[0] = overflow, flags[1] = domain error.
 void launch_bitplanes_u8(hipStream_t s, const uint8_t* gray, size_t pitch, uint32_t rows,
-                         uint32_t cols, int plane0, int nplanes, uint64_t* planes, uint32_t wpr);
+                         uint32_t cols, int plane0, int nplanes, uint64_t* planes, uint32_t wpr,
+                         bool gray_code = false);
 void launch_count(hipStream_t s, const Geom& g, const uint64_t* planes, int predict,
                   const ChunkScratch& cs, uint64_t* resid, uint64_t* weight_out);
 void launch_scan_rows(hipStream_t s, const Geom& g, const ChunkScratch& cs);
@@ -71,6 +72,7 @@ struct GrayOut {
   uint8_t* gray;
   uint64_t pitch;
   int plane0, bps, big_endian;
+  int gray_code = 0;  // BIC_OPT_GRAY_CODE: the planes are G(v)'s, the samples stored are v's
 };
 // bic_decode_pbm: the P4 rasters the decoded planes go to (plane f = frame f at raster + f * stride)
 struct PbmOut {
@@ -270,7 +272,7 @@ uint32_t gray_strips(const Geom& g);
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero,
                       bool store_resid = false, uint64_t* out_e = nullptr, uint64_t eg_stride = 0, int bps = 1,
-                      int big_endian = 0);
+                      int big_endian = 0, bool gray_code = false);
 // the count pass can write the EG stream (FusedRequest::eg_src): rows of whole 64-word strips only
 bool gray_eg_supported(const Geom& g);
 
@@ -318,9 +320,10 @@ void launch_pbm(hipStream_t s, bool pack, const uint8_t* raster_in, uint8_t* ras
 // P5 samples (1 or 2 bytes, any alignment) -> planes plane0.. (bic_raster.hip); pitch: bytes per row
 // (0: cols * bpp, a P5 raster); big_endian: the order of two-byte samples (1: pnm.cpp:73)
 void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_t rows, uint32_t cols, int plane0,
-                          int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch = 0, int big_endian = 1);
+                          int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch = 0, int big_endian = 1,
+                          bool gray_code = false);
 void launch_planes_gray(hipStream_t s, const uint64_t* planes, uint32_t rows, uint32_t cols, uint32_t wpr, int plane0,
-                        int nplanes, int bps, uint8_t* gray, uint64_t pitch);
+                        int nplanes, int bps, uint8_t* gray, uint64_t pitch, bool gray_code = false);
 
 // GF(2) algebra (bic_gf2.hip). Both launches spread their rows over gridDim.y (at most 65,535): the transpose
 // four 64-row blocks per unit, the product 256 rows per unit, so either takes at most kGf2MaxRows source rows

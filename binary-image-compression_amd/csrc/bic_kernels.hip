@@ -35,7 +35,8 @@ __device__ __forceinline__ uint64_t transpose8x8(uint64_t x) {
   return x;
 }
 
-template <bool VEC>
+// GC (BIC_OPT_GRAY_CODE): the planes of G(v) = v ^ (v >> 1), formed on the bytes before the transposes.
+template <bool VEC, bool GC>
 __global__ __launch_bounds__(kBlock) void k_bitplanes_u8(const uint8_t* __restrict__ gray, size_t pitch,
                                                          uint32_t rows, uint32_t cols, uint32_t used,
                                                          int plane0, int nplanes, uint64_t* __restrict__ planes,
@@ -65,6 +66,10 @@ __global__ __launch_bounds__(kBlock) void k_bitplanes_u8(const uint8_t* __restri
       px[g8] = v;
     }
   }
+  if constexpr (GC) {
+#pragma unroll
+    for (int g8 = 0; g8 < 8; ++g8) px[g8] ^= (px[g8] >> 1) & 0x7f7f7f7f7f7f7f7full;
+  }
   uint64_t T[8];
 #pragma unroll
   for (int g8 = 0; g8 < 8; ++g8) T[g8] = transpose8x8(bswap64(px[g8]));  // byte b = plane b's 8 bits
@@ -82,15 +87,15 @@ __global__ __launch_bounds__(kBlock) void k_bitplanes_u8(const uint8_t* __restri
 }
 
 void launch_bitplanes_u8(hipStream_t s, const uint8_t* gray, size_t pitch, uint32_t rows,
-                         uint32_t cols, int plane0, int nplanes, uint64_t* planes, uint32_t wpr) {
+                         uint32_t cols, int plane0, int nplanes, uint64_t* planes, uint32_t wpr, bool gray_code) {
   const uint32_t used = (cols + 63) / 64;
   const uint64_t waves = (uint64_t)rows * ((used + 63) / 64);
   const uint32_t grid = (uint32_t)((waves + kWaves - 1) / kWaves);
   const bool vec = (pitch % 16 == 0) && (((uintptr_t)gray) % 16 == 0);
-  if (vec)
-    k_bitplanes_u8<true><<<grid, kBlock, 0, s>>>(gray, pitch, rows, cols, used, plane0, nplanes, planes, wpr);
-  else
-    k_bitplanes_u8<false><<<grid, kBlock, 0, s>>>(gray, pitch, rows, cols, used, plane0, nplanes, planes, wpr);
+#define BIC_BP(V, G) k_bitplanes_u8<V, G><<<grid, kBlock, 0, s>>>(gray, pitch, rows, cols, used, plane0, nplanes, planes, wpr)
+  if (gray_code) { if (vec) BIC_BP(true, true); else BIC_BP(false, true); }
+  else { if (vec) BIC_BP(true, false); else BIC_BP(false, false); }
+#undef BIC_BP
 }
 
 // ------------------------------------------------------------------------------------
@@ -696,6 +701,14 @@ __device__ __forceinline__ void load64_mis(const uint8_t* src, uint4 (&v)[4]) {
 #undef BIC_MIS_CASE
 }
 
+// G(v) = v ^ (v >> 1) on the 64 one-byte samples of a lane
+__device__ __forceinline__ void gray4(uint4 (&v)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    v[q] = make_uint4(v[q].x ^ ((v[q].x >> 1) & 0x7f7f7f7fu), v[q].y ^ ((v[q].y >> 1) & 0x7f7f7f7fu),
+                      v[q].z ^ ((v[q].z >> 1) & 0x7f7f7f7fu), v[q].w ^ ((v[q].w >> 1) & 0x7f7f7f7fu));
+}
+
 // 64 two-byte samples (128 bytes) of a lane: the row's and the row above's, loaded once for both
 // byte groups (k_gray_strips16, one wave per (row, strip))
 struct Raw16 {
@@ -706,13 +719,18 @@ struct Raw16 {
 // uniform) of the sample, the low or the high one by the byte order -- and from there works as on an
 // 8-bit image: a lane's 64 pixels are 128 bytes, v_perm_b32 keeps the 64 it needs.
 // (S16 = 2: the samples of rows r0 - 1 and r0 come preloaded in `pre`, one row per wave)
-template <bool PREDICT, bool FULL, bool STORE_R, bool NP8, bool EGS, bool MIS = false, int S16 = 0>
+// GC (BIC_OPT_GRAY_CODE): every byte read -- the word's pixels, the pixel before the strip, the next
+// segment's byte -- becomes its byte of G(v) = v ^ (v >> 1) before the plane0 shift. G is linear over
+// XOR, so the med of the bytes is the med of G's planes. A two-byte sample's low byte takes bit 0 of
+// its high byte into bit 7 (lo16: the wave's group is the low byte's; a second v_perm_b32 with the
+// other selector).
+template <bool PREDICT, bool FULL, bool STORE_R, bool NP8, bool EGS, bool MIS = false, int S16 = 0, bool GC = false>
 __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray, size_t pitch, const Geom& g,
                                                 uint32_t ns, uint32_t s, uint32_t r0, uint32_t plane0,
                                                 uint64_t* __restrict__ planes, uint32_t* __restrict__ sones,
                                                 int4* __restrict__ krec, uint32_t* __restrict__ kpos, uint32_t* tw,
                                                 uint64_t* __restrict__ out_e, uint64_t eg_stride, uint32_t bo = 0,
-                                                const Raw16* pre = nullptr) {
+                                                const Raw16* pre = nullptr, uint32_t lo16 = 0) {
   const int lane = lane_id();
   const int np = NP8 ? 8 : (int)g.nplanes;
   const uint32_t w = s * 64 + lane;
@@ -743,11 +761,21 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
       }
       // byte bo of four samples (two dwords) -> one dword (k_raster_planes<2>'s selectors)
       const uint32_t sel = bo ? 0x07050301u : 0x06040200u;
+      // (GC: the byte's own G, and for the low byte's group -- lo16, wave-uniform -- bit 7 of G's low byte,
+      // v7 ^ v8: bit 0 of the sample's other byte, picked with the other selector. Dword by dword, so that
+      // no second pass keeps the 128 raw bytes alive beside the 64 picked ones)
+      auto pick = [&](uint32_t hi2, uint32_t lo2) {
+        uint32_t x = __builtin_amdgcn_perm(hi2, lo2, sel);
+        if constexpr (GC) {
+          x ^= (x >> 1) & 0x7f7f7f7fu;
+          if (lo16) x ^= (__builtin_amdgcn_perm(hi2, lo2, sel ^ 0x01010101u) & 0x01010101u) << 7;
+        }
+        return x;
+      };
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        v[q] = make_uint4(__builtin_amdgcn_perm(c[2 * q].y, c[2 * q].x, sel), __builtin_amdgcn_perm(c[2 * q].w, c[2 * q].z, sel),
-                          __builtin_amdgcn_perm(c[2 * q + 1].y, c[2 * q + 1].x, sel),
-                          __builtin_amdgcn_perm(c[2 * q + 1].w, c[2 * q + 1].z, sel));
+        v[q] = make_uint4(pick(c[2 * q].y, c[2 * q].x), pick(c[2 * q].w, c[2 * q].z), pick(c[2 * q + 1].y, c[2 * q + 1].x),
+                          pick(c[2 * q + 1].w, c[2 * q + 1].z));
     } else if constexpr (MIS) {
       if (in) load64_mis(src, v);
       else
@@ -759,6 +787,12 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
     }
     if constexpr (S16) lb = (lane == 0 && s > 0) ? (uint32_t)src[(int)bo - 2] : 0u;  // the sample before the strip
     else lb = (lane == 0 && s > 0) ? (uint32_t)src[-1] : 0u;
+    if constexpr (GC) {
+      if constexpr (!S16) gray4(v);
+      lb ^= lb >> 1;
+      if constexpr (S16 != 0)
+        if (lo16 && lane == 0 && s > 0) lb ^= ((uint32_t)src[(int)(bo ^ 1u) - 2] & 1u) << 7;
+    }
     if (plane0) {  // planes plane0.. of the range: every pixel's bits shifted down (a wave-uniform branch)
       const uint32_t m = 0x01010101u * (0xffu >> plane0);
 #pragma unroll
@@ -802,7 +836,17 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
       const uint8_t* cp = S16 ? gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 8192u) + 2 * lane + bo
                               : gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 4096u) + lane;
       uint32_t cb = cp[0], ub = rn ? cp[-(int64_t)pitch] : 0u;
-      gn = (cb ^ ub) >> plane0;
+      uint32_t gd0 = cb ^ ub;
+      if constexpr (GC) {
+        gd0 ^= gd0 >> 1;
+        if constexpr (S16 != 0)
+          if (lo16) {
+            const int64_t o = 1 - 2 * (int64_t)bo;  // the sample's other byte
+            const uint32_t co = cp[o], uo = rn ? cp[o - (int64_t)pitch] : 0u;
+            gd0 ^= ((co ^ uo) & 1u) << 7;
+          }
+      }
+      gn = gd0 >> plane0;
     }
     // D bits (8 planes per byte) of the pixel left of the word: lane l - 1's last, or the strip's
     // preceding pixel for lane 0 (0 at column 0)
@@ -903,7 +947,7 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
 #ifndef BIC_GRAY_WAVES
 #define BIC_GRAY_WAVES 4
 #endif
-template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false>
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false>
 __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips(const uint8_t* __restrict__ gray, size_t pitch, Geom g,
                                                         uint32_t ns, uint32_t plane0, uint64_t* __restrict__ planes,
                                                         uint32_t* __restrict__ sones, int4* __restrict__ krec,
@@ -921,14 +965,14 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips(const ui
   if (r0 >= g.rows) return;  // whole wave
   // strips wholly inside a row without pad bits (every strip of C3) drop the masks and the lane tests
   if ((s + 1) * 64 <= g.used && g.trail == ~0ull && g.nplanes == 8)
-    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS>(gray, pitch, g, ns, s, r0, plane0, planes, sones, krec, kpos,
-                                                            tw, out_e, eg_stride);
+    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 0, GC>(gray, pitch, g, ns, s, r0, plane0, planes, sones, krec,
+                                                                   kpos, tw, out_e, eg_stride);
   else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
-    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS>(gray, pitch, g, ns, s, r0, plane0, planes, sones, krec, kpos,
-                                                             tw, out_e, eg_stride);
+    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 0, GC>(gray, pitch, g, ns, s, r0, plane0, planes, sones, krec,
+                                                                    kpos, tw, out_e, eg_stride);
   else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
-    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS>(gray, pitch, g, ns, s, r0, plane0, planes, sones, krec,
-                                                                kpos, tw, nullptr, 0);
+    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 0, GC>(gray, pitch, g, ns, s, r0, plane0, planes, sones,
+                                                                       krec, kpos, tw, nullptr, 0);
 }
 
 // Two-byte samples (bic_encode_gray16; pnm.cpp:71-74 big-endian, or the host's uint16_t). The planes
@@ -945,7 +989,7 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips(const ui
 #define BIC_GRAY16_BOTH 1
 #endif
 constexpr bool kGray16Both = BIC_GRAY16_BOTH != 0 && kGrayByteMed && kGrayRowsBM == 1;
-template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false>
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false>
 __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips16(const uint8_t* __restrict__ gray, size_t pitch, Geom g,
                                                           uint32_t ns, uint32_t plane0, uint32_t be,
                                                           uint64_t* __restrict__ planes, uint32_t* __restrict__ sones,
@@ -989,19 +1033,22 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips16(const 
     const uint32_t p0 = h ? max(8u, plane0) - 8u : plane0;  // the group's first plane within its byte
     const uint32_t skip = h ? nlo : 0u;                     // output planes before the group's
     const uint32_t bo = h ^ (be ? 1u : 0u);                 // the group's byte of a sample (big-endian: high first)
+    const uint32_t lo16 = h ? 0u : 1u;                      // (GC: the low byte's bit 7 takes bit 8 in)
     const uint64_t rskip = (uint64_t)skip * g.rows * ns;
     uint64_t* pl = planes + (uint64_t)skip * g.plane_words;
     uint64_t* oe = out_e + (uint64_t)skip * eg_stride;
     if ((s + 1) * 64 <= g.used && g.trail == ~0ull && gg.nplanes == 8)
-      gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, S>(gray, pitch, gg, ns, s, r0, p0, pl, sones + rskip,
-                                                                 krec + rskip, kpos + rskip, tw, oe, eg_stride, bo, &raw);
+      gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, S, GC>(gray, pitch, gg, ns, s, r0, p0, pl, sones + rskip,
+                                                                     krec + rskip, kpos + rskip, tw, oe, eg_stride, bo,
+                                                                     &raw, lo16);
     else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
-      gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, S>(gray, pitch, gg, ns, s, r0, p0, pl, sones + rskip,
-                                                                  krec + rskip, kpos + rskip, tw, oe, eg_stride, bo, &raw);
+      gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, S, GC>(gray, pitch, gg, ns, s, r0, p0, pl, sones + rskip,
+                                                                      krec + rskip, kpos + rskip, tw, oe, eg_stride, bo,
+                                                                      &raw, lo16);
     else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
-      gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, S>(gray, pitch, gg, ns, s, r0, p0, pl, sones + rskip,
-                                                                     krec + rskip, kpos + rskip, tw, nullptr, 0, bo,
-                                                                     &raw);
+      gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, S, GC>(gray, pitch, gg, ns, s, r0, p0, pl,
+                                                                         sones + rskip, krec + rskip, kpos + rskip, tw,
+                                                                         nullptr, 0, bo, &raw, lo16);
   };
   if constexpr (BOTH) {  // (the LDS table reused: gray_strip_rows ends every row with a wave fence + barrier)
     if (nlo) group(0);
@@ -1022,7 +1069,7 @@ bool gray_rows_supported(const Geom& g, const void* gray, size_t pitch, const vo
 
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero, bool store_resid,
-                      uint64_t* out_e, uint64_t eg_stride, int bps, int big_endian) {
+                      uint64_t* out_e, uint64_t eg_stride, int bps, int big_endian, bool gray_code) {
   const uint32_t ns = gray_strips(g);
   const uint32_t rpw = predict && store_resid ? gray_rows_per_wave<true, true>() : gray_rows_per_wave<true, false>();
   const uint64_t units = (uint64_t)(g.rows + rpw - 1) / rpw;  // row groups per strip
@@ -1032,15 +1079,20 @@ void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Ge
   const uint32_t ngrp = bps == 2 && !both && plane0 < 8 && plane0 + (int)g.nplanes > 8 ? 2u : 1u;
   const uint32_t grid = (uint32_t)((units * ns * ngrp + kWaves - 1) / kWaves);
   const bool egs = out_e && predict && store_resid && gray_eg_supported(g);
-#define BIC_GS(P, R, E, M)                                                                                         \
+#define BIC_GSG(P, R, E, M, G)                                                                                     \
   do {                                                                                                             \
     if (bps == 2)                                                                                                  \
-      k_gray_strips16<P, R, E, M><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0,                    \
-                                                          big_endian ? 1u : 0u, planes, sones, krec, kpos, zero,   \
-                                                          out_e, eg_stride);                                       \
+      k_gray_strips16<P, R, E, M, G><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0,                 \
+                                                             big_endian ? 1u : 0u, planes, sones, krec, kpos,      \
+                                                             zero, out_e, eg_stride);                              \
     else                                                                                                           \
-      k_gray_strips<P, R, E, M><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes, sones, krec, \
-                                                        kpos, zero, out_e, eg_stride);                             \
+      k_gray_strips<P, R, E, M, G><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes, sones,    \
+                                                           krec, kpos, zero, out_e, eg_stride);                    \
+  } while (0)
+#define BIC_GS(P, R, E, M)                             \
+  do {                                                 \
+    if (gray_code) BIC_GSG(P, R, E, M, true);          \
+    else BIC_GSG(P, R, E, M, false);                   \
   } while (0)
 #define BIC_GS2(P, R) { if (mis) BIC_GS(P, R, false, true); else BIC_GS(P, R, false, false); }
   if (egs) { if (mis) BIC_GS(true, true, true, true); else BIC_GS(true, true, true, false); }
@@ -1048,6 +1100,7 @@ void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Ge
   else BIC_GS2(false, false)  // without prediction R = P
 #undef BIC_GS2
 #undef BIC_GS
+#undef BIC_GSG
 }
 
 void launch_med_rows(hipStream_t s, const Geom& g, const uint64_t* planes, int predict, uint64_t* resid,

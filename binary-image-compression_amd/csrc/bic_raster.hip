@@ -70,7 +70,9 @@ __global__ __launch_bounds__(256) void k_pbm_pack2(const uint64_t* __restrict__ 
 // k_bitplanes_u8 per byte column.
 // Rows of `pitch` bytes (a P5 raster: cols * BPP); selL / selH: the v_perm_b32 selectors of a two-byte
 // sample's low and high bytes (wave-uniform: big-endian or the host's order).
-template <int BPP>
+// GC (BIC_OPT_GRAY_CODE): the planes of G(v) = v ^ (v >> 1) on the whole sample -- bit 7 of the low byte
+// takes bit 0 of the high byte in.
+template <int BPP, bool GC>
 __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict__ base, uint32_t off, uint32_t rows,
                                                        uint32_t cols, int plane0, int nplanes,
                                                        uint64_t* __restrict__ planes, uint32_t wpr, uint64_t pitch,
@@ -97,6 +99,13 @@ __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict
                __builtin_amdgcn_perm((uint32_t)(a >> 32), (uint32_t)a, selL);
       hi8[g] = ((uint64_t)__builtin_amdgcn_perm((uint32_t)(b >> 32), (uint32_t)b, selH) << 32) |
                __builtin_amdgcn_perm((uint32_t)(a >> 32), (uint32_t)a, selH);
+    }
+  }
+  if constexpr (GC) {
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      lo8[g] ^= ((lo8[g] >> 1) & 0x7f7f7f7f7f7f7f7full) ^ ((hi8[g] & 0x0101010101010101ull) << 7);
+      hi8[g] ^= (hi8[g] >> 1) & 0x7f7f7f7f7f7f7f7full;
     }
   }
   const uint32_t valid = min(64u, cols - 64 * w);
@@ -127,7 +136,9 @@ __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict
 // transpose (an involution) turns it back into 8 samples' bytes. BPS 1: one byte per sample; BPS 2:
 // two bytes big-endian (the P5 layout write_p5_data uses for maxval >= 256, pnm.cpp:111-124).
 // 16-byte stores when the row's bytes are 16-byte aligned (VEC), byte stores otherwise.
-template <int BPS, bool VEC>
+// GC (BIC_OPT_GRAY_CODE): the planes are G's; sample bit b = XOR of the planes k >= b (bits no plane
+// covers count as 0), a suffix XOR over the blocks' bytes, then masked to the bits the planes cover.
+template <int BPS, bool VEC, bool GC>
 __global__ __launch_bounds__(256) void k_planes_gray(const uint64_t* __restrict__ planes, uint32_t rows, uint32_t cols,
                                                      uint32_t wpr, int plane0, int nplanes, uint8_t* __restrict__ gray,
                                                      uint64_t pitch) {
@@ -151,6 +162,10 @@ __global__ __launch_bounds__(256) void k_planes_gray(const uint64_t* __restrict_
       if (sb < 8) TL[g] |= byte;
       else TH[g] |= byte;
     }
+  }
+  if constexpr (GC) {
+    const uint32_t smask = ((1u << nplanes) - 1u) << plane0;
+    ungray_blocks<BPS, 8>(TL, TH, smask);
   }
   uint32_t out[BPS * 16];  // the 64 samples' bytes in file order
 #pragma unroll
@@ -181,15 +196,21 @@ __global__ __launch_bounds__(256) void k_planes_gray(const uint64_t* __restrict_
 }
 
 void launch_planes_gray(hipStream_t s, const uint64_t* planes, uint32_t rows, uint32_t cols, uint32_t wpr, int plane0,
-                        int nplanes, int bps, uint8_t* gray, uint64_t pitch) {
+                        int nplanes, int bps, uint8_t* gray, uint64_t pitch, bool gray_code) {
   const uint64_t waves = (uint64_t)rows * ((cols + 4095) / 4096);
   const uint32_t grid = (uint32_t)((waves + 3) / 4);
   if (!grid) return;
   const bool vec = reinterpret_cast<uintptr_t>(gray) % 16 == 0 && pitch % 16 == 0;
-#define BIC_PG(B, V) k_planes_gray<B, V><<<grid, 256, 0, s>>>(planes, rows, cols, wpr, plane0, nplanes, gray, pitch)
+#define BIC_PGG(B, V, G) k_planes_gray<B, V, G><<<grid, 256, 0, s>>>(planes, rows, cols, wpr, plane0, nplanes, gray, pitch)
+#define BIC_PG(B, V)                        \
+  do {                                      \
+    if (gray_code) BIC_PGG(B, V, true);     \
+    else BIC_PGG(B, V, false);              \
+  } while (0)
   if (bps == 1) { if (vec) BIC_PG(1, true); else BIC_PG(1, false); }
   else { if (vec) BIC_PG(2, true); else BIC_PG(2, false); }
 #undef BIC_PG
+#undef BIC_PGG
 }
 
 void launch_pbm(hipStream_t s, bool pack, const uint8_t* raster_in, uint8_t* raster_out, const uint64_t* plane_in,
@@ -207,7 +228,7 @@ void launch_pbm(hipStream_t s, bool pack, const uint8_t* raster_in, uint8_t* ras
 }
 
 void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_t rows, uint32_t cols, int plane0,
-                          int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch, int big_endian) {
+                          int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch, int big_endian, bool gray_code) {
   const uintptr_t r = reinterpret_cast<uintptr_t>(raster);
   if (!pitch) pitch = (uint64_t)cols * bpp;
   const uint32_t selL = big_endian ? 0x07050301u : 0x06040200u, selH = big_endian ? 0x06040200u : 0x07050301u;
@@ -215,12 +236,11 @@ void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_
   const uint64_t waves = (uint64_t)rows * ((cols + 4095) / 4096);
   const uint32_t grid = (uint32_t)((waves + 3) / 4);
   if (!grid) return;
-  if (bpp == 1)
-    k_raster_planes<1><<<grid, 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr, pitch,
-                                            selL, selH);
-  else
-    k_raster_planes<2><<<grid, 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr, pitch,
-                                            selL, selH);
+#define BIC_RP(B, G) \
+  k_raster_planes<B, G><<<grid, 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr, pitch, selL, selH)
+  if (gray_code) { if (bpp == 1) BIC_RP(1, true); else BIC_RP(2, true); }
+  else { if (bpp == 1) BIC_RP(1, false); else BIC_RP(2, false); }
+#undef BIC_RP
 }
 
 }  // namespace bic

@@ -644,6 +644,12 @@ class Context:
         planes in a context buffer; 2: the EG source with one emission kernel for every row class"""
         self._chk(self.lib.bic_ctx_set_option(self.h, 6, int(on)), "bic_ctx_set_option")
 
+    def set_gray_code(self, on=True):
+        """binary-reflected Gray coding of the samples, G(v) = v ^ (v >> 1), in every call that maps
+        samples to planes, and its inverse in every call that maps planes to samples
+        (BIC_OPT_GRAY_CODE, default off)"""
+        self._chk(self.lib.bic_ctx_set_option(self.h, 7, int(on)), "bic_ctx_set_option")
+
     def set_multipass(self, on=True):
         self._chk(self.lib.bic_ctx_set_option(self.h, 1, int(on)), "bic_ctx_set_option")
 

@@ -97,6 +97,22 @@ int bic_reserve(bic_ctx* ctx, int nplanes, size_t rows, size_t cols);
  * streams: a cross-check and A/B hook); 2: the EG source with one emission kernel for every row
  * class instead of one per class (A/B hook). */
 #define BIC_OPT_EG_SOURCE 6
+/* BIC_OPT_GRAY_CODE = 1: binary-reflected Gray coding of the samples before they are split into
+ * planes, G(v) = v ^ (v >> 1) on the whole sample (8 or 16 bits): a smooth ramp crossing 127 -> 128
+ * flips one plane instead of eight. 0 (default): the natural binary code, every call as it was. Any
+ * other value is BIC_EINVAL and leaves the setting as it was.
+ *  - Samples to planes (bic_bitplanes_u8, _u8_range, _u16, bic_pgm_bitplanes, bic_encode_gray, _range,
+ *    _packed, bic_encode_gray16, _packed): output plane b is bit plane0 + b of G(v); planes, streams,
+ *    bit counts, offsets and the row index equal those of the same call with the option off on an image
+ *    whose samples are G(v). For 16-bit samples bit 7 of G is v7 ^ v8, whatever the range.
+ *  - Planes to samples (bic_planes_to_gray, bic_decode_gray): the sample assembled from the given
+ *    planes (bits no plane covers taken as 0) goes through the inverse, v_b = XOR of g_k over k >= b,
+ *    and is then masked to the bits the planes cover. The covered bits are the image's own exactly when
+ *    the range reaches up to the highest non-zero plane of G: dropping low planes is allowed, dropping
+ *    high ones is not invertible.
+ * Calls that take or return planes only (bic_encode_planes*, bic_decode_planes, the PBM calls) are
+ * untouched. */
+#define BIC_OPT_GRAY_CODE 7
 int bic_ctx_set_option(bic_ctx* ctx, int option, long value);
 
 /* ---- a2: bitplane extraction (bitplane_tool.cpp:24-30) -----------------------------------
