@@ -1,5 +1,5 @@
-// bic_capi_decode.cpp -- the decoders' entry points (bic_decode.hip): streams to planes, to gray samples,
-// to P4 rasters. The three differ in their sink alone.
+// bic_capi_decode.cpp -- the decoders' entry points (bic_decode.hip): streams to planes, to gray or RGB samples,
+// to P4 rasters. They differ in their sink alone.
 #include "bic_ctx.h"
 
 namespace {
@@ -74,6 +74,21 @@ int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slo
   c.gray = {static_cast<uint8_t*>(gray), (uint64_t)pitch, plane0, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0,
             ctx->gray_code ? 1 : 0};
   return run_decode(ctx, "decode_gray", c);
+}
+
+int bic_decode_rgb(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                   const uint64_t* plane_bits, const uint64_t* index, int plane0, int nplanes, size_t rows, size_t cols,
+                   int predict, const uint8_t* p00, uint8_t* rgb, size_t pitch) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 || cols > SIZE_MAX / 4 || pitch < 3 * cols) return BIC_EINVAL;
+  bic::DecodeCall c{};
+  if ((rc = stream_call(c, coder, streams, slot_words, word_off, plane_bits, index, 3 * nplanes, rows, cols,
+                        (cols + 63) / 64, predict, p00, rgb)) || !c.rows)
+    return rc;
+  c.sink = bic::DecodeCall::kRgb;
+  c.rgb = {rgb, (uint64_t)pitch, plane0, ctx->gray_code ? 1 : 0};
+  return run_decode(ctx, "decode_rgb", c);
 }
 
 int bic_decode_pbm(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,

@@ -92,6 +92,39 @@ int bic_planes_to_gray(bic_ctx* ctx, const uint64_t* planes, int plane0, int npl
   return BIC_OK;
 }
 
+int bic_bitplanes_rgb(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t rows, size_t cols, int plane0, int nplanes,
+                      uint64_t* planes, size_t wpr) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 || cols > SIZE_MAX / 4 || pitch < 3 * cols ||
+      (rows && (!rgb || !planes)))
+    return BIC_EINVAL;
+  if (!geom_ok(rows, cols, wpr)) return BIC_EINVAL;
+  if (rows == 0) return BIC_OK;
+  timed(ctx, "bitplanes_rgb", [&] {
+    bic::launch_raster_planes(ctx->cur, rgb, 3, (uint32_t)rows, (uint32_t)cols, plane0, nplanes, planes, (uint32_t)wpr,
+                              (uint64_t)pitch, 0, ctx->gray_code);
+  });
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
+int bic_planes_to_rgb(bic_ctx* ctx, const uint64_t* planes, int plane0, int nplanes, size_t rows, size_t cols,
+                      size_t wpr, uint8_t* rgb, size_t pitch) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8) return BIC_EINVAL;
+  if (!geom_ok(rows, cols, wpr) || cols > SIZE_MAX / 4 || pitch < 3 * cols || (rows && (!planes || !rgb)))
+    return BIC_EINVAL;
+  if (rows == 0) return BIC_OK;
+  timed(ctx, "planes_to_rgb", [&] {
+    bic::launch_planes_gray(ctx->cur, planes, (uint32_t)rows, (uint32_t)cols, (uint32_t)wpr, plane0, nplanes, 3, rgb,
+                            (uint64_t)pitch, ctx->gray_code);
+  });
+  BIC_HIP(hipGetLastError());
+  return BIC_OK;
+}
+
 int bic_pgm_bitplanes(bic_ctx* ctx, const uint8_t* raster, size_t rows, size_t cols, int maxval, int plane0,
                       int nplanes, uint64_t* planes, size_t wpr) {
   int rc = bind(ctx);

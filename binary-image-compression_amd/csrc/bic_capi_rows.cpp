@@ -1,6 +1,6 @@
 // bic_capi_rows.cpp -- the row encoders' entry points (bic_encode_*, bic_row_index, bic_med_residual,
 // the adaptive EG coder): one driver for the staged and look-back encoders (run_fused), three sources
-// (planes, gray samples, P4 rasters) and the multi-pass fallback for rows wider than 16384 columns.
+// (planes, gray or RGB samples, P4 rasters) and the multi-pass fallback for rows wider than 16384 columns.
 #include "bic_ctx.h"
 
 namespace {
@@ -52,7 +52,8 @@ struct Shape {
   size_t rows, cols, wpr;
 };
 // bps: bytes per sample -- 1 (bic_encode_gray*), or 2 (bic_encode_gray16*: big_endian = 1 the P5 order of
-// pnm.cpp:73, 0 the host's uint16_t)
+// pnm.cpp:73, 0 the host's uint16_t), or 3 (bic_encode_rgb*: interleaved R G B pixels of one-byte samples,
+// pnm.cpp:194-239; the call's planes are then three groups, channel c's planes plane0 .. first)
 struct GrayImage {
   const uint8_t* data;
   size_t pitch;
@@ -185,10 +186,11 @@ int encode_planes_impl(bic_ctx* ctx, const uint64_t* planes, const Shape& sh, in
 int encode_gray_impl(bic_ctx* ctx, const GrayImage& img, int plane0, uint64_t* planes, const Shape& sh, int predict,
                      const bic::CoderOut& og, const bic::CoderOut& oe, uint64_t* row_index = nullptr) {
   const int nplanes = sh.nplanes, bps = img.bps;
+  const int nchan = bps == 3 ? 3 : 1, cplanes = nplanes / nchan;  // a sample's planes: of one channel
   const size_t rows = sh.rows, cols = sh.cols, wpr = sh.wpr;
   int rc = bind(ctx);
   if (rc) return rc;
-  if (plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 * bps || cols > SIZE_MAX / 2 ||
+  if (plane0 < 0 || cplanes < 1 || plane0 + cplanes > (bps == 2 ? 16 : 8) || cols > SIZE_MAX / 4 ||
       img.pitch < cols * (size_t)bps || !geom_ok(rows, cols, wpr) || !outs_ok(og, oe) || (rows && !img.data))
     return BIC_EINVAL;
   const bic::Geom g = bic::make_geom(rows, cols, wpr, nplanes);
@@ -210,7 +212,8 @@ int encode_gray_impl(bic_ctx* ctx, const GrayImage& img, int plane0, uint64_t* p
   const bool store_resid = !planes && predict;
   if (!planes && !eg_src) planes = ctx->rbuf;
   if (!fuse) {  // the same result through the two separate calls
-    if ((rc = bps == 2 ? bic_bitplanes_u16(ctx, img.data, img.pitch, rows, cols, img.big_endian, plane0, nplanes, planes, wpr)
+    if ((rc = bps == 3 ? bic_bitplanes_rgb(ctx, img.data, img.pitch, rows, cols, plane0, cplanes, planes, wpr)
+              : bps == 2 ? bic_bitplanes_u16(ctx, img.data, img.pitch, rows, cols, img.big_endian, plane0, nplanes, planes, wpr)
                        : bic_bitplanes_u8_range(ctx, img.data, img.pitch, rows, cols, plane0, nplanes, planes, wpr)))
       return rc;
     return encode_planes_impl(ctx, planes, sh, predict, og, oe, row_index);
@@ -362,6 +365,24 @@ int bic_encode_gray_packed(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size
                            size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
   if ((out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
   return encode_gray_impl(ctx, {gray, pitch, 1, 0}, plane0, planes, {nplanes, rows, cols, wpr}, predict,
+                          {out_golomb, slot_golomb, bits_golomb, off_golomb}, {out_eg, slot_eg, bits_eg, off_eg},
+                          row_index);
+}
+
+int bic_encode_rgb(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t rows, size_t cols, int plane0, int nplanes,
+                   uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
+                   uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg) {
+  if (nplanes < 1 || nplanes > 8) return BIC_EINVAL;
+  return encode_gray_impl(ctx, {rgb, pitch, 3, 0}, plane0, planes, {3 * nplanes, rows, cols, wpr}, predict,
+                          {out_golomb, slot_golomb, bits_golomb}, {out_eg, slot_eg, bits_eg});
+}
+
+int bic_encode_rgb_packed(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t rows, size_t cols, int plane0,
+                          int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
+                          size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
+                          size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
+  if (nplanes < 1 || nplanes > 8 || (out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
+  return encode_gray_impl(ctx, {rgb, pitch, 3, 0}, plane0, planes, {3 * nplanes, rows, cols, wpr}, predict,
                           {out_golomb, slot_golomb, bits_golomb, off_golomb}, {out_eg, slot_eg, bits_eg, off_eg},
                           row_index);
 }

@@ -969,6 +969,138 @@ void launch_col_apply_gray(hipStream_t s, const uint64_t* D, const uint64_t* cto
 #undef BIC_CAGG
 }
 
+// k_col_apply and k_planes_gray's 3-byte form in one pass (bic_decode_rgb): D -> interleaved R G B samples.
+// The shape of k_col_apply_gray: a lane takes kGraySeg columns of one chunk and holds one accumulator per
+// sample bit of the three channels (24; plane c * nplanes + b is bit plane0 + b of channel c, bits no plane
+// covers read the channel's nearest decoded plane and are cleared by omask), the loads of kRgbRows rows x
+// 24 bits are issued before the first is used. Per row and channel the accumulators' bytes are gathered into
+// the 8 x 8 blocks, transposed (GC: ungray_blocks per channel), and the three channels' bytes interleaved
+// with v_perm_b32 (rgb_interleave4): the lane's 48 bytes are three 16-byte stores when rgb and the pitch are
+// 16-byte aligned and the segment is full (VEC), byte stores otherwise, never past the row's 3 cols bytes.
+struct RgbArgs {
+  const uint64_t* D;     // [3 nplanes][rows][wpr]
+  const uint64_t* ctot;  // [3 nplanes][chunks][wpr] (SCAN)
+  uint32_t rows, cols, wpr;
+  int plane0, nplanes;  // per channel
+  uint8_t* rgb;
+  uint64_t pitch;
+  uint32_t omask;
+};
+template <bool VEC, bool SCAN, bool GC>
+__global__ __launch_bounds__(256) void k_col_apply_rgb(RgbArgs a) {
+  using T = typename SegWord<kGraySeg>::load;
+  using RT = typename SegWord<kGraySeg>::reg;
+  constexpr int Q = kGraySeg, NG = Q / 8, SUB = 64 / Q, NB = 24;
+  constexpr int kRgbRows = 64 / (NB * (int)(sizeof(RT) / 4));  // 64 registers of loads in flight per lane
+  static_assert(kRgbRows >= 1 && Q == 16, "a segment of 16 pixels: 48 bytes, three 16-byte stores");
+  const uint32_t nch = (a.rows + kColChunk - 1) / kColChunk, segs = (a.cols + Q - 1) / Q;
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;  // (nch * segs < 2^26: rows * (cols + 1) < 2^31)
+  if (t >= nch * segs) return;
+  const uint32_t sg = t % segs, c = t / segs;
+  const uint32_t w = sg / SUB, sub = SUB - 1 - sg % SUB;  // the segment's place in its (little-endian) word
+  const uint32_t r0 = c * kColChunk, nr = min(kColChunk, a.rows - r0);
+  const uint32_t rowb = a.wpr * 8;
+  const uint64_t plane_bytes = (uint64_t)a.rows * rowb;
+  const uint32_t c0 = uni_u32(blockIdx.x * 256 / segs);
+  const char* base = reinterpret_cast<const char*>(a.D) + (uint64_t)c0 * kColChunk * rowb;
+  const uint32_t loff = (c - c0) * kColChunk * rowb + w * 8 + sub * (Q / 8);
+  // sample bit sb of channel sb / 8 -> its plane (wave-uniform)
+  auto plane_of = [&](int sb) {
+    return (uint32_t)((sb >> 3) * a.nplanes + min(max((sb & 7) - a.plane0, 0), a.nplanes - 1));
+  };
+  // the loads as a channel's base (three scalar pairs) plus a 32-bit offset: the bit's plane within the channel
+  // (7 planes of < 2^28 bytes: rows * (cols + 1) < 2^31) and the lane's row and segment
+  const char* cbase[3];
+  uint32_t boff[8];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) cbase[ch] = base + (uint64_t)(ch * a.nplanes) * plane_bytes;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) boff[j] = (uint32_t)min(max(j - a.plane0, 0), a.nplanes - 1) * (uint32_t)plane_bytes;
+  RT acc[NB];
+#pragma unroll
+  for (int sb = 0; sb < NB; ++sb)
+    acc[sb] = SCAN ? reinterpret_cast<const T*>(a.ctot + ((uint64_t)plane_of(sb) * nch + c) * a.wpr + w)[sub] : (RT)0;
+  uint8_t* dst = a.rgb + (uint64_t)r0 * a.pitch + (uint64_t)sg * (Q * 3);
+  const uint32_t nbytes = min((uint32_t)Q, a.cols - Q * sg) * 3;
+  const bool vec = VEC && nbytes == Q * 3;
+  const uint32_t smask = ((1u << a.nplanes) - 1u) << a.plane0;
+  for (uint32_t rb = 0; rb < nr; rb += kRgbRows) {
+    RT d[kRgbRows][NB];
+#pragma unroll
+    for (int k = 0; k < kRgbRows; ++k) {
+      const uint32_t voff = loff + min(rb + k, nr - 1) * rowb;
+#pragma unroll
+      for (int sb = 0; sb < NB; ++sb)
+        d[k][sb] = *reinterpret_cast<const T*>(cbase[sb >> 3] + (boff[sb & 7] + voff));
+    }
+#pragma unroll
+    for (int k = 0; k < kRgbRows; ++k) {
+      if (rb + k >= nr) break;
+      uint32_t chan[3][2 * NG];  // per channel: the segment's 16 bytes
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        uint64_t TL[NG], TH[NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) TL[g] = TH[g] = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int sb = 8 * ch + j;
+          acc[sb] = SCAN ? acc[sb] ^ d[k][sb] : d[k][sb];
+#pragma unroll
+          for (int g = 0; g < NG; ++g) TL[g] |= (uint64_t)((acc[sb] >> (Q - 8 - 8 * g)) & 0xffu) << (8 * j);
+        }
+        if constexpr (GC) ungray_blocks<1, NG>(TL, TH, smask);
+        blocks_to_samples<1, NG>(TL, TH, 0, 0, chan[ch]);
+#pragma unroll
+        for (int q = 0; q < 2 * NG; ++q) chan[ch][q] &= a.omask;
+      }
+      uint32_t out[6 * NG];  // the segment's 48 bytes in memory order
+#pragma unroll
+      for (int q = 0; q < 2 * NG; ++q)
+        rgb_interleave4(chan[0][q], chan[1][q], chan[2][q], out[3 * q], out[3 * q + 1], out[3 * q + 2]);
+      uint8_t* p = dst + (uint64_t)(rb + k) * a.pitch;
+      if (vec) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+          reinterpret_cast<uint4*>(p)[q] = make_uint4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
+      } else if (nbytes == Q * 3) {
+#pragma unroll
+        for (int i = 0; i < Q * 3; ++i) p[i] = (uint8_t)(out[i >> 2] >> (8 * (i & 3)));
+      } else {  // the row's last segment
+#pragma unroll
+        for (int i = 0; i < Q * 3; ++i)
+          if ((uint32_t)i < nbytes) p[i] = (uint8_t)(out[i >> 2] >> (8 * (i & 3)));
+      }
+    }
+  }
+}
+
+void launch_col_apply_rgb(hipStream_t s, const uint64_t* D, const uint64_t* ctot, uint32_t rows, uint32_t cols,
+                          uint32_t wpr, uint32_t nplanes, const RgbOut& ro) {
+  RgbArgs a;
+  a.D = D;
+  a.ctot = ctot;
+  a.rows = rows;
+  a.cols = cols;
+  a.wpr = wpr;
+  a.plane0 = ro.plane0;
+  a.nplanes = (int)(nplanes / 3);
+  a.rgb = ro.rgb;
+  a.pitch = ro.pitch;
+  a.omask = ((((1u << a.nplanes) - 1u) << ro.plane0) & 0xffu) * 0x01010101u;
+  const uint64_t nt = (uint64_t)((rows + kColChunk - 1) / kColChunk) * ((cols + kGraySeg - 1) / kGraySeg);
+  const uint32_t grid = (uint32_t)((nt + 255) / 256);
+  const bool vec = reinterpret_cast<uintptr_t>(ro.rgb) % 16 == 0 && ro.pitch % 16 == 0;
+#define BIC_CAR(V, G)                                                  \
+  do {                                                                 \
+    if (ctot) k_col_apply_rgb<V, true, G><<<grid, 256, 0, s>>>(a);     \
+    else k_col_apply_rgb<V, false, G><<<grid, 256, 0, s>>>(a);         \
+  } while (0)
+  if (ro.gray_code) { if (vec) BIC_CAR(true, true); else BIC_CAR(false, true); }
+  else { if (vec) BIC_CAR(true, false); else BIC_CAR(false, false); }
+#undef BIC_CAR
+}
+
 // k_col_apply with a P4 sink (bic_decode_pbm: k_col_apply and k_pbm_pack2 in one pass): a thread sums
 // word column w of one chunk of one plane down its rows (started from the chunk's total, SCAN; without
 // prediction the D buffer holds the planes themselves) and stores bswap64 of each summed word as the
@@ -1026,7 +1158,7 @@ void launch_col_apply_pbm(hipStream_t s, const uint64_t* D, const uint64_t* ctot
 bool decode_supported(uint32_t cols) { return cols >= 1 && (cols + 63) / 64 <= kDecRowWords; }
 
 // The arena: ctot (per plane, column chunk and word) at offset 0, first_row (per plane) behind it, and
-// for a gray or P4 sink the D buffer (nplanes * rows * wpr words) at the next 256-aligned offset
+// for a gray, RGB or P4 sink the D buffer (nplanes * rows * wpr words) at the next 256-aligned offset
 static size_t decode_dbuf_offset(const DecodeCall& c) {
   const uint64_t nch = (c.rows + kColChunk - 1) / kColChunk;
   const size_t head = (size_t)c.nplanes * nch * c.wpr * 8 + (size_t)c.nplanes * 4 + 256;
@@ -1039,7 +1171,7 @@ size_t decode_scratch_bytes(const DecodeCall& c) {
 void launch_decode(hipStream_t s, const DecodeCall& c) {
   const uint32_t rows = c.rows, cols = c.cols, wpr = c.wpr, nplanes = c.nplanes;
   const bool to_planes = c.sink == DecodeCall::kPlanes;
-  // to gray samples or P4 rasters: the row kernels' output goes to the arena's D buffer instead of the
+  // to gray or RGB samples or P4 rasters: the row kernels' output goes to the arena's D buffer instead of the
   // caller's planes
   uint64_t* out = to_planes ? c.planes
                             : reinterpret_cast<uint64_t*>(static_cast<char*>(c.scratch) + decode_dbuf_offset(c));
@@ -1085,6 +1217,8 @@ void launch_decode(hipStream_t s, const DecodeCall& c) {
   }
   if (c.sink == DecodeCall::kGray)
     launch_col_apply_gray(s, out, c.predict ? ctot : nullptr, rows, cols, wpr, nplanes, c.gray);
+  if (c.sink == DecodeCall::kRgb)
+    launch_col_apply_rgb(s, out, c.predict ? ctot : nullptr, rows, cols, wpr, nplanes, c.rgb);
   if (c.sink == DecodeCall::kPbm)
     launch_col_apply_pbm(s, out, c.predict ? ctot : nullptr, rows, cols, wpr, nplanes, c.pbm);
 }

@@ -363,6 +363,22 @@ __device__ __forceinline__ void ungray_blocks(uint64_t (&TL)[NG], uint64_t (&TH)
   }
 }
 
+// Interleaved RGB samples of one byte (P6, maxval < 256: pnm.cpp:194-239). Four pixels are the three
+// dwords d0 d1 d2 (R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3); channel c's four bytes are two v_perm_b32:
+// the first gathers what d0 and d1 hold of them, the second adds d2's. The selector pair is wave-uniform.
+__host__ __device__ constexpr uint32_t rgb_sel1(uint32_t c) { return c == 0 ? 0x00060300u : c == 1 ? 0x00070401u : 0x00000502u; }
+__host__ __device__ constexpr uint32_t rgb_sel2(uint32_t c) { return c == 0 ? 0x05020100u : c == 1 ? 0x06020100u : 0x07040100u; }
+__device__ __forceinline__ uint32_t rgb_pick4(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t s1, uint32_t s2) {
+  return __builtin_amdgcn_perm(d2, __builtin_amdgcn_perm(d1, d0, s1), s2);
+}
+// and back: four pixels' R, G and B bytes (a dword each) -> the three dwords of their 12 bytes
+__device__ __forceinline__ void rgb_interleave4(uint32_t r, uint32_t g, uint32_t b, uint32_t& o0, uint32_t& o1,
+                                                uint32_t& o2) {
+  o0 = __builtin_amdgcn_perm(b, __builtin_amdgcn_perm(g, r, 0x01000400u), 0x03040100u);  // R0 G0 B0 R1
+  o1 = __builtin_amdgcn_perm(b, __builtin_amdgcn_perm(g, r, 0x06020005u), 0x03020500u);  // G1 B1 R2 G2
+  o2 = __builtin_amdgcn_perm(b, __builtin_amdgcn_perm(g, r, 0x00070300u), 0x07020106u);  // B2 R3 G3 B3
+}
+
 // Bits of the Golomb codewords whose '1' lies in residual word w of a row (plus the end-of-row
 // codeword when eol) -- the length the row encoder's emission produces for that word -- without
 // forming any codeword. n = samples of the plane before the word's first 1, jp = column of the

@@ -74,6 +74,14 @@ struct GrayOut {
   int plane0, bps, big_endian;
   int gray_code = 0;  // BIC_OPT_GRAY_CODE: the planes are G(v)'s, the samples stored are v's
 };
+// bic_decode_rgb: the interleaved R G B samples (one byte each) the decoded planes go to; plane c * np + b
+// (np = the call's planes / 3) is bit plane0 + b of channel c
+struct RgbOut {
+  uint8_t* rgb;
+  uint64_t pitch;
+  int plane0;
+  int gray_code = 0;
+};
 // bic_decode_pbm: the P4 rasters the decoded planes go to (plane f = frame f at raster + f * stride)
 struct PbmOut {
   uint8_t* raster;
@@ -88,18 +96,19 @@ struct DecodeCall {
   const uint8_t* p00;
   uint32_t rows, cols, wpr, nplanes;
   int predict;
-  enum { kPlanes, kGray, kPbm } sink;
+  enum { kPlanes, kGray, kPbm, kRgb } sink;
   // the one `sink` names
   uint64_t* planes;
   GrayOut gray;
   PbmOut pbm;
+  RgbOut rgb;
   // the context's: its arena (decode_scratch_bytes of this call), its error flags, and egad_build_dec_nib's
   // table in device memory (the context's byte-table buffer, kLutEgadDec)
   void* scratch;
   uint32_t* flags;
   const uint64_t* egnib;
 };
-// the column totals and the EG first rows; for kGray and kPbm also the D buffer (nplanes * rows * wpr
+// the column totals and the EG first rows; for kGray, kRgb and kPbm also the D buffer (nplanes * rows * wpr
 // words) the row kernels write instead of the caller's planes
 size_t decode_scratch_bytes(const DecodeCall& c);
 void launch_decode(hipStream_t s, const DecodeCall& c);
@@ -268,7 +277,9 @@ uint32_t gray_strips(const Geom& g);
 // wanted; the encoder then reads R with predict off), not the bitplanes P. out_e (with predict, the
 // bitplanes not wanted): the EG stream instead of R (FusedRequest::eg_src; slots of eg_stride
 // words); planes is then unused. bps = 2 (bic_encode_gray16): samples of two bytes, big-endian
-// (pnm.cpp:71-74) or the host's order, planes plane0 .. of 16 (k_gray_strips16)
+// (pnm.cpp:71-74) or the host's order, planes plane0 .. of 16 (k_gray_strips16). bps = 3 (bic_encode_rgb):
+// interleaved RGB pixels of one-byte samples; g.nplanes = 3 np, output plane c * np + k is plane plane0 + k
+// of channel c (k_gray_strips_rgb)
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero,
                       bool store_resid = false, uint64_t* out_e = nullptr, uint64_t eg_stride = 0, int bps = 1,

@@ -719,6 +719,10 @@ struct Raw16 {
 // uniform) of the sample, the low or the high one by the byte order -- and from there works as on an
 // 8-bit image: a lane's 64 pixels are 128 bytes, v_perm_b32 keeps the 64 it needs.
 // (S16 = 2: the samples of rows r0 - 1 and r0 come preloaded in `pre`, one row per wave)
+// S16 = 3 (k_gray_strips_rgb): interleaved RGB pixels of three one-byte samples, the wave takes channel
+// bo (0..2) of each: a lane's 64 pixels are 192 bytes -- twelve 16-byte loads, or load64_mis three times
+// -- and two v_perm_b32 per output dword keep the 64 bytes it needs (rgb_pick4). The pixel before the
+// strip is src[bo - 3], the next segment's byte lies 3 lane + bo into it. No coupling between channels.
 // GC (BIC_OPT_GRAY_CODE): every byte read -- the word's pixels, the pixel before the strip, the next
 // segment's byte -- becomes its byte of G(v) = v ^ (v >> 1) before the plane0 shift. G is linear over
 // XOR, so the med of the bytes is the med of G's planes. A two-byte sample's low byte takes bit 0 of
@@ -738,8 +742,40 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
   const uint64_t mask = FULL ? ~0ull : in ? (w == g.used - 1 ? g.trail : ~0ull) : 0ull;
   // the word's 64 pixels, and (lane 0 of strips s > 0) the pixel before the strip
   auto load = [&](uint32_t row, uint4 (&v)[4], uint32_t& lb) {
-    const uint8_t* src = gray + (uint64_t)row * pitch + (uint64_t)w * (S16 ? 128 : 64);
-    if constexpr (S16) {
+    const uint8_t* src = gray + (uint64_t)row * pitch + (uint64_t)w * (S16 == 3 ? 192 : S16 ? 128 : 64);
+    if constexpr (S16 == 3) {
+      uint4 c[12];  // the 64 pixels
+      if (in) {
+        if constexpr (MIS) {
+#pragma unroll
+          for (int t = 0; t < 3; ++t) {
+            uint4 a[4];
+            load64_mis(src + 64 * t, a);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) c[4 * t + q] = a[q];
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < 12; ++q) c[q] = reinterpret_cast<const uint4*>(src)[q];
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 12; ++q) c[q] = make_uint4(0, 0, 0, 0);
+      }
+      // byte bo of four pixels (three dwords) -> one dword. The other two channels' bytes are in c here: a
+      // per-pixel colour transform in front of the split would take them in pick
+      const uint32_t s1 = rgb_sel1(bo), s2 = rgb_sel2(bo);
+      auto pick = [&](uint32_t d0, uint32_t d1, uint32_t d2) {
+        uint32_t x = rgb_pick4(d0, d1, d2, s1, s2);
+        if constexpr (GC) x ^= (x >> 1) & 0x7f7f7f7fu;
+        return x;
+      };
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        v[q] = make_uint4(pick(c[3 * q].x, c[3 * q].y, c[3 * q].z), pick(c[3 * q].w, c[3 * q + 1].x, c[3 * q + 1].y),
+                          pick(c[3 * q + 1].z, c[3 * q + 1].w, c[3 * q + 2].x),
+                          pick(c[3 * q + 2].y, c[3 * q + 2].z, c[3 * q + 2].w));
+    } else if constexpr (S16) {
       uint4 c[8];  // the 64 samples
       if constexpr (S16 == 2) {
 #pragma unroll
@@ -785,12 +821,13 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = in ? reinterpret_cast<const uint4*>(src)[q] : make_uint4(0, 0, 0, 0);
     }
-    if constexpr (S16) lb = (lane == 0 && s > 0) ? (uint32_t)src[(int)bo - 2] : 0u;  // the sample before the strip
+    if constexpr (S16 == 3) lb = (lane == 0 && s > 0) ? (uint32_t)src[(int)bo - 3] : 0u;  // the pixel before the strip
+    else if constexpr (S16) lb = (lane == 0 && s > 0) ? (uint32_t)src[(int)bo - 2] : 0u;  // the sample before the strip
     else lb = (lane == 0 && s > 0) ? (uint32_t)src[-1] : 0u;
     if constexpr (GC) {
       if constexpr (!S16) gray4(v);
       lb ^= lb >> 1;
-      if constexpr (S16 != 0)
+      if constexpr (S16 == 1 || S16 == 2)
         if (lo16 && lane == 0 && s > 0) lb ^= ((uint32_t)src[(int)(bo ^ 1u) - 2] & 1u) << 7;
     }
     if (plane0) {  // planes plane0.. of the range: every pixel's bits shifted down (a wave-uniform branch)
@@ -802,6 +839,9 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
     }
   };
   constexpr bool BM = kGrayByteMed && PREDICT && STORE_R;
+  // (misaligned RGB rows: the next row's three load64_mis beside this row's plane words and the row
+  // above's do not fit 128 VGPRs -- 20 spilled -- so that form loads a row when it needs it)
+  constexpr bool PF = kGrayPrefetch && !(S16 == 3 && MIS);
   uint64_t up[8];
 #pragma unroll
   for (int b = 0; b < 8; ++b) up[b] = 0;
@@ -826,20 +866,21 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
     const uint32_t row = r0 + r;
     uint4 nxt[4];
     uint32_t nlb = 0;
-    if (kGrayPrefetch && r + 1 < nr) load(row + 1, nxt, nlb);
+    if (PF && r + 1 < nr) load(row + 1, nxt, nlb);
     // EGS: the D byte of pixel `lane` of the segment after this strip (the next strip of the row, or
     // the next row's first pixels; none after the last row)
     const bool lastS = s + 1 == ns;
     const uint32_t rn = lastS ? row + 1 : row;
     uint32_t gn = 0;
     if (EGS && FULL && rn < g.rows) {
-      const uint8_t* cp = S16 ? gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 8192u) + 2 * lane + bo
+      const uint8_t* cp = S16 == 3 ? gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 12288u) + 3 * lane + bo
+                          : S16 ? gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 8192u) + 2 * lane + bo
                               : gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 4096u) + lane;
       uint32_t cb = cp[0], ub = rn ? cp[-(int64_t)pitch] : 0u;
       uint32_t gd0 = cb ^ ub;
       if constexpr (GC) {
         gd0 ^= gd0 >> 1;
-        if constexpr (S16 != 0)
+        if constexpr (S16 == 1 || S16 == 2)
           if (lo16) {
             const int64_t o = 1 - 2 * (int64_t)bo;  // the sample's other byte
             const uint32_t co = cp[o], uo = rn ? cp[o - (int64_t)pitch] : 0u;
@@ -934,7 +975,7 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
     strip_records(tw, np, krec, kpos, sones, (uint64_t)row * ns + s, (uint64_t)g.rows * ns);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the next row rewrites the table
     __builtin_amdgcn_wave_barrier();
-    if constexpr (kGrayPrefetch) {
+    if constexpr (PF) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
       clb = nlb;
@@ -1058,6 +1099,45 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips16(const 
   }
 }
 
+// Interleaved RGB (bic_encode_rgb; pnm.cpp:194-239, one byte per sample). g.nplanes = 3 np: output plane
+// c * np + k is plane plane0 + k of channel c. One wave per (row block, strip, channel): the three channels
+// of a strip are neighbouring waves (of one workgroup, or of two that xcd_remap keeps on one XCD), all load the
+// same 192 bytes per lane (the second and third from L1 / L2) and keep their own 64; gray_strip_rows then runs on that channel's bytes as on an
+// 8-bit image, its plane-indexed outputs advanced by c * np (RGB in one call).
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false>
+__global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_rgb(const uint8_t* __restrict__ rgb, size_t pitch, Geom g,
+                                                            uint32_t ns, uint32_t plane0, uint64_t* __restrict__ planes,
+                                                            uint32_t* __restrict__ sones, int4* __restrict__ krec,
+                                                            uint32_t* __restrict__ kpos, uint32_t* __restrict__ zero,
+                                                            uint64_t* __restrict__ out_e, uint64_t eg_stride) {
+  __shared__ __attribute__((aligned(16))) uint32_t tab[kWaves][1024];  // strip_word_put tables
+  if (blockIdx.x == 0 && threadIdx.x < kZeroWords) zero[threadIdx.x] = 0;  // the encoder's counters
+  const uint32_t wv = wave_id();
+  uint32_t* tw = tab[wv];
+  const uint64_t gw = (uint64_t)xcd_remap(blockIdx.x, gridDim.x) * kWaves + wv;
+  const uint32_t ch = (uint32_t)(gw % 3u);  // the wave's channel
+  const uint64_t gs = gw / 3u;
+  const uint32_t s = (uint32_t)(gs % ns);
+  const uint32_t r0 = (uint32_t)(gs / ns) * gray_rows_per_wave<PREDICT, STORE_R>();
+  if (r0 >= g.rows) return;  // whole wave
+  Geom gg = g;
+  gg.nplanes = g.nplanes / 3u;
+  const uint32_t skip = ch * gg.nplanes;  // output planes before the channel's
+  const uint64_t rskip = (uint64_t)skip * g.rows * ns;
+  uint64_t* pl = planes + (uint64_t)skip * g.plane_words;
+  uint64_t* oe = out_e + (uint64_t)skip * eg_stride;
+  if ((s + 1) * 64 <= g.used && g.trail == ~0ull && gg.nplanes == 8)
+    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 3, GC>(rgb, pitch, gg, ns, s, r0, plane0, pl, sones + rskip,
+                                                                   krec + rskip, kpos + rskip, tw, oe, eg_stride, ch);
+  else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
+    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 3, GC>(rgb, pitch, gg, ns, s, r0, plane0, pl, sones + rskip,
+                                                                    krec + rskip, kpos + rskip, tw, oe, eg_stride, ch);
+  else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
+    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 3, GC>(rgb, pitch, gg, ns, s, r0, plane0, pl,
+                                                                       sones + rskip, krec + rskip, kpos + rskip, tw,
+                                                                       nullptr, 0, ch);
+}
+
 bool gray_eg_supported(const Geom& g) { return g.trail == ~0ull && g.used % 64 == 0 && g.used / 64 <= kMaxStrips; }
 
 // any gray alignment and pitch (rows not 16-byte aligned: load64_mis); every row must hold used * 64
@@ -1076,12 +1156,16 @@ void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Ge
   // (two-byte samples: a wave per byte group that holds planes of the range)
   const bool mis = pitch % 16 != 0 || reinterpret_cast<uintptr_t>(gray) % 16 != 0;  // e.g. a P5 raster in its file
   const bool both = kGray16Both && predict && store_resid && !mis;  // one wave runs both groups
-  const uint32_t ngrp = bps == 2 && !both && plane0 < 8 && plane0 + (int)g.nplanes > 8 ? 2u : 1u;
+  // (three-byte pixels: a wave per channel; g.nplanes is then all three channels' planes)
+  const uint32_t ngrp = bps == 3 ? 3u : bps == 2 && !both && plane0 < 8 && plane0 + (int)g.nplanes > 8 ? 2u : 1u;
   const uint32_t grid = (uint32_t)((units * ns * ngrp + kWaves - 1) / kWaves);
   const bool egs = out_e && predict && store_resid && gray_eg_supported(g);
 #define BIC_GSG(P, R, E, M, G)                                                                                     \
   do {                                                                                                             \
-    if (bps == 2)                                                                                                  \
+    if (bps == 3)                                                                                                  \
+      k_gray_strips_rgb<P, R, E, M, G><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes, sones, \
+                                                               krec, kpos, zero, out_e, eg_stride);                \
+    else if (bps == 2)                                                                                             \
       k_gray_strips16<P, R, E, M, G><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0,                 \
                                                              big_endian ? 1u : 0u, planes, sones, krec, kpos,      \
                                                              zero, out_e, eg_stride);                              \

@@ -72,6 +72,9 @@ __global__ __launch_bounds__(256) void k_pbm_pack2(const uint64_t* __restrict__ 
 // sample's low and high bytes (wave-uniform: big-endian or the host's order).
 // GC (BIC_OPT_GRAY_CODE): the planes of G(v) = v ^ (v >> 1) on the whole sample -- bit 7 of the low byte
 // takes bit 0 of the high byte in.
+// BPP 3 (bic_bitplanes_rgb): interleaved R G B pixels of one-byte samples (P6, pnm.cpp:194-239); the wave
+// takes channel blockIdx.y -- 24 loads, two v_perm_b32 per four pixels (rgb_pick4) -- and writes planes
+// plane0 .. of it as output planes channel * nplanes ..
 template <int BPP, bool GC>
 __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict__ base, uint32_t off, uint32_t rows,
                                                        uint32_t cols, int plane0, int nplanes,
@@ -90,6 +93,13 @@ __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict
   for (int g = 0; g < 8; ++g) {
     if constexpr (BPP == 1) {
       lo8[g] = bytes8(base, p0 + 8 * g, end);
+      hi8[g] = 0;
+    } else if constexpr (BPP == 3) {
+      const uint64_t a = bytes8(base, p0 + 24 * g, end), b = bytes8(base, p0 + 24 * g + 8, end),
+                     c = bytes8(base, p0 + 24 * g + 16, end);
+      const uint32_t s1 = rgb_sel1(blockIdx.y), s2 = rgb_sel2(blockIdx.y);
+      lo8[g] = ((uint64_t)rgb_pick4((uint32_t)(b >> 32), (uint32_t)c, (uint32_t)(c >> 32), s1, s2) << 32) |
+               rgb_pick4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, s1, s2);
       hi8[g] = 0;
     } else {
       const uint64_t a = bytes8(base, p0 + 16 * g, end), b = bytes8(base, p0 + 16 * g + 8, end);
@@ -117,6 +127,7 @@ __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict
     TH[g] = BPP == 2 ? transpose8x8_r(bswap64(hi8[g])) : 0;
   }
   const uint64_t plane_words = (uint64_t)rows * wpr;
+  if constexpr (BPP == 3) planes += (uint64_t)blockIdx.y * nplanes * plane_words;  // the channel's planes
   uint64_t* dst = planes + (uint64_t)row * wpr + w;
   for (int b = 0; b < nplanes; ++b) {
     const int sb = b + plane0;
@@ -138,6 +149,8 @@ __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict
 // 16-byte stores when the row's bytes are 16-byte aligned (VEC), byte stores otherwise.
 // GC (BIC_OPT_GRAY_CODE): the planes are G's; sample bit b = XOR of the planes k >= b (bits no plane
 // covers count as 0), a suffix XOR over the blocks' bytes, then masked to the bits the planes cover.
+// BPS 3 (bic_planes_to_rgb): planes c * nplanes + b are channel c's (plane0 + b); the three channels' bytes
+// of a group of 8 pixels are interleaved R G B with v_perm_b32 (rgb_interleave4), 192 bytes per lane.
 template <int BPS, bool VEC, bool GC>
 __global__ __launch_bounds__(256) void k_planes_gray(const uint64_t* __restrict__ planes, uint32_t rows, uint32_t cols,
                                                      uint32_t wpr, int plane0, int nplanes, uint8_t* __restrict__ gray,
@@ -150,6 +163,43 @@ __global__ __launch_bounds__(256) void k_planes_gray(const uint64_t* __restrict_
   if (w >= used) return;
   const uint64_t plane_words = (uint64_t)rows * wpr;
   const uint64_t* src = planes + (uint64_t)row * wpr + w;
+  if constexpr (BPS == 3) {
+    uint8_t* dst = gray + (uint64_t)row * pitch + (uint64_t)w * 192;
+    const uint32_t valid = min(64u, cols - 64 * w);
+    uint64_t ch[3][8];  // per channel and group: the 8 pixels' bytes, little-endian
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      uint64_t TL[8], TH[8];
+#pragma unroll
+      for (int g = 0; g < 8; ++g) TL[g] = TH[g] = 0;
+      for (int b = 0; b < nplanes; ++b) {
+        const uint64_t v = src[(uint64_t)(c * nplanes + b) * plane_words];
+#pragma unroll
+        for (int g = 0; g < 8; ++g) TL[g] |= ((v >> (56 - 8 * g)) & 0xffull) << (8 * (b + plane0));
+      }
+      if constexpr (GC) ungray_blocks<1, 8>(TL, TH, ((1u << nplanes) - 1u) << plane0);
+#pragma unroll
+      for (int g = 0; g < 8; ++g) ch[c][g] = bswap64(transpose8x8_r(TL[g]));
+    }
+    uint32_t out[48];  // the 64 pixels' bytes in file order
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      rgb_interleave4((uint32_t)ch[0][g], (uint32_t)ch[1][g], (uint32_t)ch[2][g], out[6 * g], out[6 * g + 1],
+                      out[6 * g + 2]);
+      rgb_interleave4((uint32_t)(ch[0][g] >> 32), (uint32_t)(ch[1][g] >> 32), (uint32_t)(ch[2][g] >> 32),
+                      out[6 * g + 3], out[6 * g + 4], out[6 * g + 5]);
+    }
+    if (VEC && valid == 64) {
+#pragma unroll
+      for (int q = 0; q < 12; ++q)
+        reinterpret_cast<uint4*>(dst)[q] = make_uint4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
+      return;
+    }
+#pragma unroll
+    for (int i = 0; i < 192; ++i)
+      if ((uint32_t)i < valid * 3) dst[i] = (uint8_t)(out[i >> 2] >> (8 * (i & 3)));
+    return;
+  }
   uint64_t TL[8], TH[8];
 #pragma unroll
   for (int g = 0; g < 8; ++g) TL[g] = TH[g] = 0;
@@ -208,6 +258,7 @@ void launch_planes_gray(hipStream_t s, const uint64_t* planes, uint32_t rows, ui
     else BIC_PGG(B, V, false);              \
   } while (0)
   if (bps == 1) { if (vec) BIC_PG(1, true); else BIC_PG(1, false); }
+  else if (bps == 3) { if (vec) BIC_PG(3, true); else BIC_PG(3, false); }
   else { if (vec) BIC_PG(2, true); else BIC_PG(2, false); }
 #undef BIC_PG
 #undef BIC_PGG
@@ -236,6 +287,15 @@ void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_
   const uint64_t waves = (uint64_t)rows * ((cols + 4095) / 4096);
   const uint32_t grid = (uint32_t)((waves + 3) / 4);
   if (!grid) return;
+  if (bpp == 3) {  // grid.y: the channel
+    if (gray_code)
+      k_raster_planes<3, true><<<dim3(grid, 3), 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes,
+                                                             wpr, pitch, 0, 0);
+    else
+      k_raster_planes<3, false><<<dim3(grid, 3), 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes,
+                                                              wpr, pitch, 0, 0);
+    return;
+  }
 #define BIC_RP(B, G) \
   k_raster_planes<B, G><<<grid, 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr, pitch, selL, selH)
   if (gray_code) { if (bpp == 1) BIC_RP(1, true); else BIC_RP(2, true); }

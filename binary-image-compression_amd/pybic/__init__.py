@@ -32,6 +32,7 @@ EXPORTS = [
     "bic_gf2_transpose", "bic_gf2_mul", "bic_planes_to_gray", "bic_match_encode_inv", "bic_match_encode_var", "bic_egad_row_index",
     "bic_encode_gray16", "bic_encode_gray16_packed", "bic_bitplanes_u16", "bic_decode_gray",
     "bic_encode_pbm", "bic_encode_pbm_packed", "bic_decode_pbm",
+    "bic_encode_rgb", "bic_encode_rgb_packed", "bic_bitplanes_rgb", "bic_planes_to_rgb", "bic_decode_rgb",
     "bic_bsvd_update_coefficients", "bic_bsvd_update_dictionary", "bic_bsvd_learn",
     "bic_dict_encode", "bic_set_dict_block",
     "bic_bsvd_update_dictionary_proximus", "bic_bsvd_learn_du", "bic_set_bsvd_rounds",
@@ -184,6 +185,11 @@ def load(path=LIB_PATH):
     sig("bic_encode_pbm", i32, [vp, vp, sz, i32, sz, sz, vp, sz, i32, vp, sz, vp, vp, sz, vp])
     sig("bic_encode_pbm_packed", i32, [vp, vp, sz, i32, sz, sz, vp, sz, i32, vp, sz, vp, vp, vp, sz, vp, vp, vp])
     sig("bic_decode_pbm", i32, [vp, i32, vp, sz, vp, vp, vp, i32, sz, sz, i32, vp, vp, sz])
+    sig("bic_encode_rgb", i32, [vp, vp, sz, sz, sz, i32, i32, vp, sz, i32, vp, sz, vp, vp, sz, vp])
+    sig("bic_encode_rgb_packed", i32, [vp, vp, sz, sz, sz, i32, i32, vp, sz, i32, vp, sz, vp, vp, vp, sz, vp, vp, vp])
+    sig("bic_bitplanes_rgb", i32, [vp, vp, sz, sz, sz, i32, i32, vp, sz])
+    sig("bic_planes_to_rgb", i32, [vp, vp, i32, i32, sz, sz, sz, vp, sz])
+    sig("bic_decode_rgb", i32, [vp, i32, vp, sz, vp, vp, vp, i32, i32, sz, sz, i32, vp, vp, sz])
     sig("bic_bsvd_update_coefficients", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_update_dictionary", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_learn", i32, [vp, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
@@ -502,6 +508,102 @@ class Context:
                                                     _p(oe), se, _p(be), _p(fe), _p(row_index)),
                   "bic_encode_gray16_packed")
         return planes, ((og, bg, fg) if golomb else None), ((oe, be, fe) if eg else None)
+
+    def _rgb_args(self, rgb, rows, cols, pitch):
+        """rgb: a uint8 device tensor [rows, cols, 3] (R G B interleaved; pitch = stride(0)), [rows, pitch] with
+        cols given, or raster bytes starting at the first sample with rows, cols (and pitch, default 3 * cols)"""
+        assert rgb.dtype == self.torch.uint8
+        if rgb.dim() == 3:
+            assert rgb.shape[2] == 3 and rgb.stride(2) == 1 and rgb.stride(1) == 3
+            return rgb.shape[0], (rgb.shape[1] if cols is None else cols), rgb.stride(0)
+        if rgb.dim() == 2:
+            assert cols is not None and rgb.stride(1) == 1
+            return rgb.shape[0], cols, rgb.stride(0)
+        assert rows is not None and cols is not None
+        return rows, cols, (3 * cols if pitch is None else pitch)
+
+    def bitplanes_rgb(self, rgb, cols=None, nplanes=8, plane0=0, wpr=None, out=None, rows=None, pitch=None):
+        """bic_bitplanes_rgb: interleaved RGB -> int64 tensor [3 * nplanes, rows, wpr]; plane c * nplanes + k is
+        plane plane0 + k of channel c"""
+        rows, cols, pitch = self._rgb_args(rgb, rows, cols, pitch)
+        wpr = wpr or (cols + 63) // 64
+        out = self.empty_i64(3 * nplanes, rows, wpr) if out is None else out
+        self._bind_stream()
+        self._chk(self.lib.bic_bitplanes_rgb(self.h, _p(rgb), pitch, rows, cols, plane0, nplanes, _p(out), wpr),
+                  "bic_bitplanes_rgb")
+        return out
+
+    def planes_to_rgb(self, planes, cols, plane0=0, out=None, pitch=None):
+        """bic_planes_to_rgb: planes int64 [3 * nplanes, rows, wpr] (bitplanes_rgb's order) -> uint8 device tensor
+        [rows, pitch] of interleaved samples (only the first 3 * cols bytes of a row are written)"""
+        n3, rows, wpr = planes.shape
+        assert n3 % 3 == 0
+        pitch = pitch or 3 * cols
+        out = self.torch.zeros(rows, pitch, dtype=self.torch.uint8, device=self.dev) if out is None else out
+        self._bind_stream()
+        self._chk(self.lib.bic_planes_to_rgb(self.h, _p(planes), plane0, n3 // 3, rows, cols, wpr, _p(out), pitch),
+                  "bic_planes_to_rgb")
+        return out
+
+    def encode_rgb(self, rgb, cols=None, nplanes=8, plane0=0, predict=True, planes=None, slots=(None, None),
+                   outs=(None, None), bits=(None, None), golomb=True, eg=True, store_planes=True, rows=None,
+                   pitch=None, wpr=None):
+        """bic_encode_rgb -> (planes, (out_g, bits_g) or None, (out_e, bits_e) or None), as encode_gray for
+        interleaved RGB (rgb: see _rgb_args): 3 * nplanes planes and streams, entry c * nplanes + k = plane
+        plane0 + k of channel c. wpr: the planes' words per row (default ceil(cols / 64); the one-read count
+        pass needs it even)"""
+        rows, cols, pitch = self._rgb_args(rgb, rows, cols, pitch)
+        n3 = 3 * nplanes
+        wpr = wpr or (cols + 63) // 64
+        if planes is None and store_planes:
+            planes = self.empty_i64(n3, rows, wpr)
+        wpr = planes.shape[-1] if planes is not None else wpr
+        res = []
+        for on, coder, slot, out, b in ((golomb, CODER_GOLOMB, slots[0], outs[0], bits[0]),
+                                        (eg, CODER_EG, slots[1], outs[1], bits[1])):
+            if not on:
+                res.append((None, 0, None))
+                continue
+            slot = slot or self.slot_words(rows, cols, coder)
+            out = self.empty_i64(n3, slot) if out is None else out
+            b = self.empty_i64(n3) if b is None else b
+            res.append((out, slot, b))
+        (og, sg, bg), (oe, se, be) = res
+        self._bind_stream()
+        self._chk(self.lib.bic_encode_rgb(self.h, _p(rgb), pitch, rows, cols, plane0, nplanes, _p(planes), wpr,
+                                          int(predict), _p(og), sg, _p(bg), _p(oe), se, _p(be)), "bic_encode_rgb")
+        return planes, ((og, bg) if golomb else None), ((oe, be) if eg else None)
+
+    def encode_rgb_packed(self, rgb, cols=None, nplanes=8, plane0=0, predict=True, planes=None, golomb=True, eg=True,
+                          slots=(None, None), outs=(None, None), bits=(None, None), offs=(None, None),
+                          row_index=None, store_planes=True, rows=None, pitch=None, wpr=None):
+        """bic_encode_rgb_packed -> (planes, (out_g, bits_g, off_g) or None, (out_e, bits_e, off_e) or None)"""
+        rows, cols, pitch = self._rgb_args(rgb, rows, cols, pitch)
+        n3 = 3 * nplanes
+        wpr = wpr or (cols + 63) // 64
+        if planes is None and store_planes:
+            planes = self.empty_i64(n3, rows, wpr)
+        wpr = planes.shape[-1] if planes is not None else wpr
+        (og, sg, bg, fg), (oe, se, be, fe) = self._packed_bufs(n3, rows, cols, golomb, eg, slots, outs, bits, offs)
+        self._bind_stream()
+        self._chk(self.lib.bic_encode_rgb_packed(self.h, _p(rgb), pitch, rows, cols, plane0, nplanes, _p(planes), wpr,
+                                                 int(predict), _p(og), sg, _p(bg), _p(fg), _p(oe), se, _p(be), _p(fe),
+                                                 _p(row_index)), "bic_encode_rgb_packed")
+        return planes, ((og, bg, fg) if golomb else None), ((oe, be, fe) if eg else None)
+
+    def decode_rgb(self, coder, streams, plane_bits, nplanes, rows, cols, predict=True, word_off=None,
+                   row_index=None, p00=None, plane0=0, out=None, pitch=None):
+        """bic_decode_rgb: the 3 * nplanes streams of encode_rgb (as for decode_planes) -> uint8 device tensor
+        [rows, pitch] of interleaved samples. out: a uint8 device tensor whose first byte is row 0's first (any
+        alignment), rows `pitch` apart; p00: uint8 [3 * nplanes] or None."""
+        pitch = pitch or 3 * cols
+        out = self.torch.zeros(rows, pitch, dtype=self.torch.uint8, device=self.dev) if out is None else out
+        slot = streams.shape[-1] if (word_off is None and streams.dim() == 2) else 0
+        self._bind_stream()
+        self._chk(self.lib.bic_decode_rgb(self.h, coder, _p(streams), slot, _p(word_off), _p(plane_bits),
+                                          _p(row_index), plane0, nplanes, rows, cols, int(predict), _p(p00), _p(out),
+                                          pitch), "bic_decode_rgb")
+        return out
 
     def row_index(self, planes, cols, predict=True, out=None):
         """bic_row_index: int64 [nplanes * rows * 2] (per row: Golomb bit offset, residual 1s before)"""

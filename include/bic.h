@@ -217,6 +217,40 @@ int bic_encode_gray16_packed(bic_ctx* ctx, const void* gray, size_t pitch, size_
                              int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
                              size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
                              size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index);
+/* Interleaved RGB (P6 with maxval < 256, pnm.cpp:194-239) -> streams in one call. rgb = rows of cols
+ * pixels of three one-byte samples R, G, B; row pitch `pitch` in BYTES (>= 3 * cols); any byte alignment
+ * of rgb and pitch (odd included: a P6 raster where it lies in its file's bytes, at
+ * bic_pnm_parse_header's data_offset). plane0, nplanes: the range within each channel (plane0 + nplanes
+ * <= 8). There are 3 * nplanes outputs: plane, stream, bit count, offset and row-index entry
+ * c * nplanes + k belongs to plane plane0 + k of channel c (0 = R, 1 = G, 2 = B); slots, bits_*, off_*
+ * (3 * nplanes + 1 entries), row_index and planes (3 * nplanes * rows * wpr words) are sized for them.
+ * The results are bit for bit those of bic_encode_gray_range / bic_encode_gray_packed on channel c's
+ * samples taken as a gray image (with BIC_OPT_GRAY_CODE: each channel's samples Gray-coded on their
+ * own). Nullable planes, BIC_ENOSPC, rows = 0, the domain and the argument errors as for
+ * bic_encode_gray_packed. Bitplane extraction and med are linear over XOR and no step couples the
+ * channels, so plane 8 c + b of the image is the 8-bit pipeline on channel c's bytes: with the staged
+ * encoder, an even wpr and rows of up to 16384 columns that hold ceil(cols/64)*192 readable bytes, one
+ * count kernel reads the image once (with planes NULL, predict and the EG stream into slots the count pass writes the EG stream
+ * itself, as for bic_encode_gray); otherwise the same result through bic_bitplanes_rgb followed by
+ * bic_encode_planes2 / bic_encode_planes_packed. Samples of two bytes (P6 with maxval >= 256) are out of
+ * scope: these calls have no way to express them. The device round trip is rgb -> bic_encode_rgb_packed
+ * -> bic_decode_rgb. */
+int bic_encode_rgb(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t rows, size_t cols, int plane0, int nplanes,
+                   uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
+                   uint64_t* bits_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg);
+int bic_encode_rgb_packed(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t rows, size_t cols, int plane0,
+                          int nplanes, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
+                          size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
+                          size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index);
+/* The extraction alone and its inverse, in the same plane order (plane c * nplanes + k = plane plane0 + k
+ * of channel c; planes = 3 * nplanes * rows * wpr words, pad bits and pad words 0). bic_planes_to_rgb
+ * writes only the first 3 * cols bytes of each row; sample bits no plane covers are written 0. rgb and
+ * pitch of any byte alignment; with BIC_OPT_GRAY_CODE the planes are those of each channel's Gray-coded
+ * samples, as for the gray calls. */
+int bic_bitplanes_rgb(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t rows, size_t cols, int plane0, int nplanes,
+                      uint64_t* planes, size_t wpr);
+int bic_planes_to_rgb(bic_ctx* ctx, const uint64_t* planes, int plane0, int nplanes, size_t rows, size_t cols,
+                      size_t wpr, uint8_t* rgb, size_t pitch);
 /* P4 rasters -> streams in one call: bic_pbm_unpack per frame followed by bic_encode_planes2 /
  * bic_encode_planes_packed, bit-identical streams, bit counts, offsets and row index. Frame f's raster
  * (pbm.cpp:29-77: rows x ceil(cols/8) bytes, MSB = leftmost pixel) lies at raster + f * frame_stride:
@@ -286,6 +320,16 @@ int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slo
                     const uint64_t* word_off, const uint64_t* plane_bits, const uint64_t* row_index,
                     int plane0, int nplanes, size_t rows, size_t cols, int predict, const uint8_t* p00,
                     int sample_bytes, int big_endian, void* gray, size_t pitch);
+/* streams -> interleaved RGB samples in one call: bic_decode_planes followed by bic_planes_to_rgb,
+ * without the planes, as bic_decode_gray does for gray. The 3 * nplanes streams in bic_encode_rgb's
+ * order (stream c * nplanes + k sets bit plane0 + k of channel c); coder, streams, slot_words, word_off,
+ * plane_bits, row_index, predict, the limit cols <= 16384 and BIC_EDATA from bic_sync as for
+ * bic_decode_gray; p00 (device, one byte per stream; nullable: 0). rgb = rows of `pitch` bytes (>= 3 *
+ * cols; any byte alignment of pointer and pitch), of which only the first 3 * cols are written; bits
+ * no plane covers are written 0. rows = 0: BIC_OK, nothing written. */
+int bic_decode_rgb(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                   const uint64_t* plane_bits, const uint64_t* row_index, int plane0, int nplanes, size_t rows,
+                   size_t cols, int predict, const uint8_t* p00, uint8_t* rgb, size_t pitch);
 /* streams -> P4 rasters in one call: bic_decode_planes followed by bic_pbm_pack per frame, without the
  * planes. coder, streams, slot_words, word_off, plane_bits, row_index, predict, the limit cols <= 16384
  * and BIC_EDATA from bic_sync (the rasters are then undefined) as for bic_decode_gray; stream f is frame
