@@ -236,6 +236,10 @@ int bic_ctx_set_option(bic_ctx* ctx, int option, long value) {
       if (value != 0 && value != 1) return BIC_EINVAL;  // (the setting stays as it was)
       ctx->gray_code = value == 1;
       return BIC_OK;
+    case BIC_OPT_COLOR_TRANSFORM:
+      if (value < BIC_CT_NONE || value > BIC_CT_SUBTRACT_GREEN_FOLDED) return BIC_EINVAL;  // (likewise)
+      ctx->color_transform = (int)value;
+      return BIC_OK;
     default: return BIC_EINVAL;
   }
 }
@@ -244,6 +248,22 @@ size_t bic_encode_slot_words(size_t rows, size_t cols, int coder) {
   const unsigned long long base = (unsigned long long)rows * (cols + 1);
   if (coder == BIC_CODER_EG) return (size_t)((base + 1 + 63) / 64);
   return (size_t)((2 * base + 63) / 64 + 64);
+}
+
+int bic_rgb_p00(int color_transform, int gray_code, const uint8_t pixel[3], int plane0, int nplanes, uint8_t* p00) {
+  if (color_transform < BIC_CT_NONE || color_transform > BIC_CT_SUBTRACT_GREEN_FOLDED || (gray_code != 0 && gray_code != 1) ||
+      !pixel || !p00 || plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8)
+    return BIC_EINVAL;
+  for (int c = 0; c < 3; ++c) {
+    uint32_t v = pixel[c];
+    if (c != 1 && color_transform != BIC_CT_NONE) {
+      v = (v - pixel[1]) & 0xffu;
+      if (color_transform == BIC_CT_SUBTRACT_GREEN_FOLDED) v = ((v << 1) ^ (v & 0x80u ? 0xffu : 0u)) & 0xffu;
+    }
+    if (gray_code) v ^= v >> 1;
+    for (int k = 0; k < nplanes; ++k) p00[c * nplanes + k] = (uint8_t)((v >> (plane0 + k)) & 1u);
+  }
+  return BIC_OK;
 }
 
 int bic_pnm_parse_header(const uint8_t* bytes, size_t n, bic_pnm_info* info) {

@@ -87,7 +87,7 @@ int bic_decode_rgb(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot
                         (cols + 63) / 64, predict, p00, rgb)) || !c.rows)
     return rc;
   c.sink = bic::DecodeCall::kRgb;
-  c.rgb = {rgb, (uint64_t)pitch, plane0, ctx->gray_code ? 1 : 0};
+  c.rgb = {rgb, (uint64_t)pitch, plane0, ctx->gray_code ? 1 : 0, ctx->color_transform};
   return run_decode(ctx, "decode_rgb", c);
 }
 

@@ -103,7 +103,7 @@ int bic_bitplanes_rgb(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t row
   if (rows == 0) return BIC_OK;
   timed(ctx, "bitplanes_rgb", [&] {
     bic::launch_raster_planes(ctx->cur, rgb, 3, (uint32_t)rows, (uint32_t)cols, plane0, nplanes, planes, (uint32_t)wpr,
-                              (uint64_t)pitch, 0, ctx->gray_code);
+                              (uint64_t)pitch, 0, ctx->gray_code, ctx->color_transform);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
@@ -119,7 +119,7 @@ int bic_planes_to_rgb(bic_ctx* ctx, const uint64_t* planes, int plane0, int npla
   if (rows == 0) return BIC_OK;
   timed(ctx, "planes_to_rgb", [&] {
     bic::launch_planes_gray(ctx->cur, planes, (uint32_t)rows, (uint32_t)cols, (uint32_t)wpr, plane0, nplanes, 3, rgb,
-                            (uint64_t)pitch, ctx->gray_code);
+                            (uint64_t)pitch, ctx->gray_code, ctx->color_transform);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;

@@ -986,7 +986,10 @@ struct RgbArgs {
   uint64_t pitch;
   uint32_t omask;
 };
-template <bool VEC, bool SCAN, bool GC>
+// CT (BIC_OPT_COLOR_TRANSFORM): the accumulators stay in the transformed (and Gray) domain -- they carry the
+// column sums -- and the row's R' and B' dwords, after ungray_blocks and omask, go through ct_inverse4 with the
+// row's G before the interleave (1: subtract green, 2: folded; an instantiation each).
+template <bool VEC, bool SCAN, bool GC, int CT = 0>
 __global__ __launch_bounds__(256) void k_col_apply_rgb(RgbArgs a) {
   using T = typename SegWord<kGraySeg>::load;
   using RT = typename SegWord<kGraySeg>::reg;
@@ -1054,6 +1057,13 @@ __global__ __launch_bounds__(256) void k_col_apply_rgb(RgbArgs a) {
 #pragma unroll
         for (int q = 0; q < 2 * NG; ++q) chan[ch][q] &= a.omask;
       }
+      if constexpr (CT != 0) {
+#pragma unroll
+        for (int q = 0; q < 2 * NG; ++q) {
+          chan[0][q] = ct_inverse4<CT>(chan[0][q], chan[1][q]);
+          chan[2][q] = ct_inverse4<CT>(chan[2][q], chan[1][q]);
+        }
+      }
       uint32_t out[6 * NG];  // the segment's 48 bytes in memory order
 #pragma unroll
       for (int q = 0; q < 2 * NG; ++q)
@@ -1091,14 +1101,22 @@ void launch_col_apply_rgb(hipStream_t s, const uint64_t* D, const uint64_t* ctot
   const uint64_t nt = (uint64_t)((rows + kColChunk - 1) / kColChunk) * ((cols + kGraySeg - 1) / kGraySeg);
   const uint32_t grid = (uint32_t)((nt + 255) / 256);
   const bool vec = reinterpret_cast<uintptr_t>(ro.rgb) % 16 == 0 && ro.pitch % 16 == 0;
+#define BIC_CARC(V, G, C)                                                   \
+  do {                                                                      \
+    if (ctot) k_col_apply_rgb<V, true, G, C><<<grid, 256, 0, s>>>(a);       \
+    else k_col_apply_rgb<V, false, G, C><<<grid, 256, 0, s>>>(a);           \
+  } while (0)
 #define BIC_CAR(V, G)                                                  \
   do {                                                                 \
-    if (ctot) k_col_apply_rgb<V, true, G><<<grid, 256, 0, s>>>(a);     \
+    if (ro.color_transform == 1) BIC_CARC(V, G, 1);                    \
+    else if (ro.color_transform == 2) BIC_CARC(V, G, 2);               \
+    else if (ctot) k_col_apply_rgb<V, true, G><<<grid, 256, 0, s>>>(a); \
     else k_col_apply_rgb<V, false, G><<<grid, 256, 0, s>>>(a);         \
   } while (0)
   if (ro.gray_code) { if (vec) BIC_CAR(true, true); else BIC_CAR(false, true); }
   else { if (vec) BIC_CAR(true, false); else BIC_CAR(false, false); }
 #undef BIC_CAR
+#undef BIC_CARC
 }
 
 // k_col_apply with a P4 sink (bic_decode_pbm: k_col_apply and k_pbm_pack2 in one pass): a thread sums

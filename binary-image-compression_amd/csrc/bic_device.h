@@ -379,6 +379,33 @@ __device__ __forceinline__ void rgb_interleave4(uint32_t r, uint32_t g, uint32_t
   o2 = __builtin_amdgcn_perm(b, __builtin_amdgcn_perm(g, r, 0x00070300u), 0x07020106u);  // B2 R3 G3 B3
 }
 
+// BIC_OPT_COLOR_TRANSFORM on the four bytes of a dword (four pixels of one channel, g = their green bytes);
+// no carry or borrow crosses a byte: bit 7 of every byte is kept out of the 32-bit subtraction / addition
+// and put back with an XOR. CT 1: x - g mod 256. CT 2: that difference d folded, (d << 1) ^ (d >> 7) with
+// the sign byte 0x00 / 0xff formed as (m << 1) - (m >> 7) of the sign bits m (mod 2^32, the top byte's
+// lost bit 32 changes nothing). The low byte alone is the scalar form (ct_forward4(x, g) & 0xff).
+template <int CT>
+__host__ __device__ __forceinline__ uint32_t ct_forward4(uint32_t x, uint32_t g) {
+  if constexpr (CT == 0) return x;
+  uint32_t d = ((x | 0x80808080u) - (g & 0x7f7f7f7fu)) ^ ((x ^ ~g) & 0x80808080u);
+  if constexpr (CT == 2) {
+    const uint32_t m = d & 0x80808080u;
+    d = ((d << 1) & 0xfefefefeu) ^ ((m << 1) - (m >> 7));
+  }
+  return d;
+}
+// and back: x = unfold(z) + g mod 256, unfold(z) = (z >> 1) ^ -(z & 1)
+template <int CT>
+__host__ __device__ __forceinline__ uint32_t ct_inverse4(uint32_t z, uint32_t g) {
+  if constexpr (CT == 0) return z;
+  uint32_t d = z;
+  if constexpr (CT == 2) {
+    const uint32_t l = z & 0x01010101u;
+    d = ((z >> 1) & 0x7f7f7f7fu) ^ ((l << 8) - l);
+  }
+  return ((d & 0x7f7f7f7fu) + (g & 0x7f7f7f7fu)) ^ ((d ^ g) & 0x80808080u);
+}
+
 // Bits of the Golomb codewords whose '1' lies in residual word w of a row (plus the end-of-row
 // codeword when eol) -- the length the row encoder's emission produces for that word -- without
 // forming any codeword. n = samples of the plane before the word's first 1, jp = column of the

@@ -81,6 +81,7 @@ struct RgbOut {
   uint64_t pitch;
   int plane0;
   int gray_code = 0;
+  int color_transform = 0;  // BIC_OPT_COLOR_TRANSFORM: the planes are T(pixel)'s, the samples stored the pixel's
 };
 // bic_decode_pbm: the P4 rasters the decoded planes go to (plane f = frame f at raster + f * stride)
 struct PbmOut {
@@ -279,11 +280,11 @@ uint32_t gray_strips(const Geom& g);
 // words); planes is then unused. bps = 2 (bic_encode_gray16): samples of two bytes, big-endian
 // (pnm.cpp:71-74) or the host's order, planes plane0 .. of 16 (k_gray_strips16). bps = 3 (bic_encode_rgb):
 // interleaved RGB pixels of one-byte samples; g.nplanes = 3 np, output plane c * np + k is plane plane0 + k
-// of channel c (k_gray_strips_rgb)
+// of channel c (k_gray_strips_rgb; color_transform: BIC_OPT_COLOR_TRANSFORM, bps = 3 only)
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero,
                       bool store_resid = false, uint64_t* out_e = nullptr, uint64_t eg_stride = 0, int bps = 1,
-                      int big_endian = 0, bool gray_code = false);
+                      int big_endian = 0, bool gray_code = false, int color_transform = 0);
 // the count pass can write the EG stream (FusedRequest::eg_src): rows of whole 64-word strips only
 bool gray_eg_supported(const Geom& g);
 
@@ -329,12 +330,14 @@ void launch_match_code(hipStream_t s, const MatchArgs& a, unsigned long long* ou
 void launch_pbm(hipStream_t s, bool pack, const uint8_t* raster_in, uint8_t* raster_out, const uint64_t* plane_in,
                 uint64_t* plane_out, uint32_t rows, uint32_t cols, uint32_t wpr);
 // P5 samples (1 or 2 bytes, any alignment) -> planes plane0.. (bic_raster.hip); pitch: bytes per row
-// (0: cols * bpp, a P5 raster); big_endian: the order of two-byte samples (1: pnm.cpp:73)
+// (0: cols * bpp, a P5 raster); big_endian: the order of two-byte samples (1: pnm.cpp:73);
+// color_transform: BIC_OPT_COLOR_TRANSFORM (bpp / bps = 3 only)
 void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_t rows, uint32_t cols, int plane0,
                           int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch = 0, int big_endian = 1,
-                          bool gray_code = false);
+                          bool gray_code = false, int color_transform = 0);
 void launch_planes_gray(hipStream_t s, const uint64_t* planes, uint32_t rows, uint32_t cols, uint32_t wpr, int plane0,
-                        int nplanes, int bps, uint8_t* gray, uint64_t pitch, bool gray_code = false);
+                        int nplanes, int bps, uint8_t* gray, uint64_t pitch, bool gray_code = false,
+                        int color_transform = 0);
 
 // GF(2) algebra (bic_gf2.hip). Both launches spread their rows over gridDim.y (at most 65,535): the transpose
 // four 64-row blocks per unit, the product 256 rows per unit, so either takes at most kGf2MaxRows source rows

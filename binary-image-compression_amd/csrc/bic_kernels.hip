@@ -728,7 +728,12 @@ struct Raw16 {
 // XOR, so the med of the bytes is the med of G's planes. A two-byte sample's low byte takes bit 0 of
 // its high byte into bit 7 (lo16: the wave's group is the low byte's; a second v_perm_b32 with the
 // other selector).
-template <bool PREDICT, bool FULL, bool STORE_R, bool NP8, bool EGS, bool MIS = false, int S16 = 0, bool GC = false>
+// CT (BIC_OPT_COLOR_TRANSFORM, S16 = 3 only): the waves of channels 0 and 2 also pick channel 1's bytes out
+// of the same twelve uint4 and subtract them byte-wise (ct_forward4) before G. T is not linear over XOR,
+// where the split, med and G are: the pixel before the strip is T of it and its green (src[-2]), and the next
+// segment's D byte is T(cb, its green) ^ T(ub, its green), not T of cb ^ ub. The green wave runs as with CT 0.
+template <bool PREDICT, bool FULL, bool STORE_R, bool NP8, bool EGS, bool MIS = false, int S16 = 0, bool GC = false,
+          int CT = 0>
 __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray, size_t pitch, const Geom& g,
                                                 uint32_t ns, uint32_t s, uint32_t r0, uint32_t plane0,
                                                 uint64_t* __restrict__ planes, uint32_t* __restrict__ sones,
@@ -767,6 +772,8 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
       const uint32_t s1 = rgb_sel1(bo), s2 = rgb_sel2(bo);
       auto pick = [&](uint32_t d0, uint32_t d1, uint32_t d2) {
         uint32_t x = rgb_pick4(d0, d1, d2, s1, s2);
+        if constexpr (CT != 0)
+          if (bo != 1) x = ct_forward4<CT>(x, rgb_pick4(d0, d1, d2, rgb_sel1(1), rgb_sel2(1)));  // (wave-uniform)
         if constexpr (GC) x ^= (x >> 1) & 0x7f7f7f7fu;
         return x;
       };
@@ -824,6 +831,8 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
     if constexpr (S16 == 3) lb = (lane == 0 && s > 0) ? (uint32_t)src[(int)bo - 3] : 0u;  // the pixel before the strip
     else if constexpr (S16) lb = (lane == 0 && s > 0) ? (uint32_t)src[(int)bo - 2] : 0u;  // the sample before the strip
     else lb = (lane == 0 && s > 0) ? (uint32_t)src[-1] : 0u;
+    if constexpr (S16 == 3 && CT != 0)
+      if (bo != 1 && lane == 0 && s > 0) lb = ct_forward4<CT>(lb, (uint32_t)src[-2]) & 0xffu;
     if constexpr (GC) {
       if constexpr (!S16) gray4(v);
       lb ^= lb >> 1;
@@ -877,6 +886,12 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
                           : S16 ? gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 8192u) + 2 * lane + bo
                               : gray + (uint64_t)rn * pitch + (lastS ? 0u : (s + 1) * 4096u) + lane;
       uint32_t cb = cp[0], ub = rn ? cp[-(int64_t)pitch] : 0u;
+      if constexpr (S16 == 3 && CT != 0)
+        if (bo != 1) {  // each byte with its own green, at cp[1 - bo]
+          const int64_t o = 1 - (int64_t)bo;
+          cb = ct_forward4<CT>(cb, cp[o]) & 0xffu;
+          if (rn) ub = ct_forward4<CT>(ub, cp[o - (int64_t)pitch]) & 0xffu;
+        }
       uint32_t gd0 = cb ^ ub;
       if constexpr (GC) {
         gd0 ^= gd0 >> 1;
@@ -1104,7 +1119,8 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips16(const 
 // of a strip are neighbouring waves (of one workgroup, or of two that xcd_remap keeps on one XCD), all load the
 // same 192 bytes per lane (the second and third from L1 / L2) and keep their own 64; gray_strip_rows then runs on that channel's bytes as on an
 // 8-bit image, its plane-indexed outputs advanced by c * np (RGB in one call).
-template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false>
+// CT (BIC_OPT_COLOR_TRANSFORM): 0, or 1 (subtract green) / 2 (folded), an instantiation each.
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false, int CT = 0>
 __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_rgb(const uint8_t* __restrict__ rgb, size_t pitch, Geom g,
                                                             uint32_t ns, uint32_t plane0, uint64_t* __restrict__ planes,
                                                             uint32_t* __restrict__ sones, int4* __restrict__ krec,
@@ -1127,15 +1143,17 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_rgb(cons
   uint64_t* pl = planes + (uint64_t)skip * g.plane_words;
   uint64_t* oe = out_e + (uint64_t)skip * eg_stride;
   if ((s + 1) * 64 <= g.used && g.trail == ~0ull && gg.nplanes == 8)
-    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 3, GC>(rgb, pitch, gg, ns, s, r0, plane0, pl, sones + rskip,
-                                                                   krec + rskip, kpos + rskip, tw, oe, eg_stride, ch);
-  else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
-    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 3, GC>(rgb, pitch, gg, ns, s, r0, plane0, pl, sones + rskip,
-                                                                    krec + rskip, kpos + rskip, tw, oe, eg_stride, ch);
-  else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
-    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 3, GC>(rgb, pitch, gg, ns, s, r0, plane0, pl,
+    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 3, GC, CT>(rgb, pitch, gg, ns, s, r0, plane0, pl,
                                                                        sones + rskip, krec + rskip, kpos + rskip, tw,
-                                                                       nullptr, 0, ch);
+                                                                       oe, eg_stride, ch);
+  else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
+    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 3, GC, CT>(rgb, pitch, gg, ns, s, r0, plane0, pl,
+                                                                        sones + rskip, krec + rskip, kpos + rskip, tw,
+                                                                        oe, eg_stride, ch);
+  else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
+    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 3, GC, CT>(rgb, pitch, gg, ns, s, r0, plane0, pl,
+                                                                           sones + rskip, krec + rskip, kpos + rskip, tw,
+                                                                           nullptr, 0, ch);
 }
 
 bool gray_eg_supported(const Geom& g) { return g.trail == ~0ull && g.used % 64 == 0 && g.used / 64 <= kMaxStrips; }
@@ -1149,7 +1167,7 @@ bool gray_rows_supported(const Geom& g, const void* gray, size_t pitch, const vo
 
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero, bool store_resid,
-                      uint64_t* out_e, uint64_t eg_stride, int bps, int big_endian, bool gray_code) {
+                      uint64_t* out_e, uint64_t eg_stride, int bps, int big_endian, bool gray_code, int color_transform) {
   const uint32_t ns = gray_strips(g);
   const uint32_t rpw = predict && store_resid ? gray_rows_per_wave<true, true>() : gray_rows_per_wave<true, false>();
   const uint64_t units = (uint64_t)(g.rows + rpw - 1) / rpw;  // row groups per strip
@@ -1162,7 +1180,13 @@ void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Ge
   const bool egs = out_e && predict && store_resid && gray_eg_supported(g);
 #define BIC_GSG(P, R, E, M, G)                                                                                     \
   do {                                                                                                             \
-    if (bps == 3)                                                                                                  \
+    if (bps == 3 && color_transform == 1)                                                                          \
+      k_gray_strips_rgb<P, R, E, M, G, 1><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes,     \
+                                                                  sones, krec, kpos, zero, out_e, eg_stride);      \
+    else if (bps == 3 && color_transform == 2)                                                                     \
+      k_gray_strips_rgb<P, R, E, M, G, 2><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes,     \
+                                                                  sones, krec, kpos, zero, out_e, eg_stride);      \
+    else if (bps == 3)                                                                                             \
       k_gray_strips_rgb<P, R, E, M, G><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes, sones, \
                                                                krec, kpos, zero, out_e, eg_stride);                \
     else if (bps == 2)                                                                                             \

@@ -75,7 +75,9 @@ __global__ __launch_bounds__(256) void k_pbm_pack2(const uint64_t* __restrict__ 
 // BPP 3 (bic_bitplanes_rgb): interleaved R G B pixels of one-byte samples (P6, pnm.cpp:194-239); the wave
 // takes channel blockIdx.y -- 24 loads, two v_perm_b32 per four pixels (rgb_pick4) -- and writes planes
 // plane0 .. of it as output planes channel * nplanes ..
-template <int BPP, bool GC>
+// CT (BIC_OPT_COLOR_TRANSFORM, BPP 3): channels 0 and 2 also pick the green bytes and go through ct_forward4
+// before G (1: subtract green, 2: folded; an instantiation each).
+template <int BPP, bool GC, int CT = 0>
 __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict__ base, uint32_t off, uint32_t rows,
                                                        uint32_t cols, int plane0, int nplanes,
                                                        uint64_t* __restrict__ planes, uint32_t wpr, uint64_t pitch,
@@ -98,8 +100,19 @@ __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict
       const uint64_t a = bytes8(base, p0 + 24 * g, end), b = bytes8(base, p0 + 24 * g + 8, end),
                      c = bytes8(base, p0 + 24 * g + 16, end);
       const uint32_t s1 = rgb_sel1(blockIdx.y), s2 = rgb_sel2(blockIdx.y);
-      lo8[g] = ((uint64_t)rgb_pick4((uint32_t)(b >> 32), (uint32_t)c, (uint32_t)(c >> 32), s1, s2) << 32) |
-               rgb_pick4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, s1, s2);
+      if constexpr (CT != 0) {
+        uint32_t x0 = rgb_pick4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, s1, s2),
+                 x1 = rgb_pick4((uint32_t)(b >> 32), (uint32_t)c, (uint32_t)(c >> 32), s1, s2);
+        if (blockIdx.y != 1) {
+          x0 = ct_forward4<CT>(x0, rgb_pick4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, rgb_sel1(1), rgb_sel2(1)));
+          x1 = ct_forward4<CT>(x1, rgb_pick4((uint32_t)(b >> 32), (uint32_t)c, (uint32_t)(c >> 32), rgb_sel1(1),
+                                             rgb_sel2(1)));
+        }
+        lo8[g] = ((uint64_t)x1 << 32) | x0;
+      } else {
+        lo8[g] = ((uint64_t)rgb_pick4((uint32_t)(b >> 32), (uint32_t)c, (uint32_t)(c >> 32), s1, s2) << 32) |
+                 rgb_pick4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, s1, s2);
+      }
       hi8[g] = 0;
     } else {
       const uint64_t a = bytes8(base, p0 + 16 * g, end), b = bytes8(base, p0 + 16 * g + 8, end);
@@ -151,7 +164,9 @@ __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict
 // covers count as 0), a suffix XOR over the blocks' bytes, then masked to the bits the planes cover.
 // BPS 3 (bic_planes_to_rgb): planes c * nplanes + b are channel c's (plane0 + b); the three channels' bytes
 // of a group of 8 pixels are interleaved R G B with v_perm_b32 (rgb_interleave4), 192 bytes per lane.
-template <int BPS, bool VEC, bool GC>
+// CT (BIC_OPT_COLOR_TRANSFORM, BPS 3): the assembled R' and B' (after ungray_blocks and its mask) go through
+// ct_inverse4 with the assembled G before the interleave; all eight bits of the result are written.
+template <int BPS, bool VEC, bool GC, int CT = 0>
 __global__ __launch_bounds__(256) void k_planes_gray(const uint64_t* __restrict__ planes, uint32_t rows, uint32_t cols,
                                                      uint32_t wpr, int plane0, int nplanes, uint8_t* __restrict__ gray,
                                                      uint64_t pitch) {
@@ -184,6 +199,12 @@ __global__ __launch_bounds__(256) void k_planes_gray(const uint64_t* __restrict_
     uint32_t out[48];  // the 64 pixels' bytes in file order
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
+      if constexpr (CT != 0) {
+#pragma unroll
+        for (int c = 0; c < 3; c += 2)
+          ch[c][g] = ((uint64_t)ct_inverse4<CT>((uint32_t)(ch[c][g] >> 32), (uint32_t)(ch[1][g] >> 32)) << 32) |
+                     ct_inverse4<CT>((uint32_t)ch[c][g], (uint32_t)ch[1][g]);
+      }
       rgb_interleave4((uint32_t)ch[0][g], (uint32_t)ch[1][g], (uint32_t)ch[2][g], out[6 * g], out[6 * g + 1],
                       out[6 * g + 2]);
       rgb_interleave4((uint32_t)(ch[0][g] >> 32), (uint32_t)(ch[1][g] >> 32), (uint32_t)(ch[2][g] >> 32),
@@ -246,7 +267,7 @@ __global__ __launch_bounds__(256) void k_planes_gray(const uint64_t* __restrict_
 }
 
 void launch_planes_gray(hipStream_t s, const uint64_t* planes, uint32_t rows, uint32_t cols, uint32_t wpr, int plane0,
-                        int nplanes, int bps, uint8_t* gray, uint64_t pitch, bool gray_code) {
+                        int nplanes, int bps, uint8_t* gray, uint64_t pitch, bool gray_code, int color_transform) {
   const uint64_t waves = (uint64_t)rows * ((cols + 4095) / 4096);
   const uint32_t grid = (uint32_t)((waves + 3) / 4);
   if (!grid) return;
@@ -257,9 +278,20 @@ void launch_planes_gray(hipStream_t s, const uint64_t* planes, uint32_t rows, ui
     if (gray_code) BIC_PGG(B, V, true);     \
     else BIC_PGG(B, V, false);              \
   } while (0)
-  if (bps == 1) { if (vec) BIC_PG(1, true); else BIC_PG(1, false); }
+#define BIC_PGC(V, G, C) \
+  k_planes_gray<3, V, G, C><<<grid, 256, 0, s>>>(planes, rows, cols, wpr, plane0, nplanes, gray, pitch)
+#define BIC_PGC2(C)                                                          \
+  do {                                                                       \
+    if (gray_code) { if (vec) BIC_PGC(true, true, C); else BIC_PGC(false, true, C); }   \
+    else { if (vec) BIC_PGC(true, false, C); else BIC_PGC(false, false, C); }           \
+  } while (0)
+  if (bps == 3 && color_transform == 1) BIC_PGC2(1);
+  else if (bps == 3 && color_transform == 2) BIC_PGC2(2);
+  else if (bps == 1) { if (vec) BIC_PG(1, true); else BIC_PG(1, false); }
   else if (bps == 3) { if (vec) BIC_PG(3, true); else BIC_PG(3, false); }
   else { if (vec) BIC_PG(2, true); else BIC_PG(2, false); }
+#undef BIC_PGC2
+#undef BIC_PGC
 #undef BIC_PG
 #undef BIC_PGG
 }
@@ -279,7 +311,8 @@ void launch_pbm(hipStream_t s, bool pack, const uint8_t* raster_in, uint8_t* ras
 }
 
 void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_t rows, uint32_t cols, int plane0,
-                          int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch, int big_endian, bool gray_code) {
+                          int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch, int big_endian, bool gray_code,
+                          int color_transform) {
   const uintptr_t r = reinterpret_cast<uintptr_t>(raster);
   if (!pitch) pitch = (uint64_t)cols * bpp;
   const uint32_t selL = big_endian ? 0x07050301u : 0x06040200u, selH = big_endian ? 0x06040200u : 0x07050301u;
@@ -287,6 +320,15 @@ void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_
   const uint64_t waves = (uint64_t)rows * ((cols + 4095) / 4096);
   const uint32_t grid = (uint32_t)((waves + 3) / 4);
   if (!grid) return;
+  if (bpp == 3 && color_transform) {  // grid.y: the channel
+#define BIC_RPC(G, C) \
+  k_raster_planes<3, G, C><<<dim3(grid, 3), 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr, \
+                                                         pitch, 0, 0)
+    if (color_transform == 1) { if (gray_code) BIC_RPC(true, 1); else BIC_RPC(false, 1); }
+    else { if (gray_code) BIC_RPC(true, 2); else BIC_RPC(false, 2); }
+#undef BIC_RPC
+    return;
+  }
   if (bpp == 3) {  // grid.y: the channel
     if (gray_code)
       k_raster_planes<3, true><<<dim3(grid, 3), 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes,

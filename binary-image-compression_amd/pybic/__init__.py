@@ -33,6 +33,7 @@ EXPORTS = [
     "bic_encode_gray16", "bic_encode_gray16_packed", "bic_bitplanes_u16", "bic_decode_gray",
     "bic_encode_pbm", "bic_encode_pbm_packed", "bic_decode_pbm",
     "bic_encode_rgb", "bic_encode_rgb_packed", "bic_bitplanes_rgb", "bic_planes_to_rgb", "bic_decode_rgb",
+    "bic_rgb_p00",
     "bic_bsvd_update_coefficients", "bic_bsvd_update_dictionary", "bic_bsvd_learn",
     "bic_dict_encode", "bic_set_dict_block",
     "bic_bsvd_update_dictionary_proximus", "bic_bsvd_learn_du", "bic_set_bsvd_rounds",
@@ -43,6 +44,11 @@ EXPORTS = [
     "bic_bsvd_append_atom", "bic_bsvd_model_codelength", "bic_bsvd_learn_mdl",
     "bic_patches_gather", "bic_patches_scatter", "bic_mosaic_dims", "bic_mosaic", "bic_bsvd_learn_image",
 ]
+
+# BIC_OPT_COLOR_TRANSFORM and its values (include/bic.h)
+OPT_COLOR_TRANSFORM = 8
+CT_NONE, CT_SUBTRACT_GREEN, CT_SUBTRACT_GREEN_FOLDED = 0, 1, 2
+_CT_NAMES = {"none": CT_NONE, "subtract_green": CT_SUBTRACT_GREEN, "subtract_green_folded": CT_SUBTRACT_GREEN_FOLDED}
 
 # bic_bsvd_learn_du rules (include/bic.h)
 BSVD_DU_STEEPEST, BSVD_DU_PROXIMUS = 0, 1
@@ -190,6 +196,7 @@ def load(path=LIB_PATH):
     sig("bic_bitplanes_rgb", i32, [vp, vp, sz, sz, sz, i32, i32, vp, sz])
     sig("bic_planes_to_rgb", i32, [vp, vp, i32, i32, sz, sz, sz, vp, sz])
     sig("bic_decode_rgb", i32, [vp, i32, vp, sz, vp, vp, vp, i32, i32, sz, sz, i32, vp, vp, sz])
+    sig("bic_rgb_p00", i32, [i32, i32, C.c_char_p, i32, i32, vp])
     sig("bic_bsvd_update_coefficients", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_update_dictionary", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_learn", i32, [vp, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
@@ -752,6 +759,17 @@ class Context:
         (BIC_OPT_GRAY_CODE, default off)"""
         self._chk(self.lib.bic_ctx_set_option(self.h, 7, int(on)), "bic_ctx_set_option")
 
+    def set_color_transform(self, mode):
+        """reversible per-pixel colour transform in front of the RGB bitplane split and its inverse on the way
+        back (BIC_OPT_COLOR_TRANSFORM, default 0): 0 / "none", 1 / "subtract_green" (R - G, G, B - G mod 256),
+        2 / "subtract_green_folded" (the differences with the sign folded into bit 0). Any other value raises
+        BicError and leaves the mode as it was. The gray, 16-bit, PBM and planes-only calls ignore it."""
+        if isinstance(mode, str):
+            if mode not in _CT_NAMES:
+                raise BicError(BIC_EINVAL, "bic_ctx_set_option")
+            mode = _CT_NAMES[mode]
+        self._chk(self.lib.bic_ctx_set_option(self.h, OPT_COLOR_TRANSFORM, int(mode)), "bic_ctx_set_option")
+
     def set_multipass(self, on=True):
         self._chk(self.lib.bic_ctx_set_option(self.h, 1, int(on)), "bic_ctx_set_option")
 
@@ -1186,6 +1204,19 @@ class Context:
         self._chk(self.lib.bic_pack_streams(self.h, _p(slots), n, slot_words, _p(plane_bits), _p(dst), _p(off)),
                   "bic_pack_streams")
         return dst, off
+
+
+def rgb_p00(color_transform, gray_code, pixel, plane0=0, nplanes=8):
+    """bic_rgb_p00: the p00 bytes decode_rgb needs for an image whose first pixel is `pixel` (R, G, B) under the
+    given colour transform (0 / 1 / 2) and Gray-code setting -> uint8 numpy array [3 * nplanes] (host only)"""
+    px = bytes(bytearray(int(v) & 0xFF for v in pixel))
+    if len(px) != 3:
+        raise BicError(BIC_EINVAL, "bic_rgb_p00")
+    out = np.zeros(3 * max(int(nplanes), 1), np.uint8)
+    rc = load().bic_rgb_p00(int(color_transform), int(gray_code), px, int(plane0), int(nplanes), out.ctypes.data)
+    if rc != BIC_OK:
+        raise BicError(rc, "bic_rgb_p00")
+    return out
 
 
 def pnm_header(data):

@@ -113,6 +113,26 @@ int bic_reserve(bic_ctx* ctx, int nplanes, size_t rows, size_t cols);
  * Calls that take or return planes only (bic_encode_planes*, bic_decode_planes, the PBM calls) are
  * untouched. */
 #define BIC_OPT_GRAY_CODE 7
+/* BIC_OPT_COLOR_TRANSFORM: a reversible per-pixel colour transform T in front of the RGB bitplane split,
+ * on one-byte samples. BIC_CT_NONE (0, default): none, every call as it was. BIC_CT_SUBTRACT_GREEN (1):
+ * R' = (R - G) mod 256, G' = G, B' = (B - G) mod 256. BIC_CT_SUBTRACT_GREEN_FOLDED (2): the same
+ * differences, each read as a signed 8-bit d and folded with z = ((d << 1) ^ (d >> 7)) & 0xFF (arithmetic
+ * shift: 0 -> 0, -1 -> 1, 1 -> 2, -128 -> 255; inverse d = (z >> 1) ^ -(z & 1)), so that a difference
+ * hovering around 0 stays in the low planes. Both are bijections on (R, G); G is never changed. Any other
+ * value is BIC_EINVAL and leaves the setting as it was.
+ *  - Samples to planes (bic_encode_rgb, bic_encode_rgb_packed, bic_bitplanes_rgb): T, then the Gray code
+ *    if BIC_OPT_GRAY_CODE is on (per channel), then the plane0 shift and the split. Planes, streams, bit
+ *    counts, offsets and the row index equal those of the same call with the option off on the image T(img).
+ *  - Planes to samples (bic_planes_to_rgb, bic_decode_rgb): the three channel samples R', G', B' are
+ *    assembled from the given planes (bits no plane covers count as 0, after the un-Gray step and its
+ *    mask); then R = (unfold(R') + G') & 0xFF and B likewise (unfold = identity in mode 1), G = G' as
+ *    assembled, and all eight bits of the result are written. The result is the image exactly when
+ *    plane0 = 0 and nplanes = 8; for any other range it is this formula.
+ * The gray, 16-bit, PBM and planes-only calls ignore the option. */
+#define BIC_OPT_COLOR_TRANSFORM 8
+#define BIC_CT_NONE 0
+#define BIC_CT_SUBTRACT_GREEN 1
+#define BIC_CT_SUBTRACT_GREEN_FOLDED 2
 int bic_ctx_set_option(bic_ctx* ctx, int option, long value);
 
 /* ---- a2: bitplane extraction (bitplane_tool.cpp:24-30) -----------------------------------
@@ -251,6 +271,12 @@ int bic_bitplanes_rgb(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t row
                       uint64_t* planes, size_t wpr);
 int bic_planes_to_rgb(bic_ctx* ctx, const uint64_t* planes, int plane0, int nplanes, size_t rows, size_t cols,
                       size_t wpr, uint8_t* rgb, size_t pitch);
+/* The p00 bytes bic_decode_rgb needs for an image whose first pixel is `pixel` (R, G, B), under the given
+ * BIC_OPT_COLOR_TRANSFORM and BIC_OPT_GRAY_CODE values: p00[c * nplanes + k] = bit plane0 + k of channel c
+ * of the transformed, then Gray-coded, pixel. Host code, no context. p00: host, 3 * nplanes bytes.
+ * BIC_EINVAL: a mode outside 0..2, gray_code outside 0..1, a NULL pointer, plane0 < 0, nplanes < 1 or
+ * plane0 + nplanes > 8. */
+int bic_rgb_p00(int color_transform, int gray_code, const uint8_t pixel[3], int plane0, int nplanes, uint8_t* p00);
 /* P4 rasters -> streams in one call: bic_pbm_unpack per frame followed by bic_encode_planes2 /
  * bic_encode_planes_packed, bit-identical streams, bit counts, offsets and row index. Frame f's raster
  * (pbm.cpp:29-77: rows x ceil(cols/8) bytes, MSB = leftmost pixel) lies at raster + f * frame_stride:

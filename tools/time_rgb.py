@@ -13,8 +13,14 @@ variants alternate in ONE process, `--repeats` times, each repeat `--steps` call
 a warm-up, on two input buffers used in turn so that the Infinity Cache cannot serve a re-run. One JSON line
 per (stage, repeat, variant), then per stage a summary line (the criterion: the slowest one_call repeat below
 the fastest two_call repeat) and the count pass's own time from the bracketed launches.
+--color-transform {0,1,2} and --gray-code set BIC_OPT_COLOR_TRANSFORM / BIC_OPT_GRAY_CODE for every call (p00
+then comes from bic_rgb_p00); with a transform on, a further stage alternates the one-call encode with the
+transform on and off (encode_ct_on_off). --input smooth replaces the uniform bytes by a luminance ramp with a
+small chroma and noise; --stream-bits records the one-call stream bits of that input for every (transform, Gray
+code) pair before the timing.
 Needs a device; fails without one.
-Usage: python tools/time_rgb.py [--check] [--steps 20] [--repeats 5] [--out profiles/r19/time_rgb.jsonl]"""
+Usage: python tools/time_rgb.py [--check] [--steps 20] [--repeats 5] [--color-transform 1] [--gray-code]
+       [--input smooth] [--stream-bits] [--out profiles/r20/time_rgb_ct.jsonl]"""
 import argparse
 import json
 import os
@@ -33,6 +39,11 @@ def main():
     ap.add_argument("--rows", type=int, default=5456)
     ap.add_argument("--cols", type=int, default=16384)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r19", "time_rgb.jsonl"))
+    ap.add_argument("--color-transform", type=int, choices=(0, 1, 2), default=0)
+    ap.add_argument("--gray-code", action="store_true")
+    ap.add_argument("--input", choices=("uniform", "smooth"), default="uniform")
+    ap.add_argument("--stream-bits", action="store_true")
+    ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     args = ap.parse_args()
     assert args.steps >= 20 or args.rows < 5456, "at least 20 steps per variant at full size"
     import torch
@@ -43,8 +54,27 @@ def main():
     wpr = (cols + 63) // 64
     gen = torch.Generator(device=ctx.dev)
     gen.manual_seed(0x526742)
-    imgs = [torch.randint(0, 256, (rows * cols * 3,), dtype=torch.uint8, device=ctx.dev, generator=gen)
-            for _ in range(2)]
+    ct, gc = args.color_transform, args.gray_code
+    ctx.set_color_transform(ct)
+    ctx.set_gray_code(gc)
+
+    def smooth(k):
+        """a luminance ramp shared by the three channels, a slow chroma of a few levels and noise of -1 .. 1"""
+        i = torch.arange(rows, device=ctx.dev, dtype=torch.float32)[:, None]
+        j = torch.arange(cols, device=ctx.dev, dtype=torch.float32)[None, :]
+        y = 24 + (i * (80 / rows)).floor() + (j * (120 / cols)).floor() + (8 * torch.sin(j / 37 + k)).trunc() + \
+            (8 * torch.cos(i / 11)).trunc()
+        n = torch.randint(0, 3, (3, rows, cols), device=ctx.dev, generator=gen).float() - 1
+        r = y + (6 * torch.sin(i / 9 + j / 50)).trunc() + n[0]
+        g = y + n[1] + 1
+        b = y + (5 * torch.cos(i / 13 - j / 70)).trunc() + n[2]
+        return torch.stack([r, g, b], dim=2).clamp(0, 255).to(torch.uint8).reshape(-1).contiguous()
+
+    if args.input == "smooth":
+        imgs = [smooth(k) for k in range(2)]
+    else:
+        imgs = [torch.randint(0, 256, (rows * cols * 3,), dtype=torch.uint8, device=ctx.dev, generator=gen)
+                for _ in range(2)]
     sg, se = ctx.slot_words(rows, cols, 0), ctx.slot_words(rows, cols, 1)
     # one set of outputs per input buffer: the decoders then alternate between two sets of streams too
     sets = [dict(outs=(ctx.empty_i64(n * sg), ctx.empty_i64(n * se)), bits=(ctx.empty_i64(n), ctx.empty_i64(n)),
@@ -52,7 +82,7 @@ def main():
             for _ in range(2)]
     planes = ctx.empty_i64(n, rows, wpr)
     back = torch.empty((rows, 3 * cols), dtype=torch.uint8, device=ctx.dev)
-    p00 = [torch.stack([(im[c] >> b) & 1 for c in range(3) for b in range(8)]).contiguous() for im in imgs]
+    p00 = [torch.from_numpy(pybic.rgb_p00(ct, gc, im[:3].cpu().numpy())).to(ctx.dev) for im in imgs]
 
     def enc_one(i):
         ctx.encode_rgb_packed(imgs[i], rows=rows, cols=cols, store_planes=False, **sets[i])
@@ -105,7 +135,7 @@ def main():
     stream_bytes = int(as_u64(sets[0]["bits"][0]).sum() + as_u64(sets[0]["bits"][1]).sum()) // 8
 
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    f = open(args.out, "w")
+    f = open(args.out, "a" if args.append else "w")
 
     def emit(d):
         line = json.dumps(d)
@@ -114,7 +144,23 @@ def main():
         f.flush()
 
     stream = torch.cuda.current_stream()
-    config = f"{rows}x{cols} RGB, one-byte samples, uniform, 24 planes, Golomb + EG packed, row index"
+    config = (f"{rows}x{cols} RGB, one-byte samples, {args.input}, 24 planes, Golomb + EG packed, row index, "
+              f"color_transform {ct}, gray_code {int(gc)}")
+    if args.stream_bits:
+        for m in (0, 1, 2):
+            for g in (False, True):
+                ctx.set_color_transform(m)
+                ctx.set_gray_code(g)
+                enc_one(0)
+                ctx.sync()
+                emit({"tool": "time_rgb", "stage": "stream_bits", "input": args.input, "rows": rows, "cols": cols,
+                      "color_transform": m, "gray_code": int(g), "golomb_bits": int(as_u64(sets[0]["bits"][0]).sum()),
+                      "eg_bits": int(as_u64(sets[0]["bits"][1]).sum()), "raw_bits": rows * cols * 24})
+        ctx.set_color_transform(ct)
+        ctx.set_gray_code(gc)
+        for i in range(2):
+            enc_one(i)
+        ctx.sync()
 
     def timed(fn):
         for i in range(args.warmup):
@@ -146,6 +192,26 @@ def main():
               "criterion_met": bool(max(ms["one_call"]) < min(ms["two_call"])), "checked": checked, **more})
 
     ms = ab("encode", enc_one, enc_two)
+    if ct:  # the one-call encode with the transform on against off, alternating (the streams differ: encode only)
+        def enc_off(i):
+            ctx.set_color_transform(0)
+            enc_one(i)
+            ctx.set_color_transform(ct)
+
+        mo = {"ct_on": [], "ct_off": []}
+        for r in range(args.repeats):
+            for name, fn in (("ct_on", enc_one), ("ct_off", enc_off)):
+                t = timed(fn)
+                mo[name].append(t)
+                emit({"tool": "time_rgb", "stage": "encode_ct_on_off", "config": config, "repeat": r, "variant": name,
+                      "steps": args.steps, "ms_per_step": round(t, 4)})
+        emit({"tool": "time_rgb", "stage": "encode_ct_on_off", "config": config, "summary": True,
+              "ct_on_ms": [round(x, 4) for x in mo["ct_on"]], "ct_off_ms": [round(x, 4) for x in mo["ct_off"]],
+              "ratio_of_medians": round(sorted(mo["ct_on"])[len(mo["ct_on"]) // 2] /
+                                        sorted(mo["ct_off"])[len(mo["ct_off"]) // 2], 4)})
+        for i in range(2):  # the decoders below read the streams of the transform in force
+            enc_one(i)
+        ctx.sync()
     # the count pass alone (bracketed launches; a pass of its own, after the A/B)
     ctx.prof_enable(True)
     ctx.prof_only("bitplanes_count")
