@@ -76,6 +76,27 @@ int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slo
   return run_decode(ctx, "decode_gray", c);
 }
 
+int bic_decode_gray_frames(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                           const uint64_t* plane_bits, const uint64_t* index, int nframes, int plane0, int nplanes,
+                           size_t rows, size_t cols, int predict, const uint8_t* p00, int sample_bytes, int big_endian,
+                           void* gray, size_t pitch, size_t frame_stride) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if ((sample_bytes != 1 && sample_bytes != 2) || plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 * sample_bytes ||
+      nframes < 1 || (uint64_t)nframes * (uint64_t)nplanes > 65535 || cols > SIZE_MAX / 4 ||
+      pitch < cols * (size_t)sample_bytes)
+    return BIC_EINVAL;
+  if (nframes > 1 && pitch && (rows > SIZE_MAX / pitch || frame_stride < rows * pitch)) return BIC_EINVAL;
+  bic::DecodeCall c{};
+  if ((rc = stream_call(c, coder, streams, slot_words, word_off, plane_bits, index, nframes * nplanes, rows, cols,
+                        (cols + 63) / 64, predict, p00, gray)) || !c.rows)
+    return rc;
+  c.sink = bic::DecodeCall::kGray;
+  c.gray = {static_cast<uint8_t*>(gray), (uint64_t)pitch, plane0, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0,
+            ctx->gray_code ? 1 : 0, (uint32_t)nframes, nframes > 1 ? (uint64_t)frame_stride : 0};
+  return run_decode(ctx, "decode_gray_frames", c);
+}
+
 int bic_decode_rgb(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
                    const uint64_t* plane_bits, const uint64_t* index, int plane0, int nplanes, size_t rows, size_t cols,
                    int predict, const uint8_t* p00, uint8_t* rgb, size_t pitch) {

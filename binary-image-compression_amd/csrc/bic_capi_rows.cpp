@@ -1,6 +1,6 @@
 // bic_capi_rows.cpp -- the row encoders' entry points (bic_encode_*, bic_row_index, bic_med_residual,
-// the adaptive EG coder): one driver for the staged and look-back encoders (run_fused), three sources
-// (planes, gray or RGB samples, P4 rasters) and the multi-pass fallback for rows wider than 16384 columns.
+// the adaptive EG coder): one driver for the staged and look-back encoders (run_fused), four sources
+// (planes, gray or RGB samples, a batch of gray frames, P4 rasters) and the multi-pass fallback for rows wider than 16384 columns.
 #include "bic_ctx.h"
 
 namespace {
@@ -235,6 +235,64 @@ int encode_gray_impl(bic_ctx* ctx, const GrayImage& img, int plane0, uint64_t* p
   return BIC_OK;
 }
 
+// nframes gray images of one geometry (frame f at img.data + f * stride) in one encode: fplanes planes per
+// frame, output entry f * fplanes + k = plane plane0 + k of frame f. As in encode_gray_impl only the count pass
+// (k_gray_strips_frames, one-byte samples) and the fallback's plane extraction know the frames; everything
+// after them is per (plane, row) over nframes * fplanes planes. One frame is encode_gray_impl itself.
+int encode_gray_frames_impl(bic_ctx* ctx, const GrayImage& img, size_t stride, int nframes, int plane0, int fplanes,
+                            uint64_t* planes, size_t rows, size_t cols, size_t wpr, int predict,
+                            const bic::CoderOut& og, const bic::CoderOut& oe, uint64_t* row_index = nullptr) {
+  const int bps = img.bps;
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (nframes < 1 || fplanes < 1 || (uint64_t)nframes * (uint64_t)fplanes > 65535 || (bps != 1 && bps != 2) ||
+      plane0 < 0 || plane0 + fplanes > 8 * bps || cols > SIZE_MAX / 4 || img.pitch < cols * (size_t)bps ||
+      !geom_ok(rows, cols, wpr) || !outs_ok(og, oe) || (rows && !img.data))
+    return BIC_EINVAL;
+  if (nframes > 1 && (rows > SIZE_MAX / img.pitch || stride < rows * img.pitch)) return BIC_EINVAL;
+  if (nframes == 1)
+    return encode_gray_impl(ctx, img, plane0, planes, {fplanes, rows, cols, wpr}, predict, og, oe, row_index);
+  const int nplanes = nframes * fplanes;
+  const Shape sh{nplanes, rows, cols, wpr};
+  if (rows == 0) return encode_planes_impl(ctx, planes, sh, predict, og, oe, row_index);  // zero counts and offsets
+  const bic::Geom g = bic::make_geom(rows, cols, wpr, nplanes);
+  const bool store_resid = !planes && predict;
+  const uint64_t eg_words = ((uint64_t)rows * (cols + 1) + 1 + 63) / 64;
+  const bool fuse = bps == 1 && bic::fused_supported(g) && !ctx->force_multipass && !ctx->two_pass &&
+                    !ctx->single_kernel && staged_pays(ctx, g) && bic::med_rows_supported(g, planes, nullptr) &&
+                    bic::gray_rows_supported(g, img.data, img.pitch, planes, bps);
+  if (fuse && !bic::gray_frames_supported(g, (uint64_t)nframes, predict ? 1 : 0, store_resid)) return BIC_EINVAL;
+  const bool eg_src = fuse && !planes && predict && oe.out && !oe.off && bic::gray_eg_supported(g) &&
+                      eg_words <= oe.slot && (og.out || !row_index) && !ctx->eg_src_off;
+  // no bitplanes wanted: the residual planes (or the fallback's planes) of all frames in the context's buffer
+  if (!planes && !eg_src && (rc = ensure_rbuf(ctx, (size_t)nplanes * rows * wpr * 8))) return rc;
+  if (!planes && !eg_src) planes = ctx->rbuf;
+  if (!fuse) {  // the same result through the separate calls, one extraction per frame
+    for (int f = 0; f < nframes; ++f) {
+      const uint8_t* fr = img.data + (size_t)f * stride;
+      uint64_t* fp = planes + (size_t)f * fplanes * rows * wpr;
+      if ((rc = bps == 2 ? bic_bitplanes_u16(ctx, fr, img.pitch, rows, cols, img.big_endian, plane0, fplanes, fp, wpr)
+                         : bic_bitplanes_u8_range(ctx, fr, img.pitch, rows, cols, plane0, fplanes, fp, wpr)))
+        return rc;
+    }
+    return encode_planes_impl(ctx, planes, sh, predict, og, oe, row_index);
+  }
+  const int pr = predict && !store_resid ? 1 : 0;  // R stored: the encoder codes it as given
+  bic::FusedCall c{g, planes, pr, bic::kEncStaged, {og, oe, og.out ? row_index : nullptr}};
+  c.rq.eg_src = eg_src;
+  c.rq.eg_src_one = ctx->eg_src_one;
+  c.rq.counted = true;
+  c.rq.ns = bic::gray_strips(g);
+  if ((rc = run_fused(ctx, c, [&](const bic::FusedArena& ar) {
+         bic::launch_gray_frames(ctx->cur, img.data, img.pitch, stride, (uint32_t)nframes, g, predict ? 1 : 0, plane0,
+                                 planes, ar.sones, ar.krec, ar.kpos, ar.counter, store_resid,
+                                 eg_src ? oe.out : nullptr, oe.slot, ctx->gray_code);
+       })))
+    return rc;
+  if (row_index && !og.out) return bic_row_index(ctx, planes, nplanes, rows, cols, wpr, pr, row_index);
+  return BIC_OK;
+}
+
 // nframes P4 rasters (frame f at raster + f * stride) as the planes of one encode. Only the count pass
 // (and the fallback's unpacking) knows the source; everything after it is per (plane, row).
 int encode_pbm_impl(bic_ctx* ctx, const uint8_t* raster, size_t stride, uint64_t* planes, const Shape& sh, int predict,
@@ -367,6 +425,28 @@ int bic_encode_gray_packed(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size
   return encode_gray_impl(ctx, {gray, pitch, 1, 0}, plane0, planes, {nplanes, rows, cols, wpr}, predict,
                           {out_golomb, slot_golomb, bits_golomb, off_golomb}, {out_eg, slot_eg, bits_eg, off_eg},
                           row_index);
+}
+
+int bic_encode_gray_frames(bic_ctx* ctx, const void* gray, size_t frame_stride, int nframes, size_t pitch, size_t rows,
+                           size_t cols, int sample_bytes, int big_endian, int plane0, int nplanes, uint64_t* planes,
+                           size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb, uint64_t* bits_golomb,
+                           uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg) {
+  return encode_gray_frames_impl(
+      ctx, {static_cast<const uint8_t*>(gray), pitch, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0},
+      frame_stride, nframes, plane0, nplanes, planes, rows, cols, wpr, predict, {out_golomb, slot_golomb, bits_golomb},
+      {out_eg, slot_eg, bits_eg});
+}
+
+int bic_encode_gray_frames_packed(bic_ctx* ctx, const void* gray, size_t frame_stride, int nframes, size_t pitch,
+                                  size_t rows, size_t cols, int sample_bytes, int big_endian, int plane0, int nplanes,
+                                  uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
+                                  uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg, size_t slot_eg,
+                                  uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
+  if ((out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
+  return encode_gray_frames_impl(
+      ctx, {static_cast<const uint8_t*>(gray), pitch, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0},
+      frame_stride, nframes, plane0, nplanes, planes, rows, cols, wpr, predict,
+      {out_golomb, slot_golomb, bits_golomb, off_golomb}, {out_eg, slot_eg, bits_eg, off_eg}, row_index);
 }
 
 int bic_encode_rgb(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t rows, size_t cols, int plane0, int nplanes,

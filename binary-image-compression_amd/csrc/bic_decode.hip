@@ -853,16 +853,27 @@ struct GrayArgs {
   uint64_t pitch;
   uint32_t sel0, sel1;  // blocks_to_samples' byte order (BPS 2)
   uint32_t omask;       // an output word's bits that some plane covers
+  uint64_t frame_stride;  // (FR) frame f's image at gray + f * frame_stride
 };
 // GC (BIC_OPT_GRAY_CODE): the planes are those of G(v) = v ^ (v >> 1). The accumulators stay G's (they
 // carry the column sums from row to row); the gathered blocks go through ungray_blocks, where the
 // sample bits no plane covers count as 0 before the XOR, not only after it.
-template <int BPS, bool VEC, bool SCAN, bool GC>
+// FR (bic_decode_gray_frames): blockIdx.y is the frame and a.nplanes ONE frame's plane count. The frame's
+// planes of D and of the chunk totals lie f * a.nplanes planes in and its image f * a.frame_stride bytes in
+// (64-bit offsets); from there the single image's walk. VEC then only when every frame's rows are 16-byte
+// aligned. The default instantiation is the single image's kernel.
+template <int BPS, bool VEC, bool SCAN, bool GC, bool FR = false>
 __global__ __launch_bounds__(256) void k_col_apply_gray(GrayArgs a) {
   using T = typename SegWord<kGraySeg>::load;  // kGraySeg bits of a D word
   using RT = typename SegWord<kGraySeg>::reg;
   constexpr int Q = kGraySeg, NG = Q / 8, SUB = 64 / Q, NB = 8 * BPS;
   constexpr int kGrayRows = 64 / (NB * (int)(sizeof(RT) / 4));  // 64 registers of loads in flight per lane
+  if constexpr (FR) {
+    const uint64_t f = blockIdx.y, fp = f * (uint32_t)a.nplanes;
+    a.D += fp * a.rows * a.wpr;
+    if constexpr (SCAN) a.ctot += fp * ((a.rows + kColChunk - 1) / kColChunk) * a.wpr;
+    a.gray += f * a.frame_stride;
+  }
   const uint32_t nch = (a.rows + kColChunk - 1) / kColChunk, segs = (a.cols + Q - 1) / Q;
   const uint32_t t = blockIdx.x * 256 + threadIdx.x;  // (nch * segs < 2^26: rows * (cols + 1) < 2^31)
   if (t >= nch * segs) return;
@@ -936,6 +947,8 @@ __global__ __launch_bounds__(256) void k_col_apply_gray(GrayArgs a) {
 
 void launch_col_apply_gray(hipStream_t s, const uint64_t* D, const uint64_t* ctot, uint32_t rows, uint32_t cols,
                            uint32_t wpr, uint32_t nplanes, const GrayOut& go) {
+  const bool frames = go.nframes > 1;
+  if (frames) nplanes /= go.nframes;  // (the call's planes are all frames'; the kernel and the masks take one frame's)
   GrayArgs a;
   a.D = D;
   a.ctot = ctot;
@@ -952,11 +965,16 @@ void launch_col_apply_gray(hipStream_t s, const uint64_t* D, const uint64_t* cto
   a.omask = go.bps == 1 ? lo * 0x01010101u : (go.big_endian ? hi | lo << 8 : lo | hi << 8) * 0x00010001u;
   const uint64_t nt = (uint64_t)((rows + kColChunk - 1) / kColChunk) * ((cols + kGraySeg - 1) / kGraySeg);
   const uint32_t grid = (uint32_t)((nt + 255) / 256);
-  const bool vec = reinterpret_cast<uintptr_t>(go.gray) % 16 == 0 && go.pitch % 16 == 0;
-#define BIC_CAGG(B, V, G)                                                 \
-  do {                                                                    \
-    if (ctot) k_col_apply_gray<B, V, true, G><<<grid, 256, 0, s>>>(a);    \
-    else k_col_apply_gray<B, V, false, G><<<grid, 256, 0, s>>>(a);        \
+  a.frame_stride = go.frame_stride;
+  const dim3 fgrid(grid, go.nframes);  // (nframes <= 65535)
+  const bool vec = reinterpret_cast<uintptr_t>(go.gray) % 16 == 0 && go.pitch % 16 == 0 &&
+                   (!frames || go.frame_stride % 16 == 0);
+#define BIC_CAGG(B, V, G)                                                                  \
+  do {                                                                                     \
+    if (frames && ctot) k_col_apply_gray<B, V, true, G, true><<<fgrid, 256, 0, s>>>(a);    \
+    else if (frames) k_col_apply_gray<B, V, false, G, true><<<fgrid, 256, 0, s>>>(a);      \
+    else if (ctot) k_col_apply_gray<B, V, true, G><<<grid, 256, 0, s>>>(a);                \
+    else k_col_apply_gray<B, V, false, G><<<grid, 256, 0, s>>>(a);                         \
   } while (0)
 #define BIC_CAG(B, V)                          \
   do {                                         \

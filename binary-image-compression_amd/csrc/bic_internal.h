@@ -73,6 +73,9 @@ struct GrayOut {
   uint64_t pitch;
   int plane0, bps, big_endian;
   int gray_code = 0;  // BIC_OPT_GRAY_CODE: the planes are G(v)'s, the samples stored are v's
+  // bic_decode_gray_frames: the call's planes are nframes groups, group f those of the image at gray + f * frame_stride
+  uint32_t nframes = 1;
+  uint64_t frame_stride = 0;
 };
 // bic_decode_rgb: the interleaved R G B samples (one byte each) the decoded planes go to; plane c * np + b
 // (np = the call's planes / 3) is bit plane0 + b of channel c
@@ -287,6 +290,14 @@ void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Ge
                       int big_endian = 0, bool gray_code = false, int color_transform = 0);
 // the count pass can write the EG stream (FusedRequest::eg_src): rows of whole 64-word strips only
 bool gray_eg_supported(const Geom& g);
+// launch_gray_rows for nframes images of one-byte samples in one launch (bic_encode_gray_frames): frame f at
+// gray + f * frame_stride, g.nplanes = nframes x one frame's planes, output plane f * (g.nplanes / nframes) + k
+// = plane plane0 + k of frame f (k_gray_strips_frames). gray_frames_supported: its grid fits 31 bits
+bool gray_frames_supported(const Geom& g, uint64_t nframes, int predict, bool store_resid);
+void launch_gray_frames(hipStream_t s, const uint8_t* gray, size_t pitch, uint64_t frame_stride, uint32_t nframes,
+                        const Geom& g, int predict, int plane0, uint64_t* planes, uint32_t* sones, int4* krec,
+                        uint32_t* kpos, uint32_t* zero, bool store_resid, uint64_t* out_e, uint64_t eg_stride,
+                        bool gray_code);
 
 void launch_patch_search(hipStream_t s, const uint64_t* plane, uint32_t rows, uint32_t cols, uint32_t wpr,
                          uint32_t W, uint32_t* besti, uint32_t* bestj, uint32_t* bestd);

@@ -1156,6 +1156,49 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_rgb(cons
                                                                            nullptr, 0, ch);
 }
 
+// Gray frames (bic_encode_gray_frames; DESIGN.md §3, gray frames in one call): nframes images of g.rows x
+// g.cols one-byte samples, frame f at gray + f * frame_stride (any byte alignment of the three: MIS when one
+// of gray, pitch and the stride is no multiple of 16 -- frame 0 may be aligned where frame 1 is not).
+// g.nplanes is ONE frame's plane count; output plane f * g.nplanes + k is plane plane0 + k of frame f. One wave
+// per (frame, row block, strip): the wave's index / (a frame's row blocks x strips) is its frame, so a row
+// block ends at its frame's last row and r0 = 0 is every frame's own first row (no row above, R(0,0) = 0);
+// the strips of a row block stay neighbouring waves. gray_strip_rows then runs on the frame as on a single
+// image, its plane-indexed outputs advanced by f * g.nplanes planes as k_gray_strips_rgb advances them per
+// channel. All offsets 64-bit.
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false>
+__global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_frames(
+    const uint8_t* __restrict__ gray, size_t pitch, uint64_t frame_stride, uint32_t nframes, Geom g, uint32_t ns,
+    uint32_t plane0, uint64_t* __restrict__ planes, uint32_t* __restrict__ sones, int4* __restrict__ krec,
+    uint32_t* __restrict__ kpos, uint32_t* __restrict__ zero, uint64_t* __restrict__ out_e, uint64_t eg_stride) {
+  __shared__ __attribute__((aligned(16))) uint32_t tab[kWaves][1024];  // strip_word_put tables
+  if (blockIdx.x == 0 && threadIdx.x < kZeroWords) zero[threadIdx.x] = 0;  // the encoder's counters
+  const uint32_t wv = wave_id();
+  uint32_t* tw = tab[wv];
+  constexpr uint32_t RPW = gray_rows_per_wave<PREDICT, STORE_R>();
+  const uint32_t wpf = ((g.rows + RPW - 1) / RPW) * ns;  // waves per frame (< 2^31: rows * (cols + 1) < 2^31)
+  const uint64_t gw = (uint64_t)xcd_remap(blockIdx.x, gridDim.x) * kWaves + wv;
+  const uint64_t f = gw / wpf;  // the wave's frame
+  if (f >= nframes) return;     // whole wave
+  const uint32_t fw = (uint32_t)(gw % wpf);
+  const uint32_t s = fw % ns;  // the strips of one row block are neighbouring waves
+  const uint32_t r0 = (fw / ns) * RPW;  // (< g.rows: fw < wpf)
+  const uint8_t* fg = gray + f * frame_stride;
+  const uint64_t skip = f * g.nplanes;  // output planes before the frame's
+  const uint64_t rskip = skip * g.rows * ns;
+  uint64_t* pl = planes + skip * g.plane_words;
+  uint64_t* oe = out_e + skip * eg_stride;
+  if ((s + 1) * 64 <= g.used && g.trail == ~0ull && g.nplanes == 8)
+    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 0, GC>(fg, pitch, g, ns, s, r0, plane0, pl, sones + rskip,
+                                                                   krec + rskip, kpos + rskip, tw, oe, eg_stride);
+  else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
+    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 0, GC>(fg, pitch, g, ns, s, r0, plane0, pl, sones + rskip,
+                                                                    krec + rskip, kpos + rskip, tw, oe, eg_stride);
+  else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
+    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 0, GC>(fg, pitch, g, ns, s, r0, plane0, pl,
+                                                                       sones + rskip, krec + rskip, kpos + rskip, tw,
+                                                                       nullptr, 0);
+}
+
 bool gray_eg_supported(const Geom& g) { return g.trail == ~0ull && g.used % 64 == 0 && g.used / 64 <= kMaxStrips; }
 
 // any gray alignment and pitch (rows not 16-byte aligned: load64_mis); every row must hold used * 64
@@ -1209,6 +1252,47 @@ void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Ge
 #undef BIC_GS2
 #undef BIC_GS
 #undef BIC_GSG
+}
+
+// the frame-aware count pass's grid (workgroups); 0: it would not fit 31 bits
+static uint32_t gray_frames_grid(const Geom& g, uint64_t nframes, int predict, bool store_resid) {
+  const uint32_t rpw = predict && store_resid ? gray_rows_per_wave<true, true>() : gray_rows_per_wave<true, false>();
+  const uint64_t wpf = (uint64_t)((g.rows + rpw - 1) / rpw) * gray_strips(g);
+  const uint64_t grid = (nframes * wpf + kWaves - 1) / kWaves;  // (nframes < 2^16, wpf < 2^31)
+  return grid < (1ull << 31) ? (uint32_t)grid : 0u;
+}
+bool gray_frames_supported(const Geom& g, uint64_t nframes, int predict, bool store_resid) {
+  return gray_frames_grid(g, nframes, predict, store_resid) != 0;
+}
+
+// g: the call's geometry, g.nplanes = nframes x one frame's planes
+void launch_gray_frames(hipStream_t s, const uint8_t* gray, size_t pitch, uint64_t frame_stride, uint32_t nframes,
+                        const Geom& g, int predict, int plane0, uint64_t* planes, uint32_t* sones, int4* krec,
+                        uint32_t* kpos, uint32_t* zero, bool store_resid, uint64_t* out_e, uint64_t eg_stride,
+                        bool gray_code) {
+  const uint32_t ns = gray_strips(g);
+  Geom gf = g;  // one frame's
+  gf.nplanes = g.nplanes / nframes;
+  const uint32_t grid = gray_frames_grid(g, nframes, predict, store_resid);
+  // every frame's rows 16-byte aligned, or the misaligned-load form (e.g. P5 files one after the other)
+  const bool mis = pitch % 16 != 0 || reinterpret_cast<uintptr_t>(gray) % 16 != 0 || (nframes > 1 && frame_stride % 16 != 0);
+  const bool egs = out_e && predict && store_resid && gray_eg_supported(g);
+#define BIC_GFG(P, R, E, M, G)                                                                                  \
+  k_gray_strips_frames<P, R, E, M, G><<<grid, kBlock, 0, s>>>(gray, pitch, frame_stride, nframes, gf, ns,       \
+                                                              (uint32_t)plane0, planes, sones, krec, kpos, zero, \
+                                                              out_e, eg_stride)
+#define BIC_GF(P, R, E, M)                             \
+  do {                                                 \
+    if (gray_code) BIC_GFG(P, R, E, M, true);          \
+    else BIC_GFG(P, R, E, M, false);                   \
+  } while (0)
+#define BIC_GF2(P, R) { if (mis) BIC_GF(P, R, false, true); else BIC_GF(P, R, false, false); }
+  if (egs) { if (mis) BIC_GF(true, true, true, true); else BIC_GF(true, true, true, false); }
+  else if (predict) { if (store_resid) BIC_GF2(true, true) else BIC_GF2(true, false) }
+  else BIC_GF2(false, false)  // without prediction R = P
+#undef BIC_GF2
+#undef BIC_GF
+#undef BIC_GFG
 }
 
 void launch_med_rows(hipStream_t s, const Geom& g, const uint64_t* planes, int predict, uint64_t* resid,

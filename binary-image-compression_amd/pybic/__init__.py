@@ -32,6 +32,7 @@ EXPORTS = [
     "bic_gf2_transpose", "bic_gf2_mul", "bic_planes_to_gray", "bic_match_encode_inv", "bic_match_encode_var", "bic_egad_row_index",
     "bic_encode_gray16", "bic_encode_gray16_packed", "bic_bitplanes_u16", "bic_decode_gray",
     "bic_encode_pbm", "bic_encode_pbm_packed", "bic_decode_pbm",
+    "bic_encode_gray_frames", "bic_encode_gray_frames_packed", "bic_decode_gray_frames",
     "bic_encode_rgb", "bic_encode_rgb_packed", "bic_bitplanes_rgb", "bic_planes_to_rgb", "bic_decode_rgb",
     "bic_rgb_p00",
     "bic_bsvd_update_coefficients", "bic_bsvd_update_dictionary", "bic_bsvd_learn",
@@ -191,6 +192,12 @@ def load(path=LIB_PATH):
     sig("bic_encode_pbm", i32, [vp, vp, sz, i32, sz, sz, vp, sz, i32, vp, sz, vp, vp, sz, vp])
     sig("bic_encode_pbm_packed", i32, [vp, vp, sz, i32, sz, sz, vp, sz, i32, vp, sz, vp, vp, vp, sz, vp, vp, vp])
     sig("bic_decode_pbm", i32, [vp, i32, vp, sz, vp, vp, vp, i32, sz, sz, i32, vp, vp, sz])
+    sig("bic_encode_gray_frames", i32, [vp, vp, sz, i32, sz, sz, sz, i32, i32, i32, i32, vp, sz, i32, vp, sz, vp, vp, sz,
+                                        vp])
+    sig("bic_encode_gray_frames_packed", i32, [vp, vp, sz, i32, sz, sz, sz, i32, i32, i32, i32, vp, sz, i32, vp, sz, vp,
+                                               vp, vp, sz, vp, vp, vp])
+    sig("bic_decode_gray_frames", i32, [vp, i32, vp, sz, vp, vp, vp, i32, i32, i32, sz, sz, i32, vp, i32, i32, vp, sz,
+                                        sz])
     sig("bic_encode_rgb", i32, [vp, vp, sz, sz, sz, i32, i32, vp, sz, i32, vp, sz, vp, vp, sz, vp])
     sig("bic_encode_rgb_packed", i32, [vp, vp, sz, sz, sz, i32, i32, vp, sz, i32, vp, sz, vp, vp, vp, sz, vp, vp, vp])
     sig("bic_bitplanes_rgb", i32, [vp, vp, sz, sz, sz, i32, i32, vp, sz])
@@ -718,6 +725,84 @@ class Context:
         self._chk(self.lib.bic_decode_pbm(self.h, coder, _p(streams), slot, _p(word_off), _p(plane_bits),
                                           _p(row_index), nframes, rows, cols, int(predict), _p(p00), _p(out), stride),
                   "bic_decode_pbm")
+        return out
+
+    def _frames_args(self, rows, cols, nframes, nplanes, sample_bytes, pitch, frame_stride, planes, wpr):
+        """pitch (default cols * sample_bytes), frame_stride (default rows * pitch), planes (None: NULL; True:
+        allocated here; or an int64 tensor [nframes * nplanes, rows, wpr]) and wpr (default ceil(cols / 64);
+        the one-read count pass needs it even)"""
+        pitch = cols * sample_bytes if pitch is None else pitch
+        stride = rows * pitch if frame_stride is None else frame_stride
+        wpr = wpr or (cols + 63) // 64
+        if planes is True:
+            planes = self.empty_i64(nframes * nplanes, rows, wpr)
+        wpr = planes.shape[-1] if planes is not None else wpr
+        return pitch, stride, planes, wpr
+
+    def encode_gray_frames(self, gray, rows, cols, nframes=1, frame_stride=None, pitch=None, sample_bytes=1,
+                           big_endian=True, nplanes=None, plane0=0, predict=True, planes=None, golomb=True, eg=True,
+                           slots=(None, None), outs=(None, None), bits=(None, None), wpr=None):
+        """bic_encode_gray_frames: gray = a uint8 device tensor whose first byte is frame 0's first sample byte
+        (any alignment, e.g. concatenated P5 files' bytes [data_offset:]), frame f frame_stride bytes further ->
+        (planes, (out_g, bits_g) or None, (out_e, bits_e) or None); entry f * nplanes + k of each is plane
+        plane0 + k of frame f. planes: see _frames_args (None: not returned)."""
+        nplanes = 8 * sample_bytes - plane0 if nplanes is None else nplanes
+        pitch, stride, planes, wpr = self._frames_args(rows, cols, nframes, nplanes, sample_bytes, pitch, frame_stride,
+                                                       planes, wpr)
+        n = nframes * nplanes
+        res = []
+        for on, coder, slot, out, b in ((golomb, CODER_GOLOMB, slots[0], outs[0], bits[0]),
+                                        (eg, CODER_EG, slots[1], outs[1], bits[1])):
+            if not on:
+                res.append((None, 0, None))
+                continue
+            slot = slot or self.slot_words(rows, cols, coder)
+            out = self.empty_i64(n, slot) if out is None else out
+            b = self.empty_i64(n) if b is None else b
+            res.append((out, slot, b))
+        (og, sg, bg), (oe, se, be) = res
+        self._bind_stream()
+        self._chk(self.lib.bic_encode_gray_frames(self.h, _p(gray), stride, nframes, pitch, rows, cols, sample_bytes,
+                                                  int(big_endian), plane0, nplanes, _p(planes), wpr, int(predict),
+                                                  _p(og), sg, _p(bg), _p(oe), se, _p(be)), "bic_encode_gray_frames")
+        return planes, ((og, bg) if golomb else None), ((oe, be) if eg else None)
+
+    def encode_gray_frames_packed(self, gray, rows, cols, nframes=1, frame_stride=None, pitch=None, sample_bytes=1,
+                                  big_endian=True, nplanes=None, plane0=0, predict=True, planes=None, golomb=True,
+                                  eg=True, slots=(None, None), outs=(None, None), bits=(None, None),
+                                  offs=(None, None), row_index=None, wpr=None):
+        """bic_encode_gray_frames_packed -> (planes, (out_g, bits_g, off_g) or None, (out_e, bits_e, off_e) or
+        None); the offsets run through all nframes * nplanes streams"""
+        nplanes = 8 * sample_bytes - plane0 if nplanes is None else nplanes
+        pitch, stride, planes, wpr = self._frames_args(rows, cols, nframes, nplanes, sample_bytes, pitch, frame_stride,
+                                                       planes, wpr)
+        (og, sg, bg, fg), (oe, se, be, fe) = self._packed_bufs(nframes * nplanes, rows, cols, golomb, eg, slots, outs,
+                                                               bits, offs)
+        self._bind_stream()
+        self._chk(self.lib.bic_encode_gray_frames_packed(self.h, _p(gray), stride, nframes, pitch, rows, cols,
+                                                         sample_bytes, int(big_endian), plane0, nplanes, _p(planes),
+                                                         wpr, int(predict), _p(og), sg, _p(bg), _p(fg), _p(oe), se,
+                                                         _p(be), _p(fe), _p(row_index)),
+                  "bic_encode_gray_frames_packed")
+        return planes, ((og, bg, fg) if golomb else None), ((oe, be, fe) if eg else None)
+
+    def decode_gray_frames(self, coder, streams, plane_bits, nframes, nplanes, rows, cols, predict=True,
+                           word_off=None, row_index=None, p00=None, plane0=0, sample_bytes=1, big_endian=True,
+                           out=None, pitch=None, frame_stride=None):
+        """bic_decode_gray_frames: the nframes * nplanes streams of encode_gray_frames (as for decode_planes) ->
+        uint8 device tensor of sample bytes, frame f at byte f * frame_stride (default rows * pitch), rows
+        `pitch` apart. out: a uint8 device tensor whose first byte is frame 0's first (any alignment). p00:
+        uint8 device tensor [nframes * nplanes] or None."""
+        pitch = pitch or cols * sample_bytes
+        stride = rows * pitch if frame_stride is None else frame_stride
+        if out is None:
+            out = self.torch.zeros((nframes - 1) * stride + rows * pitch, dtype=self.torch.uint8, device=self.dev)
+        slot = streams.shape[-1] if (word_off is None and streams.dim() == 2) else 0
+        self._bind_stream()
+        self._chk(self.lib.bic_decode_gray_frames(self.h, coder, _p(streams), slot, _p(word_off), _p(plane_bits),
+                                                  _p(row_index), nframes, plane0, nplanes, rows, cols, int(predict),
+                                                  _p(p00), sample_bytes, int(big_endian), _p(out), pitch, stride),
+                  "bic_decode_gray_frames")
         return out
 
     def _packed_bufs(self, n, rows, cols, golomb, eg, slots, outs, bits, offs):

@@ -301,6 +301,35 @@ int bic_encode_pbm_packed(bic_ctx* ctx, const uint8_t* raster, size_t frame_stri
                           size_t cols, uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb,
                           size_t slot_golomb, uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg,
                           size_t slot_eg, uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index);
+/* A batch of gray frames -> streams in one call: nframes images of one geometry (tiles of a scan, video
+ * frames, a queue of small images), each coded as bic_encode_gray_range / bic_encode_gray_packed (sample_bytes
+ * = 1) or bic_encode_gray16 / bic_encode_gray16_packed (sample_bytes = 2, big_endian as there; ignored for
+ * one-byte samples) codes it alone -- fresh coders per plane, no row above a frame's row 0, R(0,0) = 0 in
+ * every frame -- bit for bit. Frame f is rows x cols samples at (const uint8_t*)gray + f * frame_stride, row
+ * pitch `pitch` bytes (>= cols * sample_bytes); gray, pitch and frame_stride of any byte alignment (a buffer
+ * of concatenated P5 files + data_offset works as it lies); frame_stride >= rows * pitch (ignored when
+ * nframes = 1). plane0, nplanes: the plane range within a sample (plane0 + nplanes <= 8 * sample_bytes).
+ * There are nframes * nplanes outputs: plane, slot, bit count, offset and row-index entry f * nplanes + k
+ * belongs to plane plane0 + k of frame f; off_* have nframes * nplanes + 1 entries and run through all
+ * streams as bic_pack_streams would lay them out; planes, when given, holds nframes * nplanes * rows * wpr
+ * words. BIC_OPT_GRAY_CODE as in the single-image calls. Nullable planes and coders, BIC_ENOSPC, the domain
+ * rows * (cols + 1) < 2^31 per plane, the 15-byte read round-out and rows = 0 as for bic_encode_gray_packed.
+ * BIC_EINVAL also for nframes < 1, nframes * nplanes > 65535 and a frame_stride below rows * pitch.
+ * One-byte samples, the staged encoder (>= 32768 rows in all planes, or BIC_OPT_STAGED), an even wpr, cols
+ * <= 16384 and rows that hold ceil(cols/64)*64 readable bytes: one count kernel reads every frame once
+ * (with planes NULL, predict and the EG stream into slots it writes the EG streams itself); otherwise, and
+ * for two-byte samples, the same result through bic_bitplanes_u8_range / bic_bitplanes_u16 per frame and
+ * one bic_encode_planes2 / bic_encode_planes_packed. The device round trip is gray frames ->
+ * bic_encode_gray_frames_packed -> bic_decode_gray_frames. */
+int bic_encode_gray_frames(bic_ctx* ctx, const void* gray, size_t frame_stride, int nframes, size_t pitch, size_t rows,
+                           size_t cols, int sample_bytes, int big_endian, int plane0, int nplanes, uint64_t* planes,
+                           size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb, uint64_t* bits_golomb,
+                           uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg);
+int bic_encode_gray_frames_packed(bic_ctx* ctx, const void* gray, size_t frame_stride, int nframes, size_t pitch,
+                                  size_t rows, size_t cols, int sample_bytes, int big_endian, int plane0, int nplanes,
+                                  uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
+                                  uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg, size_t slot_eg,
+                                  uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index);
 
 /* ---- f1: decoders on the device (GolombDecoder.cpp:15-23 read order, eg.cpp:20-37 as written) --
  * row_index (device, nplanes * rows * 2 u64; nullable in the encoders above): per row of each plane,
@@ -346,6 +375,18 @@ int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slo
                     const uint64_t* word_off, const uint64_t* plane_bits, const uint64_t* row_index,
                     int plane0, int nplanes, size_t rows, size_t cols, int predict, const uint8_t* p00,
                     int sample_bytes, int big_endian, void* gray, size_t pitch);
+/* bic_decode_gray for every frame of a batch in one call: the nframes * nplanes streams in
+ * bic_encode_gray_frames' order (stream f * nplanes + k sets bit plane0 + k of frame f's samples; p00 one
+ * byte per stream), frame f written at (uint8_t*)gray + f * frame_stride (>= rows * pitch, ignored when
+ * nframes = 1; any byte alignment). Only the first cols * sample_bytes bytes of each row of each frame are
+ * written: pitch padding and the gap between frames keep the caller's bytes. Coders, row_index, BIC_EDATA,
+ * cols <= 16384 and rows = 0 as for bic_decode_gray; BIC_EINVAL also for nframes < 1 and nframes * nplanes >
+ * 65535. */
+int bic_decode_gray_frames(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words,
+                           const uint64_t* word_off, const uint64_t* plane_bits, const uint64_t* row_index,
+                           int nframes, int plane0, int nplanes, size_t rows, size_t cols, int predict,
+                           const uint8_t* p00, int sample_bytes, int big_endian, void* gray, size_t pitch,
+                           size_t frame_stride);
 /* streams -> interleaved RGB samples in one call: bic_decode_planes followed by bic_planes_to_rgb,
  * without the planes, as bic_decode_gray does for gray. The 3 * nplanes streams in bic_encode_rgb's
  * order (stream c * nplanes + k sets bit plane0 + k of channel c); coder, streams, slot_words, word_off,
