@@ -240,6 +240,10 @@ int bic_ctx_set_option(bic_ctx* ctx, int option, long value) {
       if (value < BIC_CT_NONE || value > BIC_CT_SUBTRACT_GREEN_FOLDED) return BIC_EINVAL;  // (likewise)
       ctx->color_transform = (int)value;
       return BIC_OK;
+    case BIC_OPT_SAMPLE_PREDICT:
+      if (value < BIC_SP_NONE || value > BIC_SP_LEFT_FOLDED) return BIC_EINVAL;  // (likewise)
+      ctx->sample_predict = (int)value;
+      return BIC_OK;
     default: return BIC_EINVAL;
   }
 }
@@ -263,6 +267,17 @@ int bic_rgb_p00(int color_transform, int gray_code, const uint8_t pixel[3], int 
     if (gray_code) v ^= v >> 1;
     for (int k = 0; k < nplanes; ++k) p00[c * nplanes + k] = (uint8_t)((v >> (plane0 + k)) & 1u);
   }
+  return BIC_OK;
+}
+
+int bic_gray_p00(int sample_predict, int gray_code, uint8_t sample, int plane0, int nplanes, uint8_t* p00) {
+  if (sample_predict < BIC_SP_NONE || sample_predict > BIC_SP_LEFT_FOLDED || (gray_code != 0 && gray_code != 1) || !p00 ||
+      plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8)
+    return BIC_EINVAL;
+  uint32_t v = sample;  // (no left neighbour: the sample is its own difference)
+  if (sample_predict == BIC_SP_LEFT_FOLDED) v = ((v << 1) ^ (v & 0x80u ? 0xffu : 0u)) & 0xffu;
+  if (gray_code) v ^= v >> 1;
+  for (int k = 0; k < nplanes; ++k) p00[k] = (uint8_t)((v >> (plane0 + k)) & 1u);
   return BIC_OK;
 }
 

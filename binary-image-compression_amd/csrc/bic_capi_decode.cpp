@@ -36,6 +36,11 @@ int run_decode(bic_ctx* ctx, const char* name, bic::DecodeCall& c) {
   c.flags = ctx->flags;
   c.egnib = ctx->lut + bic::kLutEgadDec;
   timed(ctx, name, [&] { bic::launch_decode(ctx->cur, c); });
+  if (c.sink == bic::DecodeCall::kGray && c.gray.sample_predict)  // the z samples just stored -> the samples, in place
+    timed(ctx, "sample_unpredict", [&] {
+      bic::launch_sample_unpredict(ctx->cur, c.gray.sample_predict, c.gray.gray, c.gray.pitch, c.gray.frame_stride,
+                                   c.gray.nframes, c.rows, c.cols);
+    });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
 }
@@ -73,6 +78,7 @@ int bic_decode_gray(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slo
   c.sink = bic::DecodeCall::kGray;
   c.gray = {static_cast<uint8_t*>(gray), (uint64_t)pitch, plane0, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0,
             ctx->gray_code ? 1 : 0};
+  c.gray.sample_predict = sample_bytes == 1 ? ctx->sample_predict : 0;
   return run_decode(ctx, "decode_gray", c);
 }
 
@@ -94,6 +100,7 @@ int bic_decode_gray_frames(bic_ctx* ctx, int coder, const uint64_t* streams, siz
   c.sink = bic::DecodeCall::kGray;
   c.gray = {static_cast<uint8_t*>(gray), (uint64_t)pitch, plane0, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0,
             ctx->gray_code ? 1 : 0, (uint32_t)nframes, nframes > 1 ? (uint64_t)frame_stride : 0};
+  c.gray.sample_predict = sample_bytes == 1 ? ctx->sample_predict : 0;
   return run_decode(ctx, "decode_gray_frames", c);
 }
 

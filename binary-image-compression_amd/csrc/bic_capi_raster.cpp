@@ -14,7 +14,7 @@ int bic_bitplanes_u8_range(bic_ctx* ctx, const uint8_t* gray, size_t pitch, size
   if (rows == 0) return BIC_OK;
   timed(ctx, "bitplanes_u8", [&] {
     bic::launch_bitplanes_u8(ctx->cur, gray, pitch, (uint32_t)rows, (uint32_t)cols, plane0, nplanes, planes,
-                             (uint32_t)wpr, ctx->gray_code);
+                             (uint32_t)wpr, ctx->gray_code, ctx->sample_predict);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
@@ -88,6 +88,11 @@ int bic_planes_to_gray(bic_ctx* ctx, const uint64_t* planes, int plane0, int npl
     bic::launch_planes_gray(ctx->cur, planes, (uint32_t)rows, (uint32_t)cols, (uint32_t)wpr, plane0, nplanes,
                             sample_bytes, static_cast<uint8_t*>(gray), (uint64_t)pitch, ctx->gray_code);
   });
+  if (sample_bytes == 1 && ctx->sample_predict)  // the z samples just stored -> the samples, in place
+    timed(ctx, "sample_unpredict", [&] {
+      bic::launch_sample_unpredict(ctx->cur, ctx->sample_predict, static_cast<uint8_t*>(gray), (uint64_t)pitch, 0, 1,
+                                   (uint32_t)rows, (uint32_t)cols);
+    });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
 }
@@ -135,7 +140,7 @@ int bic_pgm_bitplanes(bic_ctx* ctx, const uint8_t* raster, size_t rows, size_t c
   if (rows == 0) return BIC_OK;
   timed(ctx, "pgm_bitplanes", [&] {
     bic::launch_raster_planes(ctx->cur, raster, maxval < 256 ? 1 : 2, (uint32_t)rows, (uint32_t)cols, plane0, nplanes,
-                              planes, (uint32_t)wpr, 0, 1, ctx->gray_code);
+                              planes, (uint32_t)wpr, 0, 1, ctx->gray_code, 0, maxval < 256 ? ctx->sample_predict : 0);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;

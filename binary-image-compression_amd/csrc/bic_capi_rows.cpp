@@ -228,7 +228,8 @@ int encode_gray_impl(bic_ctx* ctx, const GrayImage& img, int plane0, uint64_t* p
   if ((rc = run_fused(ctx, c, [&](const bic::FusedArena& ar) {
          bic::launch_gray_rows(ctx->cur, img.data, img.pitch, g, predict ? 1 : 0, plane0, planes, ar.sones, ar.krec,
                                ar.kpos, ar.counter, store_resid, eg_src ? oe.out : nullptr, oe.slot, bps,
-                               img.big_endian, ctx->gray_code, bps == 3 ? ctx->color_transform : 0);
+                               img.big_endian, ctx->gray_code, bps == 3 ? ctx->color_transform : 0,
+                               bps == 1 ? ctx->sample_predict : 0);
        })))
     return rc;
   if (row_index && !og.out) return bic_row_index(ctx, planes, nplanes, rows, cols, wpr, pr, row_index);
@@ -286,7 +287,7 @@ int encode_gray_frames_impl(bic_ctx* ctx, const GrayImage& img, size_t stride, i
   if ((rc = run_fused(ctx, c, [&](const bic::FusedArena& ar) {
          bic::launch_gray_frames(ctx->cur, img.data, img.pitch, stride, (uint32_t)nframes, g, predict ? 1 : 0, plane0,
                                  planes, ar.sones, ar.krec, ar.kpos, ar.counter, store_resid,
-                                 eg_src ? oe.out : nullptr, oe.slot, ctx->gray_code);
+                                 eg_src ? oe.out : nullptr, oe.slot, ctx->gray_code, ctx->sample_predict);
        })))
     return rc;
   if (row_index && !og.out) return bic_row_index(ctx, planes, nplanes, rows, cols, wpr, pr, row_index);

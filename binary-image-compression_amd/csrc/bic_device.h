@@ -406,6 +406,30 @@ __host__ __device__ __forceinline__ uint32_t ct_inverse4(uint32_t z, uint32_t g)
   return ((d & 0x7f7f7f7fu) + (g & 0x7f7f7f7fu)) ^ ((d ^ g) & 0x80808080u);
 }
 
+// BIC_OPT_SAMPLE_PREDICT on the four samples of a dword (four neighbours of a row, byte 0 the leftmost): each
+// minus the sample on its left mod 256 (SP 1), that difference folded (SP 2) -- ct_forward4 with the row
+// shifted one sample to the right in the place of the green bytes. prev: the dword before x, whose top byte is
+// the left neighbour of x's byte 0.
+template <int SP>
+__device__ __forceinline__ uint32_t sp_forward4(uint32_t x, uint32_t prev) {
+  return ct_forward4<SP>(x, __builtin_amdgcn_alignbyte(x, prev, 3));
+}
+// and back on a dword of z samples: the unfolded differences' inclusive byte prefix sums mod 256 (no carry
+// crosses a byte); the caller adds what lies to the left of the dword to every byte (sp_add4).
+__host__ __device__ __forceinline__ uint32_t sp_add4(uint32_t a, uint32_t b) {
+  return ((a & 0x7f7f7f7fu) + (b & 0x7f7f7f7fu)) ^ ((a ^ b) & 0x80808080u);
+}
+template <int SP>
+__host__ __device__ __forceinline__ uint32_t sp_scan4(uint32_t z) {
+  uint32_t d = z;
+  if constexpr (SP == 2) {
+    const uint32_t l = z & 0x01010101u;
+    d = ((z >> 1) & 0x7f7f7f7fu) ^ ((l << 8) - l);
+  }
+  d = sp_add4(d, d << 8);
+  return sp_add4(d, d << 16);
+}
+
 // Bits of the Golomb codewords whose '1' lies in residual word w of a row (plus the end-of-row
 // codeword when eol) -- the length the row encoder's emission produces for that word -- without
 // forming any codeword. n = samples of the plane before the word's first 1, jp = column of the

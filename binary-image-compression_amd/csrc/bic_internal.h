@@ -45,7 +45,7 @@ ChunkScratch carve_chunk_scratch(void* base, const Geom& g);
 // Launchers (all asynchronous on `s`). flags[0] = overflow, flags[1] = domain error.
 void launch_bitplanes_u8(hipStream_t s, const uint8_t* gray, size_t pitch, uint32_t rows,
                          uint32_t cols, int plane0, int nplanes, uint64_t* planes, uint32_t wpr,
-                         bool gray_code = false);
+                         bool gray_code = false, int sample_predict = 0);
 void launch_count(hipStream_t s, const Geom& g, const uint64_t* planes, int predict,
                   const ChunkScratch& cs, uint64_t* resid, uint64_t* weight_out);
 void launch_scan_rows(hipStream_t s, const Geom& g, const ChunkScratch& cs);
@@ -76,6 +76,9 @@ struct GrayOut {
   // bic_decode_gray_frames: the call's planes are nframes groups, group f those of the image at gray + f * frame_stride
   uint32_t nframes = 1;
   uint64_t frame_stride = 0;
+  // BIC_OPT_SAMPLE_PREDICT (bps 1): the planes are T(row)'s; the sink stores the z samples and the entry point
+  // turns them into v's in place with launch_sample_unpredict, a pass of its own after the decode
+  int sample_predict = 0;
 };
 // bic_decode_rgb: the interleaved R G B samples (one byte each) the decoded planes go to; plane c * np + b
 // (np = the call's planes / 3) is bit plane0 + b of channel c
@@ -283,11 +286,12 @@ uint32_t gray_strips(const Geom& g);
 // words); planes is then unused. bps = 2 (bic_encode_gray16): samples of two bytes, big-endian
 // (pnm.cpp:71-74) or the host's order, planes plane0 .. of 16 (k_gray_strips16). bps = 3 (bic_encode_rgb):
 // interleaved RGB pixels of one-byte samples; g.nplanes = 3 np, output plane c * np + k is plane plane0 + k
-// of channel c (k_gray_strips_rgb; color_transform: BIC_OPT_COLOR_TRANSFORM, bps = 3 only)
+// of channel c (k_gray_strips_rgb; color_transform: BIC_OPT_COLOR_TRANSFORM, bps = 3 only).
+// sample_predict: BIC_OPT_SAMPLE_PREDICT (bps = 1 only)
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero,
                       bool store_resid = false, uint64_t* out_e = nullptr, uint64_t eg_stride = 0, int bps = 1,
-                      int big_endian = 0, bool gray_code = false, int color_transform = 0);
+                      int big_endian = 0, bool gray_code = false, int color_transform = 0, int sample_predict = 0);
 // the count pass can write the EG stream (FusedRequest::eg_src): rows of whole 64-word strips only
 bool gray_eg_supported(const Geom& g);
 // launch_gray_rows for nframes images of one-byte samples in one launch (bic_encode_gray_frames): frame f at
@@ -297,7 +301,7 @@ bool gray_frames_supported(const Geom& g, uint64_t nframes, int predict, bool st
 void launch_gray_frames(hipStream_t s, const uint8_t* gray, size_t pitch, uint64_t frame_stride, uint32_t nframes,
                         const Geom& g, int predict, int plane0, uint64_t* planes, uint32_t* sones, int4* krec,
                         uint32_t* kpos, uint32_t* zero, bool store_resid, uint64_t* out_e, uint64_t eg_stride,
-                        bool gray_code);
+                        bool gray_code, int sample_predict = 0);
 
 void launch_patch_search(hipStream_t s, const uint64_t* plane, uint32_t rows, uint32_t cols, uint32_t wpr,
                          uint32_t W, uint32_t* besti, uint32_t* bestj, uint32_t* bestd);
@@ -345,10 +349,15 @@ void launch_pbm(hipStream_t s, bool pack, const uint8_t* raster_in, uint8_t* ras
 // color_transform: BIC_OPT_COLOR_TRANSFORM (bpp / bps = 3 only)
 void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_t rows, uint32_t cols, int plane0,
                           int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch = 0, int big_endian = 1,
-                          bool gray_code = false, int color_transform = 0);
+                          bool gray_code = false, int color_transform = 0, int sample_predict = 0);
 void launch_planes_gray(hipStream_t s, const uint64_t* planes, uint32_t rows, uint32_t cols, uint32_t wpr, int plane0,
                         int nplanes, int bps, uint8_t* gray, uint64_t pitch, bool gray_code = false,
                         int color_transform = 0);
+// BIC_OPT_SAMPLE_PREDICT on the way back, in place on the one-byte z samples launch_planes_gray or the gray
+// decoder sink stored (k_sample_unpredict: a wave per row of each frame; 0: no launch). Only the rows' first
+// `cols` bytes are touched.
+void launch_sample_unpredict(hipStream_t s, int sample_predict, uint8_t* gray, uint64_t pitch, uint64_t frame_stride,
+                             uint32_t nframes, uint32_t rows, uint32_t cols);
 
 // GF(2) algebra (bic_gf2.hip). Both launches spread their rows over gridDim.y (at most 65,535): the transpose
 // four 64-row blocks per unit, the product 256 rows per unit, so either takes at most kGf2MaxRows source rows

@@ -36,7 +36,10 @@ __device__ __forceinline__ uint64_t transpose8x8(uint64_t x) {
 }
 
 // GC (BIC_OPT_GRAY_CODE): the planes of G(v) = v ^ (v >> 1), formed on the bytes before the transposes.
-template <bool VEC, bool GC>
+// SP (BIC_OPT_SAMPLE_PREDICT): before G every sample becomes its difference from the sample on its left (2: folded;
+// sp_forward4); the left of the word's first sample is one more byte load (0 at column 0), and the samples past the
+// row's end, which T would make non-zero, are cleared again.
+template <bool VEC, bool GC, int SP = 0>
 __global__ __launch_bounds__(kBlock) void k_bitplanes_u8(const uint8_t* __restrict__ gray, size_t pitch,
                                                          uint32_t rows, uint32_t cols, uint32_t used,
                                                          int plane0, int nplanes, uint64_t* __restrict__ planes,
@@ -66,6 +69,18 @@ __global__ __launch_bounds__(kBlock) void k_bitplanes_u8(const uint8_t* __restri
       px[g8] = v;
     }
   }
+  if constexpr (SP != 0) {
+    uint32_t prev = w ? (uint32_t)src[-1] << 24 : 0u;
+    const uint32_t valid = min(64u, cols - 64 * w);
+#pragma unroll
+    for (int g8 = 0; g8 < 8; ++g8) {
+      const uint32_t lo = (uint32_t)px[g8], hi = (uint32_t)(px[g8] >> 32);
+      const uint64_t t = ((uint64_t)sp_forward4<SP>(hi, lo) << 32) | sp_forward4<SP>(lo, prev);
+      prev = hi;
+      const uint32_t nb = valid > 8u * g8 ? min(8u, valid - 8u * g8) : 0u;  // the group's samples inside the row
+      px[g8] = nb == 8 ? t : t & ((1ull << (8 * nb)) - 1);
+    }
+  }
   if constexpr (GC) {
 #pragma unroll
     for (int g8 = 0; g8 < 8; ++g8) px[g8] ^= (px[g8] >> 1) & 0x7f7f7f7f7f7f7f7full;
@@ -87,15 +102,24 @@ __global__ __launch_bounds__(kBlock) void k_bitplanes_u8(const uint8_t* __restri
 }
 
 void launch_bitplanes_u8(hipStream_t s, const uint8_t* gray, size_t pitch, uint32_t rows,
-                         uint32_t cols, int plane0, int nplanes, uint64_t* planes, uint32_t wpr, bool gray_code) {
+                         uint32_t cols, int plane0, int nplanes, uint64_t* planes, uint32_t wpr, bool gray_code,
+                         int sample_predict) {
   const uint32_t used = (cols + 63) / 64;
   const uint64_t waves = (uint64_t)rows * ((used + 63) / 64);
   const uint32_t grid = (uint32_t)((waves + kWaves - 1) / kWaves);
   const bool vec = (pitch % 16 == 0) && (((uintptr_t)gray) % 16 == 0);
-#define BIC_BP(V, G) k_bitplanes_u8<V, G><<<grid, kBlock, 0, s>>>(gray, pitch, rows, cols, used, plane0, nplanes, planes, wpr)
+#define BIC_BPS(V, G, S) \
+  k_bitplanes_u8<V, G, S><<<grid, kBlock, 0, s>>>(gray, pitch, rows, cols, used, plane0, nplanes, planes, wpr)
+#define BIC_BP(V, G)                               \
+  do {                                             \
+    if (sample_predict == 1) BIC_BPS(V, G, 1);     \
+    else if (sample_predict == 2) BIC_BPS(V, G, 2); \
+    else BIC_BPS(V, G, 0);                         \
+  } while (0)
   if (gray_code) { if (vec) BIC_BP(true, true); else BIC_BP(false, true); }
   else { if (vec) BIC_BP(true, false); else BIC_BP(false, false); }
 #undef BIC_BP
+#undef BIC_BPS
 }
 
 // ------------------------------------------------------------------------------------
@@ -732,8 +756,15 @@ struct Raw16 {
 // of the same twelve uint4 and subtract them byte-wise (ct_forward4) before G. T is not linear over XOR,
 // where the split, med and G are: the pixel before the strip is T of it and its green (src[-2]), and the next
 // segment's D byte is T(cb, its green) ^ T(ub, its green), not T of cb ^ ub. The green wave runs as with CT 0.
+// SP (BIC_OPT_SAMPLE_PREDICT, S16 = 0 only): every sample becomes its difference from the sample on its left
+// (1: mod 256, 2: folded) before G. In the lane's 64 bytes the left neighbour is the byte before (sp_forward4 down
+// the 16 dwords); the left of byte 0 is lane - 1's byte 63 (a one-lane DPP shift), for lane 0 the raw pixel before
+// the strip, 0 at column 0. Like CT it is not linear over XOR: the pixel before the strip becomes T of it (its own
+// left is src[-2]: column >= 4095 there), and the next segment's D byte is T(cb, cp[-1]) ^ T(ub, the byte left of
+// ub), with no left at the next row's column 0. Lanes past g.used and pad samples hold garbage after T; it reaches
+// one sample to the right at most, all in bits that `mask` clears.
 template <bool PREDICT, bool FULL, bool STORE_R, bool NP8, bool EGS, bool MIS = false, int S16 = 0, bool GC = false,
-          int CT = 0>
+          int CT = 0, int SP = 0>
 __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray, size_t pitch, const Geom& g,
                                                 uint32_t ns, uint32_t s, uint32_t r0, uint32_t plane0,
                                                 uint64_t* __restrict__ planes, uint32_t* __restrict__ sones,
@@ -833,6 +864,19 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
     else lb = (lane == 0 && s > 0) ? (uint32_t)src[-1] : 0u;
     if constexpr (S16 == 3 && CT != 0)
       if (bo != 1 && lane == 0 && s > 0) lb = ct_forward4<CT>(lb, (uint32_t)src[-2]) & 0xffu;
+    if constexpr (SP != 0) {
+      static_assert(S16 == 0 || SP == 0, "sample prediction: one-byte gray samples only");
+      uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v[3].w, 0x138, 0xf, 0xf, true);  // lane - 1's last dword
+      if (lane == 0) prev = lb << 24;  // the raw pixel before the strip (0 in strip 0)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const uint4 x = v[q];
+        v[q] = make_uint4(sp_forward4<SP>(x.x, prev), sp_forward4<SP>(x.y, x.x), sp_forward4<SP>(x.z, x.y),
+                          sp_forward4<SP>(x.w, x.z));
+        prev = x.w;
+      }
+      if (lane == 0 && s > 0) lb = ct_forward4<SP>(lb, (uint32_t)src[-2]) & 0xffu;
+    }
     if constexpr (GC) {
       if constexpr (!S16) gray4(v);
       lb ^= lb >> 1;
@@ -892,6 +936,11 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
           cb = ct_forward4<CT>(cb, cp[o]) & 0xffu;
           if (rn) ub = ct_forward4<CT>(ub, cp[o - (int64_t)pitch]) & 0xffu;
         }
+      if constexpr (SP != 0) {  // each byte with its own left one (the next row's column 0 has none)
+        const bool nl = lastS && lane == 0;
+        cb = ct_forward4<SP>(cb, nl ? 0u : (uint32_t)cp[-1]) & 0xffu;
+        if (rn) ub = ct_forward4<SP>(ub, nl ? 0u : (uint32_t)cp[-1 - (int64_t)pitch]) & 0xffu;
+      }
       uint32_t gd0 = cb ^ ub;
       if constexpr (GC) {
         gd0 ^= gd0 >> 1;
@@ -1003,7 +1052,7 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
 #ifndef BIC_GRAY_WAVES
 #define BIC_GRAY_WAVES 4
 #endif
-template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false>
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false, int SP = 0>
 __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips(const uint8_t* __restrict__ gray, size_t pitch, Geom g,
                                                         uint32_t ns, uint32_t plane0, uint64_t* __restrict__ planes,
                                                         uint32_t* __restrict__ sones, int4* __restrict__ krec,
@@ -1021,14 +1070,14 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips(const ui
   if (r0 >= g.rows) return;  // whole wave
   // strips wholly inside a row without pad bits (every strip of C3) drop the masks and the lane tests
   if ((s + 1) * 64 <= g.used && g.trail == ~0ull && g.nplanes == 8)
-    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 0, GC>(gray, pitch, g, ns, s, r0, plane0, planes, sones, krec,
-                                                                   kpos, tw, out_e, eg_stride);
+    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 0, GC, 0, SP>(gray, pitch, g, ns, s, r0, plane0, planes, sones,
+                                                                          krec, kpos, tw, out_e, eg_stride);
   else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
-    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 0, GC>(gray, pitch, g, ns, s, r0, plane0, planes, sones, krec,
-                                                                    kpos, tw, out_e, eg_stride);
+    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 0, GC, 0, SP>(gray, pitch, g, ns, s, r0, plane0, planes, sones,
+                                                                           krec, kpos, tw, out_e, eg_stride);
   else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
-    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 0, GC>(gray, pitch, g, ns, s, r0, plane0, planes, sones,
-                                                                       krec, kpos, tw, nullptr, 0);
+    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 0, GC, 0, SP>(gray, pitch, g, ns, s, r0, plane0, planes,
+                                                                              sones, krec, kpos, tw, nullptr, 0);
 }
 
 // Two-byte samples (bic_encode_gray16; pnm.cpp:71-74 big-endian, or the host's uint16_t). The planes
@@ -1165,7 +1214,7 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_rgb(cons
 // the strips of a row block stay neighbouring waves. gray_strip_rows then runs on the frame as on a single
 // image, its plane-indexed outputs advanced by f * g.nplanes planes as k_gray_strips_rgb advances them per
 // channel. All offsets 64-bit.
-template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false>
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false, int SP = 0>
 __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_frames(
     const uint8_t* __restrict__ gray, size_t pitch, uint64_t frame_stride, uint32_t nframes, Geom g, uint32_t ns,
     uint32_t plane0, uint64_t* __restrict__ planes, uint32_t* __restrict__ sones, int4* __restrict__ krec,
@@ -1188,15 +1237,17 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_frames(
   uint64_t* pl = planes + skip * g.plane_words;
   uint64_t* oe = out_e + skip * eg_stride;
   if ((s + 1) * 64 <= g.used && g.trail == ~0ull && g.nplanes == 8)
-    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 0, GC>(fg, pitch, g, ns, s, r0, plane0, pl, sones + rskip,
-                                                                   krec + rskip, kpos + rskip, tw, oe, eg_stride);
+    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 0, GC, 0, SP>(fg, pitch, g, ns, s, r0, plane0, pl,
+                                                                          sones + rskip, krec + rskip, kpos + rskip, tw,
+                                                                          oe, eg_stride);
   else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
-    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 0, GC>(fg, pitch, g, ns, s, r0, plane0, pl, sones + rskip,
-                                                                    krec + rskip, kpos + rskip, tw, oe, eg_stride);
+    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 0, GC, 0, SP>(fg, pitch, g, ns, s, r0, plane0, pl,
+                                                                           sones + rskip, krec + rskip, kpos + rskip, tw,
+                                                                           oe, eg_stride);
   else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
-    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 0, GC>(fg, pitch, g, ns, s, r0, plane0, pl,
-                                                                       sones + rskip, krec + rskip, kpos + rskip, tw,
-                                                                       nullptr, 0);
+    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 0, GC, 0, SP>(fg, pitch, g, ns, s, r0, plane0, pl,
+                                                                              sones + rskip, krec + rskip, kpos + rskip,
+                                                                              tw, nullptr, 0);
 }
 
 bool gray_eg_supported(const Geom& g) { return g.trail == ~0ull && g.used % 64 == 0 && g.used / 64 <= kMaxStrips; }
@@ -1210,7 +1261,8 @@ bool gray_rows_supported(const Geom& g, const void* gray, size_t pitch, const vo
 
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero, bool store_resid,
-                      uint64_t* out_e, uint64_t eg_stride, int bps, int big_endian, bool gray_code, int color_transform) {
+                      uint64_t* out_e, uint64_t eg_stride, int bps, int big_endian, bool gray_code, int color_transform,
+                      int sample_predict) {
   const uint32_t ns = gray_strips(g);
   const uint32_t rpw = predict && store_resid ? gray_rows_per_wave<true, true>() : gray_rows_per_wave<true, false>();
   const uint64_t units = (uint64_t)(g.rows + rpw - 1) / rpw;  // row groups per strip
@@ -1236,6 +1288,12 @@ void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Ge
       k_gray_strips16<P, R, E, M, G><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0,                 \
                                                              big_endian ? 1u : 0u, planes, sones, krec, kpos,      \
                                                              zero, out_e, eg_stride);                              \
+    else if (sample_predict == 1)                                                                                  \
+      k_gray_strips<P, R, E, M, G, 1><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes, sones, \
+                                                              krec, kpos, zero, out_e, eg_stride);                 \
+    else if (sample_predict == 2)                                                                                  \
+      k_gray_strips<P, R, E, M, G, 2><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes, sones, \
+                                                              krec, kpos, zero, out_e, eg_stride);                 \
     else                                                                                                           \
       k_gray_strips<P, R, E, M, G><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes, sones,    \
                                                            krec, kpos, zero, out_e, eg_stride);                    \
@@ -1269,7 +1327,7 @@ bool gray_frames_supported(const Geom& g, uint64_t nframes, int predict, bool st
 void launch_gray_frames(hipStream_t s, const uint8_t* gray, size_t pitch, uint64_t frame_stride, uint32_t nframes,
                         const Geom& g, int predict, int plane0, uint64_t* planes, uint32_t* sones, int4* krec,
                         uint32_t* kpos, uint32_t* zero, bool store_resid, uint64_t* out_e, uint64_t eg_stride,
-                        bool gray_code) {
+                        bool gray_code, int sample_predict) {
   const uint32_t ns = gray_strips(g);
   Geom gf = g;  // one frame's
   gf.nplanes = g.nplanes / nframes;
@@ -1277,10 +1335,16 @@ void launch_gray_frames(hipStream_t s, const uint8_t* gray, size_t pitch, uint64
   // every frame's rows 16-byte aligned, or the misaligned-load form (e.g. P5 files one after the other)
   const bool mis = pitch % 16 != 0 || reinterpret_cast<uintptr_t>(gray) % 16 != 0 || (nframes > 1 && frame_stride % 16 != 0);
   const bool egs = out_e && predict && store_resid && gray_eg_supported(g);
-#define BIC_GFG(P, R, E, M, G)                                                                                  \
-  k_gray_strips_frames<P, R, E, M, G><<<grid, kBlock, 0, s>>>(gray, pitch, frame_stride, nframes, gf, ns,       \
-                                                              (uint32_t)plane0, planes, sones, krec, kpos, zero, \
-                                                              out_e, eg_stride)
+#define BIC_GFS(P, R, E, M, G, S)                                                                                  \
+  k_gray_strips_frames<P, R, E, M, G, S><<<grid, kBlock, 0, s>>>(gray, pitch, frame_stride, nframes, gf, ns,       \
+                                                                 (uint32_t)plane0, planes, sones, krec, kpos, zero, \
+                                                                 out_e, eg_stride)
+#define BIC_GFG(P, R, E, M, G)                              \
+  do {                                                      \
+    if (sample_predict == 1) BIC_GFS(P, R, E, M, G, 1);     \
+    else if (sample_predict == 2) BIC_GFS(P, R, E, M, G, 2); \
+    else BIC_GFS(P, R, E, M, G, 0);                         \
+  } while (0)
 #define BIC_GF(P, R, E, M)                             \
   do {                                                 \
     if (gray_code) BIC_GFG(P, R, E, M, true);          \
@@ -1293,6 +1357,7 @@ void launch_gray_frames(hipStream_t s, const uint8_t* gray, size_t pitch, uint64
 #undef BIC_GF2
 #undef BIC_GF
 #undef BIC_GFG
+#undef BIC_GFS
 }
 
 void launch_med_rows(hipStream_t s, const Geom& g, const uint64_t* planes, int predict, uint64_t* resid,

@@ -77,7 +77,9 @@ __global__ __launch_bounds__(256) void k_pbm_pack2(const uint64_t* __restrict__ 
 // plane0 .. of it as output planes channel * nplanes ..
 // CT (BIC_OPT_COLOR_TRANSFORM, BPP 3): channels 0 and 2 also pick the green bytes and go through ct_forward4
 // before G (1: subtract green, 2: folded; an instantiation each).
-template <int BPP, bool GC, int CT = 0>
+// SP (BIC_OPT_SAMPLE_PREDICT, BPP 1): every sample minus the one on its left (2: folded) before G, as in
+// k_bitplanes_u8; the left of the word's first sample is one more byte load, 0 at column 0.
+template <int BPP, bool GC, int CT = 0, int SP = 0>
 __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict__ base, uint32_t off, uint32_t rows,
                                                        uint32_t cols, int plane0, int nplanes,
                                                        uint64_t* __restrict__ planes, uint32_t wpr, uint64_t pitch,
@@ -122,6 +124,16 @@ __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict
                __builtin_amdgcn_perm((uint32_t)(a >> 32), (uint32_t)a, selL);
       hi8[g] = ((uint64_t)__builtin_amdgcn_perm((uint32_t)(b >> 32), (uint32_t)b, selH) << 32) |
                __builtin_amdgcn_perm((uint32_t)(a >> 32), (uint32_t)a, selH);
+    }
+  }
+  if constexpr (SP != 0) {
+    static_assert(BPP == 1 || SP == 0, "sample prediction: one-byte gray samples only");
+    uint32_t prev = w ? (uint32_t)base[p0 - 1] << 24 : 0u;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {  // (samples past the row's end: `mask` below)
+      const uint32_t lo = (uint32_t)lo8[g], hi = (uint32_t)(lo8[g] >> 32);
+      lo8[g] = ((uint64_t)sp_forward4<SP>(hi, lo) << 32) | sp_forward4<SP>(lo, prev);
+      prev = hi;
     }
   }
   if constexpr (GC) {
@@ -312,7 +324,7 @@ void launch_pbm(hipStream_t s, bool pack, const uint8_t* raster_in, uint8_t* ras
 
 void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_t rows, uint32_t cols, int plane0,
                           int nplanes, uint64_t* planes, uint32_t wpr, uint64_t pitch, int big_endian, bool gray_code,
-                          int color_transform) {
+                          int color_transform, int sample_predict) {
   const uintptr_t r = reinterpret_cast<uintptr_t>(raster);
   if (!pitch) pitch = (uint64_t)cols * bpp;
   const uint32_t selL = big_endian ? 0x07050301u : 0x06040200u, selH = big_endian ? 0x06040200u : 0x07050301u;
@@ -338,11 +350,84 @@ void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_
                                                               wpr, pitch, 0, 0);
     return;
   }
+  if (bpp == 1 && sample_predict) {
+#define BIC_RPS(G, S) \
+  k_raster_planes<1, G, 0, S><<<grid, 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr, pitch, 0, 0)
+    if (sample_predict == 1) { if (gray_code) BIC_RPS(true, 1); else BIC_RPS(false, 1); }
+    else { if (gray_code) BIC_RPS(true, 2); else BIC_RPS(false, 2); }
+#undef BIC_RPS
+    return;
+  }
 #define BIC_RP(B, G) \
   k_raster_planes<B, G><<<grid, 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr, pitch, selL, selH)
   if (gray_code) { if (bpp == 1) BIC_RP(1, true); else BIC_RP(2, true); }
   else { if (bpp == 1) BIC_RP(1, false); else BIC_RP(2, false); }
 #undef BIC_RP
+}
+
+// BIC_OPT_SAMPLE_PREDICT on the way back (one-byte samples), in place on the z samples k_planes_gray /
+// k_col_apply_gray have just stored: v(j) = (v(j - 1) + d(j)) & 0xff along the row from v(-1) = 0, d = z (SP 1)
+// or its unfolding (SP 2). One wave per (frame, row) walks the row in pieces of 1024 bytes, 16 per lane: the
+// dwords' inclusive byte prefix sums (sp_scan4), the dwords' totals down the lane, the lanes' totals scanned
+// across the wave by DPP (row_shr 1 2 4 8 inside a row of 16, row_bcast 15 and 31 across the rows), and a
+// wave-uniform carry byte into the next piece. A lane whose 16 bytes lie inside the row and are 16-byte aligned
+// loads and stores them as one uint4; at the row's end, or with a misaligned row, it takes bytes -- nothing
+// past the row's first `cols` bytes is read or written (pitch padding and the gap between frames stay).
+template <int SP>
+__global__ __launch_bounds__(256) void k_sample_unpredict(uint8_t* __restrict__ gray, uint64_t pitch,
+                                                          uint64_t frame_stride, uint32_t rows, uint32_t cols) {
+  const uint32_t row = blockIdx.x * 4 + wave_id();
+  if (row >= rows) return;  // whole wave
+  const uint32_t lane = lane_id();
+  uint8_t* p = gray + (uint64_t)blockIdx.y * frame_stride + (uint64_t)row * pitch;
+  const bool al = reinterpret_cast<uintptr_t>(p) % 16 == 0;  // (wave-uniform)
+  uint32_t carry = 0;  // the sample left of the piece
+  for (uint32_t c0 = 0; c0 < cols; c0 += 1024) {
+    const uint32_t j = c0 + 16 * lane;
+    const bool vec = al && j + 16 <= cols;
+    uint32_t x[4] = {0, 0, 0, 0};
+    if (vec) {
+      const uint4 t = *reinterpret_cast<const uint4*>(p + j);
+      x[0] = t.x, x[1] = t.y, x[2] = t.z, x[3] = t.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (j + i < cols) x[i >> 2] |= (uint32_t)p[j + i] << (8 * (i & 3));
+    }
+    uint32_t run = 0;  // the lane's bytes before the dword, summed
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      x[q] = sp_add4(sp_scan4<SP>(x[q]), run * 0x01010101u);
+      run = x[q] >> 24;
+    }
+    // the lanes' totals, inclusive across the wave (mod 256: the high bits are dropped at the end)
+    uint32_t t = run;
+    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x111, 0xf, 0xf, true);
+    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x112, 0xf, 0xf, true);
+    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x114, 0xf, 0xf, true);
+    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x118, 0xf, 0xf, true);
+    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x142, 0xa, 0xf, false);  // rows 1, 3 += row 0's, 2's total
+    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x143, 0xc, 0xf, false);  // rows 2, 3 += rows 0-1's total
+    const uint32_t add = ((t - run + carry) & 0xffu) * 0x01010101u;  // what lies left of the lane's bytes
+#pragma unroll
+    for (int q = 0; q < 4; ++q) x[q] = sp_add4(x[q], add);
+    carry = ((uint32_t)__builtin_amdgcn_readlane((int)t, 63) + carry) & 0xffu;
+    if (vec) {
+      *reinterpret_cast<uint4*>(p + j) = make_uint4(x[0], x[1], x[2], x[3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (j + i < cols) p[j + i] = (uint8_t)(x[i >> 2] >> (8 * (i & 3)));
+    }
+  }
+}
+
+void launch_sample_unpredict(hipStream_t s, int sample_predict, uint8_t* gray, uint64_t pitch, uint64_t frame_stride,
+                             uint32_t nframes, uint32_t rows, uint32_t cols) {
+  if (!sample_predict || !rows || !cols || !nframes) return;
+  const dim3 grid((rows + 3) / 4, nframes);  // (nframes <= 65535)
+  if (sample_predict == 1) k_sample_unpredict<1><<<grid, 256, 0, s>>>(gray, pitch, frame_stride, rows, cols);
+  else k_sample_unpredict<2><<<grid, 256, 0, s>>>(gray, pitch, frame_stride, rows, cols);
 }
 
 }  // namespace bic

@@ -34,7 +34,7 @@ EXPORTS = [
     "bic_encode_pbm", "bic_encode_pbm_packed", "bic_decode_pbm",
     "bic_encode_gray_frames", "bic_encode_gray_frames_packed", "bic_decode_gray_frames",
     "bic_encode_rgb", "bic_encode_rgb_packed", "bic_bitplanes_rgb", "bic_planes_to_rgb", "bic_decode_rgb",
-    "bic_rgb_p00",
+    "bic_rgb_p00", "bic_gray_p00",
     "bic_bsvd_update_coefficients", "bic_bsvd_update_dictionary", "bic_bsvd_learn",
     "bic_dict_encode", "bic_set_dict_block",
     "bic_bsvd_update_dictionary_proximus", "bic_bsvd_learn_du", "bic_set_bsvd_rounds",
@@ -50,6 +50,10 @@ EXPORTS = [
 OPT_COLOR_TRANSFORM = 8
 CT_NONE, CT_SUBTRACT_GREEN, CT_SUBTRACT_GREEN_FOLDED = 0, 1, 2
 _CT_NAMES = {"none": CT_NONE, "subtract_green": CT_SUBTRACT_GREEN, "subtract_green_folded": CT_SUBTRACT_GREEN_FOLDED}
+# BIC_OPT_SAMPLE_PREDICT and its values (include/bic.h)
+OPT_SAMPLE_PREDICT = 9
+SP_NONE, SP_LEFT, SP_LEFT_FOLDED = 0, 1, 2
+_SP_NAMES = {"none": SP_NONE, "left": SP_LEFT, "left_folded": SP_LEFT_FOLDED}
 
 # bic_bsvd_learn_du rules (include/bic.h)
 BSVD_DU_STEEPEST, BSVD_DU_PROXIMUS = 0, 1
@@ -204,6 +208,7 @@ def load(path=LIB_PATH):
     sig("bic_planes_to_rgb", i32, [vp, vp, i32, i32, sz, sz, sz, vp, sz])
     sig("bic_decode_rgb", i32, [vp, i32, vp, sz, vp, vp, vp, i32, i32, sz, sz, i32, vp, vp, sz])
     sig("bic_rgb_p00", i32, [i32, i32, C.c_char_p, i32, i32, vp])
+    sig("bic_gray_p00", i32, [i32, i32, C.c_uint8, i32, i32, vp])
     sig("bic_bsvd_update_coefficients", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_update_dictionary", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_learn", i32, [vp, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
@@ -855,6 +860,17 @@ class Context:
             mode = _CT_NAMES[mode]
         self._chk(self.lib.bic_ctx_set_option(self.h, OPT_COLOR_TRANSFORM, int(mode)), "bic_ctx_set_option")
 
+    def set_sample_predict(self, mode):
+        """left-neighbour prediction of one-byte gray samples in front of the bitplane split and its inverse on
+        the way back (BIC_OPT_SAMPLE_PREDICT, default 0): 0 / "none", 1 / "left" ((v - left) mod 256, left = 0 at
+        column 0), 2 / "left_folded" (that difference with the sign folded into bit 0). Any other value raises
+        BicError and leaves the mode as it was. Two-byte samples, the RGB, PBM and planes-only calls ignore it."""
+        if isinstance(mode, str):
+            if mode not in _SP_NAMES:
+                raise BicError(BIC_EINVAL, "bic_ctx_set_option")
+            mode = _SP_NAMES[mode]
+        self._chk(self.lib.bic_ctx_set_option(self.h, OPT_SAMPLE_PREDICT, int(mode)), "bic_ctx_set_option")
+
     def set_multipass(self, on=True):
         self._chk(self.lib.bic_ctx_set_option(self.h, 1, int(on)), "bic_ctx_set_option")
 
@@ -1301,6 +1317,18 @@ def rgb_p00(color_transform, gray_code, pixel, plane0=0, nplanes=8):
     rc = load().bic_rgb_p00(int(color_transform), int(gray_code), px, int(plane0), int(nplanes), out.ctypes.data)
     if rc != BIC_OK:
         raise BicError(rc, "bic_rgb_p00")
+    return out
+
+
+def gray_p00(sample_predict, gray_code, sample, plane0=0, nplanes=8):
+    """bic_gray_p00: the p00 bytes decode_gray / decode_gray_frames need for a one-byte image (or frame) whose
+    first sample is `sample` under the given sample prediction (0 / 1 / 2) and Gray-code setting -> uint8 numpy
+    array [nplanes] (host only)"""
+    out = np.zeros(max(int(nplanes), 1), np.uint8)
+    rc = load().bic_gray_p00(int(sample_predict), int(gray_code), int(sample) & 0xFF, int(plane0), int(nplanes),
+                             out.ctypes.data)
+    if rc != BIC_OK:
+        raise BicError(rc, "bic_gray_p00")
     return out
 
 

@@ -133,6 +133,29 @@ int bic_reserve(bic_ctx* ctx, int nplanes, size_t rows, size_t cols);
 #define BIC_CT_NONE 0
 #define BIC_CT_SUBTRACT_GREEN 1
 #define BIC_CT_SUBTRACT_GREEN_FOLDED 2
+/* BIC_OPT_SAMPLE_PREDICT: left-neighbour prediction T of one-byte gray samples in front of the bitplane split, so
+ * that a smooth row leaves its high planes empty. BIC_SP_NONE (0, default): none, every call as it was.
+ * BIC_SP_LEFT (1): d(i,j) = (v(i,j) - v(i,j-1)) mod 256, with v(i,-1) = 0 in every row of every frame.
+ * BIC_SP_LEFT_FOLDED (2): the same d, read as a signed 8-bit value and folded as BIC_CT_SUBTRACT_GREEN_FOLDED
+ * folds its differences, z = ((d << 1) ^ (d >> 7)) & 0xFF (0 -> 0, -1 -> 1, 1 -> 2, -128 -> 255; inverse
+ * d = (z >> 1) ^ -(z & 1)). Both are bijections on a row. Any other value is BIC_EINVAL and leaves the setting
+ * as it was.
+ *  - Samples to planes, one-byte samples only (bic_bitplanes_u8, _u8_range, bic_pgm_bitplanes with maxval < 256,
+ *    bic_encode_gray, _range, _packed, bic_encode_gray_frames, _packed with sample_bytes = 1): T, then the Gray
+ *    code if BIC_OPT_GRAY_CODE is on, then the plane0 shift and the split. Planes, streams, bit counts, packed
+ *    offsets and the row index equal those of the same call with the option off on the image T(img).
+ *  - Planes to samples (bic_planes_to_gray, bic_decode_gray, bic_decode_gray_frames, each with sample_bytes = 1):
+ *    the sample z is assembled from the given planes as with the option off (bits no plane covers count as 0,
+ *    then the un-Gray step and its mask), unfolded in mode 2 to d, then v(j) = (v(j-1) + d(j)) & 0xFF along the
+ *    row from v(-1) = 0, and all eight bits of the result are written (a pass of its own over the stored rows'
+ *    first cols bytes; pitch padding and the gap between frames keep the caller's bytes). The result is the
+ *    image exactly when plane0 = 0 and nplanes = 8; for any other range it is this formula.
+ * Two-byte samples (bic_bitplanes_u16, bic_encode_gray16*, sample_bytes = 2, bic_pgm_bitplanes with maxval >= 256),
+ * the RGB calls, the PBM calls and the planes-only calls ignore the option. */
+#define BIC_OPT_SAMPLE_PREDICT 9
+#define BIC_SP_NONE 0
+#define BIC_SP_LEFT 1
+#define BIC_SP_LEFT_FOLDED 2
 int bic_ctx_set_option(bic_ctx* ctx, int option, long value);
 
 /* ---- a2: bitplane extraction (bitplane_tool.cpp:24-30) -----------------------------------
@@ -277,6 +300,12 @@ int bic_planes_to_rgb(bic_ctx* ctx, const uint64_t* planes, int plane0, int npla
  * BIC_EINVAL: a mode outside 0..2, gray_code outside 0..1, a NULL pointer, plane0 < 0, nplanes < 1 or
  * plane0 + nplanes > 8. */
 int bic_rgb_p00(int color_transform, int gray_code, const uint8_t pixel[3], int plane0, int nplanes, uint8_t* p00);
+/* The gray twin: the p00 bytes bic_decode_gray / bic_decode_gray_frames need for a one-byte image (or frame) whose
+ * first sample is `sample`, under the given BIC_OPT_SAMPLE_PREDICT and BIC_OPT_GRAY_CODE values. The first sample
+ * has no left neighbour, so it is its own difference: p00[k] = bit plane0 + k of fold(sample) in mode 2, of the
+ * sample in modes 0 and 1, after the Gray code. Host code, no context. p00: host, nplanes bytes. BIC_EINVAL: a
+ * mode outside 0..2, gray_code outside 0..1, a NULL p00, plane0 < 0, nplanes < 1 or plane0 + nplanes > 8. */
+int bic_gray_p00(int sample_predict, int gray_code, uint8_t sample, int plane0, int nplanes, uint8_t* p00);
 /* P4 rasters -> streams in one call: bic_pbm_unpack per frame followed by bic_encode_planes2 /
  * bic_encode_planes_packed, bit-identical streams, bit counts, offsets and row index. Frame f's raster
  * (pbm.cpp:29-77: rows x ceil(cols/8) bytes, MSB = leftmost pixel) lies at raster + f * frame_stride:
