@@ -119,6 +119,26 @@ int bic_decode_rgb(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot
   return run_decode(ctx, "decode_rgb", c);
 }
 
+int bic_decode_rgb_frames(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
+                          const uint64_t* plane_bits, const uint64_t* index, int nframes, int plane0, int nplanes,
+                          size_t rows, size_t cols, int predict, const uint8_t* p00, uint8_t* rgb, size_t pitch,
+                          size_t frame_stride) {
+  int rc = bind(ctx);
+  if (rc) return rc;
+  if (plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8 || nframes < 1 ||
+      (uint64_t)nframes * 3u * (uint64_t)nplanes > 65535 || cols > SIZE_MAX / 4 || pitch < 3 * cols)
+    return BIC_EINVAL;
+  if (nframes > 1 && pitch && (rows > SIZE_MAX / pitch || frame_stride < rows * pitch)) return BIC_EINVAL;
+  bic::DecodeCall c{};
+  if ((rc = stream_call(c, coder, streams, slot_words, word_off, plane_bits, index, nframes * 3 * nplanes, rows, cols,
+                        (cols + 63) / 64, predict, p00, rgb)) || !c.rows)
+    return rc;
+  c.sink = bic::DecodeCall::kRgb;
+  c.rgb = {rgb, (uint64_t)pitch, plane0, ctx->gray_code ? 1 : 0, ctx->color_transform, (uint32_t)nframes,
+           nframes > 1 ? (uint64_t)frame_stride : 0};
+  return run_decode(ctx, "decode_rgb_frames", c);
+}
+
 int bic_decode_pbm(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
                    const uint64_t* plane_bits, const uint64_t* index, int nframes, size_t rows, size_t cols, int predict,
                    const uint8_t* p00, uint8_t* raster, size_t frame_stride) {

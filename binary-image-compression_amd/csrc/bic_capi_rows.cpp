@@ -1,6 +1,6 @@
 // bic_capi_rows.cpp -- the row encoders' entry points (bic_encode_*, bic_row_index, bic_med_residual,
 // the adaptive EG coder): one driver for the staged and look-back encoders (run_fused), four sources
-// (planes, gray or RGB samples, a batch of gray frames, P4 rasters) and the multi-pass fallback for rows wider than 16384 columns.
+// (planes, gray or RGB samples, a batch of gray or RGB frames, P4 rasters) and the multi-pass fallback for rows wider than 16384 columns.
 #include "bic_ctx.h"
 
 namespace {
@@ -90,9 +90,10 @@ bool outs_ok(const bic::CoderOut& g, const bic::CoderOut& e) {
 // pass -> prefix -> rows -> finish. c comes as {g, planes, predict, mode, rq}.
 // count: the caller's count pass (bic_encode_gray*'s bitplane kernel, rq.counted), given the arena;
 // without one the staged prefix counts for itself. prefix_only (bic_row_index): the staged prefix
-// alone, recorded as "row_index".
+// alone, recorded as "row_index". count_name: the count pass's profile name.
 template <typename Count>
-int run_fused(bic_ctx* ctx, bic::FusedCall& c, Count&& count, bool prefix_only = false) {
+int run_fused(bic_ctx* ctx, bic::FusedCall& c, Count&& count, bool prefix_only = false,
+              const char* count_name = "bitplanes_count") {
   int rc = ensure_scratch(ctx, bic::fused_scratch_bytes(c.g));
   if (rc) return rc;
   c.ar = bic::carve_fused_arena(ctx->scratch, c.g);
@@ -104,7 +105,7 @@ int run_fused(bic_ctx* ctx, bic::FusedCall& c, Count&& count, bool prefix_only =
   // anyway: calls on one context are ordered by the caller)
   c.rq.zero_ready = !staged && !ctx->captured && ctx->scratch_zero_prev >= c.ar.zero_bytes;
   if (!staged) bic::launch_lookback_clear(ctx->cur, c);
-  if (c.rq.counted) timed(ctx, "bitplanes_count", [&] { count(c.ar); });
+  if (c.rq.counted) timed(ctx, count_name, [&] { count(c.ar); });
   // staged encoder: per-row counts, scans and Golomb lengths (every row's offsets known up front)
   if (staged)
     timed(ctx, prefix_only ? "row_index" : "encode_prefix",
@@ -240,14 +241,18 @@ int encode_gray_impl(bic_ctx* ctx, const GrayImage& img, int plane0, uint64_t* p
 // frame, output entry f * fplanes + k = plane plane0 + k of frame f. As in encode_gray_impl only the count pass
 // (k_gray_strips_frames, one-byte samples) and the fallback's plane extraction know the frames; everything
 // after them is per (plane, row) over nframes * fplanes planes. One frame is encode_gray_impl itself.
+// bps = 3 (bic_encode_rgb_frames): interleaved RGB frames, fplanes = 3 x one channel's planes as in
+// encode_gray_impl, entry (f * 3 + c) * (fplanes / 3) + k = plane plane0 + k of channel c of frame f; the count
+// pass is k_gray_strips_rgb_frames ("rgb_frames_count" in the profile), the fallback bic_bitplanes_rgb per frame.
 int encode_gray_frames_impl(bic_ctx* ctx, const GrayImage& img, size_t stride, int nframes, int plane0, int fplanes,
                             uint64_t* planes, size_t rows, size_t cols, size_t wpr, int predict,
                             const bic::CoderOut& og, const bic::CoderOut& oe, uint64_t* row_index = nullptr) {
   const int bps = img.bps;
+  const int nchan = bps == 3 ? 3 : 1, cplanes = fplanes / nchan;  // a sample's planes: of one channel
   int rc = bind(ctx);
   if (rc) return rc;
-  if (nframes < 1 || fplanes < 1 || (uint64_t)nframes * (uint64_t)fplanes > 65535 || (bps != 1 && bps != 2) ||
-      plane0 < 0 || plane0 + fplanes > 8 * bps || cols > SIZE_MAX / 4 || img.pitch < cols * (size_t)bps ||
+  if (nframes < 1 || cplanes < 1 || (uint64_t)nframes * (uint64_t)fplanes > 65535 || bps < 1 || bps > 3 ||
+      plane0 < 0 || plane0 + cplanes > (bps == 2 ? 16 : 8) || cols > SIZE_MAX / 4 || img.pitch < cols * (size_t)bps ||
       !geom_ok(rows, cols, wpr) || !outs_ok(og, oe) || (rows && !img.data))
     return BIC_EINVAL;
   if (nframes > 1 && (rows > SIZE_MAX / img.pitch || stride < rows * img.pitch)) return BIC_EINVAL;
@@ -259,10 +264,12 @@ int encode_gray_frames_impl(bic_ctx* ctx, const GrayImage& img, size_t stride, i
   const bic::Geom g = bic::make_geom(rows, cols, wpr, nplanes);
   const bool store_resid = !planes && predict;
   const uint64_t eg_words = ((uint64_t)rows * (cols + 1) + 1 + 63) / 64;
-  const bool fuse = bps == 1 && bic::fused_supported(g) && !ctx->force_multipass && !ctx->two_pass &&
+  const bool fuse = bps != 2 && bic::fused_supported(g) && !ctx->force_multipass && !ctx->two_pass &&
                     !ctx->single_kernel && staged_pays(ctx, g) && bic::med_rows_supported(g, planes, nullptr) &&
                     bic::gray_rows_supported(g, img.data, img.pitch, planes, bps);
-  if (fuse && !bic::gray_frames_supported(g, (uint64_t)nframes, predict ? 1 : 0, store_resid)) return BIC_EINVAL;
+  if (fuse && !(bps == 3 ? bic::rgb_frames_supported(g, (uint64_t)nframes, predict ? 1 : 0, store_resid)
+                         : bic::gray_frames_supported(g, (uint64_t)nframes, predict ? 1 : 0, store_resid)))
+    return BIC_EINVAL;
   const bool eg_src = fuse && !planes && predict && oe.out && !oe.off && bic::gray_eg_supported(g) &&
                       eg_words <= oe.slot && (og.out || !row_index) && !ctx->eg_src_off;
   // no bitplanes wanted: the residual planes (or the fallback's planes) of all frames in the context's buffer
@@ -272,7 +279,8 @@ int encode_gray_frames_impl(bic_ctx* ctx, const GrayImage& img, size_t stride, i
     for (int f = 0; f < nframes; ++f) {
       const uint8_t* fr = img.data + (size_t)f * stride;
       uint64_t* fp = planes + (size_t)f * fplanes * rows * wpr;
-      if ((rc = bps == 2 ? bic_bitplanes_u16(ctx, fr, img.pitch, rows, cols, img.big_endian, plane0, fplanes, fp, wpr)
+      if ((rc = bps == 3 ? bic_bitplanes_rgb(ctx, fr, img.pitch, rows, cols, plane0, cplanes, fp, wpr)
+                : bps == 2 ? bic_bitplanes_u16(ctx, fr, img.pitch, rows, cols, img.big_endian, plane0, fplanes, fp, wpr)
                          : bic_bitplanes_u8_range(ctx, fr, img.pitch, rows, cols, plane0, fplanes, fp, wpr)))
         return rc;
     }
@@ -284,11 +292,19 @@ int encode_gray_frames_impl(bic_ctx* ctx, const GrayImage& img, size_t stride, i
   c.rq.eg_src_one = ctx->eg_src_one;
   c.rq.counted = true;
   c.rq.ns = bic::gray_strips(g);
-  if ((rc = run_fused(ctx, c, [&](const bic::FusedArena& ar) {
-         bic::launch_gray_frames(ctx->cur, img.data, img.pitch, stride, (uint32_t)nframes, g, predict ? 1 : 0, plane0,
-                                 planes, ar.sones, ar.krec, ar.kpos, ar.counter, store_resid,
-                                 eg_src ? oe.out : nullptr, oe.slot, ctx->gray_code, ctx->sample_predict);
-       })))
+  if ((rc = run_fused(
+           ctx, c,
+           [&](const bic::FusedArena& ar) {
+             if (bps == 3)
+               bic::launch_rgb_frames(ctx->cur, img.data, img.pitch, stride, (uint32_t)nframes, g, predict ? 1 : 0,
+                                      plane0, planes, ar.sones, ar.krec, ar.kpos, ar.counter, store_resid,
+                                      eg_src ? oe.out : nullptr, oe.slot, ctx->gray_code, ctx->color_transform);
+             else
+               bic::launch_gray_frames(ctx->cur, img.data, img.pitch, stride, (uint32_t)nframes, g, predict ? 1 : 0,
+                                       plane0, planes, ar.sones, ar.krec, ar.kpos, ar.counter, store_resid,
+                                       eg_src ? oe.out : nullptr, oe.slot, ctx->gray_code, ctx->sample_predict);
+           },
+           false, bps == 3 ? "rgb_frames_count" : "bitplanes_count")))
     return rc;
   if (row_index && !og.out) return bic_row_index(ctx, planes, nplanes, rows, cols, wpr, pr, row_index);
   return BIC_OK;
@@ -432,6 +448,7 @@ int bic_encode_gray_frames(bic_ctx* ctx, const void* gray, size_t frame_stride, 
                            size_t cols, int sample_bytes, int big_endian, int plane0, int nplanes, uint64_t* planes,
                            size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb, uint64_t* bits_golomb,
                            uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg) {
+  if (sample_bytes != 1 && sample_bytes != 2) return BIC_EINVAL;
   return encode_gray_frames_impl(
       ctx, {static_cast<const uint8_t*>(gray), pitch, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0},
       frame_stride, nframes, plane0, nplanes, planes, rows, cols, wpr, predict, {out_golomb, slot_golomb, bits_golomb},
@@ -443,11 +460,31 @@ int bic_encode_gray_frames_packed(bic_ctx* ctx, const void* gray, size_t frame_s
                                   uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
                                   uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg, size_t slot_eg,
                                   uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index) {
-  if ((out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
+  if ((sample_bytes != 1 && sample_bytes != 2) || (out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
   return encode_gray_frames_impl(
       ctx, {static_cast<const uint8_t*>(gray), pitch, sample_bytes, sample_bytes == 2 && big_endian ? 1 : 0},
       frame_stride, nframes, plane0, nplanes, planes, rows, cols, wpr, predict,
       {out_golomb, slot_golomb, bits_golomb, off_golomb}, {out_eg, slot_eg, bits_eg, off_eg}, row_index);
+}
+
+int bic_encode_rgb_frames(bic_ctx* ctx, const uint8_t* rgb, size_t frame_stride, int nframes, size_t pitch, size_t rows,
+                          size_t cols, int plane0, int nplanes, uint64_t* planes, size_t wpr, int predict,
+                          uint64_t* out_golomb, size_t slot_golomb, uint64_t* bits_golomb, uint64_t* out_eg,
+                          size_t slot_eg, uint64_t* bits_eg) {
+  if (nplanes < 1 || nplanes > 8) return BIC_EINVAL;
+  return encode_gray_frames_impl(ctx, {rgb, pitch, 3, 0}, frame_stride, nframes, plane0, 3 * nplanes, planes, rows, cols,
+                                 wpr, predict, {out_golomb, slot_golomb, bits_golomb}, {out_eg, slot_eg, bits_eg});
+}
+
+int bic_encode_rgb_frames_packed(bic_ctx* ctx, const uint8_t* rgb, size_t frame_stride, int nframes, size_t pitch,
+                                 size_t rows, size_t cols, int plane0, int nplanes, uint64_t* planes, size_t wpr,
+                                 int predict, uint64_t* out_golomb, size_t slot_golomb, uint64_t* bits_golomb,
+                                 uint64_t* off_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg,
+                                 uint64_t* off_eg, uint64_t* row_index) {
+  if (nplanes < 1 || nplanes > 8 || (out_golomb && !off_golomb) || (out_eg && !off_eg)) return BIC_EINVAL;
+  return encode_gray_frames_impl(ctx, {rgb, pitch, 3, 0}, frame_stride, nframes, plane0, 3 * nplanes, planes, rows, cols,
+                                 wpr, predict, {out_golomb, slot_golomb, bits_golomb, off_golomb},
+                                 {out_eg, slot_eg, bits_eg, off_eg}, row_index);
 }
 
 int bic_encode_rgb(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t rows, size_t cols, int plane0, int nplanes,

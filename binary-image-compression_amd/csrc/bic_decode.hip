@@ -1003,17 +1003,28 @@ struct RgbArgs {
   uint8_t* rgb;
   uint64_t pitch;
   uint32_t omask;
+  uint64_t frame_stride;  // (FR) frame f's image at rgb + f * frame_stride
 };
 // CT (BIC_OPT_COLOR_TRANSFORM): the accumulators stay in the transformed (and Gray) domain -- they carry the
 // column sums -- and the row's R' and B' dwords, after ungray_blocks and omask, go through ct_inverse4 with the
 // row's G before the interleave (1: subtract green, 2: folded; an instantiation each).
-template <bool VEC, bool SCAN, bool GC, int CT = 0>
+// FR (bic_decode_rgb_frames): blockIdx.y is the frame, as in k_col_apply_gray. The frame's 3 a.nplanes planes of
+// D and of the chunk totals lie f * 3 * a.nplanes planes in and its image f * a.frame_stride bytes in (64-bit
+// offsets); from there the single image's walk. VEC then only when every frame's rows are 16-byte aligned. The
+// default instantiation is the single image's kernel.
+template <bool VEC, bool SCAN, bool GC, int CT = 0, bool FR = false>
 __global__ __launch_bounds__(256) void k_col_apply_rgb(RgbArgs a) {
   using T = typename SegWord<kGraySeg>::load;
   using RT = typename SegWord<kGraySeg>::reg;
   constexpr int Q = kGraySeg, NG = Q / 8, SUB = 64 / Q, NB = 24;
   constexpr int kRgbRows = 64 / (NB * (int)(sizeof(RT) / 4));  // 64 registers of loads in flight per lane
   static_assert(kRgbRows >= 1 && Q == 16, "a segment of 16 pixels: 48 bytes, three 16-byte stores");
+  if constexpr (FR) {
+    const uint64_t f = blockIdx.y, fp = f * (3u * (uint32_t)a.nplanes);
+    a.D += fp * a.rows * a.wpr;
+    if constexpr (SCAN) a.ctot += fp * ((a.rows + kColChunk - 1) / kColChunk) * a.wpr;
+    a.rgb += f * a.frame_stride;
+  }
   const uint32_t nch = (a.rows + kColChunk - 1) / kColChunk, segs = (a.cols + Q - 1) / Q;
   const uint32_t t = blockIdx.x * 256 + threadIdx.x;  // (nch * segs < 2^26: rows * (cols + 1) < 2^31)
   if (t >= nch * segs) return;
@@ -1105,6 +1116,8 @@ __global__ __launch_bounds__(256) void k_col_apply_rgb(RgbArgs a) {
 
 void launch_col_apply_rgb(hipStream_t s, const uint64_t* D, const uint64_t* ctot, uint32_t rows, uint32_t cols,
                           uint32_t wpr, uint32_t nplanes, const RgbOut& ro) {
+  const bool frames = ro.nframes > 1;
+  if (frames) nplanes /= ro.nframes;  // (the call's planes are all frames'; the kernel and the masks take one frame's)
   RgbArgs a;
   a.D = D;
   a.ctot = ctot;
@@ -1118,16 +1131,22 @@ void launch_col_apply_rgb(hipStream_t s, const uint64_t* D, const uint64_t* ctot
   a.omask = ((((1u << a.nplanes) - 1u) << ro.plane0) & 0xffu) * 0x01010101u;
   const uint64_t nt = (uint64_t)((rows + kColChunk - 1) / kColChunk) * ((cols + kGraySeg - 1) / kGraySeg);
   const uint32_t grid = (uint32_t)((nt + 255) / 256);
-  const bool vec = reinterpret_cast<uintptr_t>(ro.rgb) % 16 == 0 && ro.pitch % 16 == 0;
-#define BIC_CARC(V, G, C)                                                   \
-  do {                                                                      \
-    if (ctot) k_col_apply_rgb<V, true, G, C><<<grid, 256, 0, s>>>(a);       \
-    else k_col_apply_rgb<V, false, G, C><<<grid, 256, 0, s>>>(a);           \
+  a.frame_stride = ro.frame_stride;
+  const dim3 fgrid(grid, ro.nframes);  // (nframes <= 65535)
+  const bool vec = reinterpret_cast<uintptr_t>(ro.rgb) % 16 == 0 && ro.pitch % 16 == 0 &&
+                   (!frames || ro.frame_stride % 16 == 0);
+#define BIC_CARC(V, G, C)                                                                   \
+  do {                                                                                      \
+    if (frames && ctot) k_col_apply_rgb<V, true, G, C, true><<<fgrid, 256, 0, s>>>(a);      \
+    else if (frames) k_col_apply_rgb<V, false, G, C, true><<<fgrid, 256, 0, s>>>(a);        \
+    else if (ctot) k_col_apply_rgb<V, true, G, C><<<grid, 256, 0, s>>>(a);                  \
+    else k_col_apply_rgb<V, false, G, C><<<grid, 256, 0, s>>>(a);                           \
   } while (0)
 #define BIC_CAR(V, G)                                                  \
   do {                                                                 \
     if (ro.color_transform == 1) BIC_CARC(V, G, 1);                    \
     else if (ro.color_transform == 2) BIC_CARC(V, G, 2);               \
+    else if (frames) BIC_CARC(V, G, 0);                                \
     else if (ctot) k_col_apply_rgb<V, true, G><<<grid, 256, 0, s>>>(a); \
     else k_col_apply_rgb<V, false, G><<<grid, 256, 0, s>>>(a);         \
   } while (0)

@@ -88,6 +88,9 @@ struct RgbOut {
   int plane0;
   int gray_code = 0;
   int color_transform = 0;  // BIC_OPT_COLOR_TRANSFORM: the planes are T(pixel)'s, the samples stored the pixel's
+  // bic_decode_rgb_frames: the call's planes are nframes groups of 3 np, group f those of the image at rgb + f * frame_stride
+  uint32_t nframes = 1;
+  uint64_t frame_stride = 0;
 };
 // bic_decode_pbm: the P4 rasters the decoded planes go to (plane f = frame f at raster + f * stride)
 struct PbmOut {
@@ -302,6 +305,14 @@ void launch_gray_frames(hipStream_t s, const uint8_t* gray, size_t pitch, uint64
                         const Geom& g, int predict, int plane0, uint64_t* planes, uint32_t* sones, int4* krec,
                         uint32_t* kpos, uint32_t* zero, bool store_resid, uint64_t* out_e, uint64_t eg_stride,
                         bool gray_code, int sample_predict = 0);
+// launch_gray_rows' bps = 3 form for nframes interleaved RGB images in one launch (bic_encode_rgb_frames): frame f at
+// rgb + f * frame_stride, g.nplanes = nframes x 3 x one channel's planes np, output plane (f * 3 + c) * np + k = plane
+// plane0 + k of channel c of frame f (k_gray_strips_rgb_frames). rgb_frames_supported: its grid fits 31 bits
+bool rgb_frames_supported(const Geom& g, uint64_t nframes, int predict, bool store_resid);
+void launch_rgb_frames(hipStream_t s, const uint8_t* rgb, size_t pitch, uint64_t frame_stride, uint32_t nframes,
+                       const Geom& g, int predict, int plane0, uint64_t* planes, uint32_t* sones, int4* krec,
+                       uint32_t* kpos, uint32_t* zero, bool store_resid, uint64_t* out_e, uint64_t eg_stride,
+                       bool gray_code, int color_transform);
 
 void launch_patch_search(hipStream_t s, const uint64_t* plane, uint32_t rows, uint32_t cols, uint32_t wpr,
                          uint32_t W, uint32_t* besti, uint32_t* bestj, uint32_t* bestd);

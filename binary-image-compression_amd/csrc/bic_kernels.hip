@@ -1250,6 +1250,54 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_frames(
                                                                               tw, nullptr, 0);
 }
 
+// RGB frames (bic_encode_rgb_frames; DESIGN.md §3, RGB frames in one call): k_gray_strips_rgb and
+// k_gray_strips_frames composed. nframes interleaved RGB images of g.rows x g.cols pixels, frame f at rgb +
+// f * frame_stride (MIS when one of rgb, pitch and the stride is no multiple of 16). g is ONE frame's geometry,
+// g.nplanes = 3 np; output plane (f * 3 + c) * np + k is plane plane0 + k of channel c of frame f. One wave per
+// (frame, row block, strip, channel), the channel fastest: the three channels of a strip stay neighbouring waves
+// and share their 192 bytes per lane through L1 / L2; then the strip, the row block, the frame. The wave's index
+// / (3 x a frame's row blocks x strips) is its frame, so r0 = 0 is every frame's own first row (no row above,
+// R(0,0) = 0) and a channel's green (CT) is its own frame's. All offsets 64-bit.
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false, int CT = 0>
+__global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_rgb_frames(
+    const uint8_t* __restrict__ rgb, size_t pitch, uint64_t frame_stride, uint32_t nframes, Geom g, uint32_t ns,
+    uint32_t plane0, uint64_t* __restrict__ planes, uint32_t* __restrict__ sones, int4* __restrict__ krec,
+    uint32_t* __restrict__ kpos, uint32_t* __restrict__ zero, uint64_t* __restrict__ out_e, uint64_t eg_stride) {
+  __shared__ __attribute__((aligned(16))) uint32_t tab[kWaves][1024];  // strip_word_put tables
+  if (blockIdx.x == 0 && threadIdx.x < kZeroWords) zero[threadIdx.x] = 0;  // the encoder's counters
+  const uint32_t wv = wave_id();
+  uint32_t* tw = tab[wv];
+  constexpr uint32_t RPW = gray_rows_per_wave<PREDICT, STORE_R>();
+  const uint32_t wpf = ((g.rows + RPW - 1) / RPW) * ns;  // waves per frame and channel (< 2^31: rows * (cols + 1) < 2^31)
+  const uint64_t gw = (uint64_t)xcd_remap(blockIdx.x, gridDim.x) * kWaves + wv;
+  const uint32_t ch = (uint32_t)(gw % 3u);  // the wave's channel
+  const uint64_t gs = gw / 3u;
+  const uint64_t f = gs / wpf;  // the wave's frame
+  if (f >= nframes) return;     // whole wave
+  const uint32_t fw = (uint32_t)(gs % wpf);
+  const uint32_t s = fw % ns;  // the strips of one row block are neighbouring waves
+  const uint32_t r0 = (fw / ns) * RPW;  // (< g.rows: fw < wpf)
+  const uint8_t* fr = rgb + f * frame_stride;
+  Geom gg = g;
+  gg.nplanes = g.nplanes / 3u;
+  const uint64_t skip = (f * 3u + ch) * gg.nplanes;  // output planes before the frame's channel's
+  const uint64_t rskip = skip * g.rows * ns;
+  uint64_t* pl = planes + skip * g.plane_words;
+  uint64_t* oe = out_e + skip * eg_stride;
+  if ((s + 1) * 64 <= g.used && g.trail == ~0ull && gg.nplanes == 8)
+    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 3, GC, CT>(fr, pitch, gg, ns, s, r0, plane0, pl,
+                                                                       sones + rskip, krec + rskip, kpos + rskip, tw,
+                                                                       oe, eg_stride, ch);
+  else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
+    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 3, GC, CT>(fr, pitch, gg, ns, s, r0, plane0, pl,
+                                                                        sones + rskip, krec + rskip, kpos + rskip, tw,
+                                                                        oe, eg_stride, ch);
+  else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
+    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 3, GC, CT>(fr, pitch, gg, ns, s, r0, plane0, pl,
+                                                                           sones + rskip, krec + rskip, kpos + rskip, tw,
+                                                                           nullptr, 0, ch);
+}
+
 bool gray_eg_supported(const Geom& g) { return g.trail == ~0ull && g.used % 64 == 0 && g.used / 64 <= kMaxStrips; }
 
 // any gray alignment and pitch (rows not 16-byte aligned: load64_mis); every row must hold used * 64
@@ -1358,6 +1406,54 @@ void launch_gray_frames(hipStream_t s, const uint8_t* gray, size_t pitch, uint64
 #undef BIC_GF
 #undef BIC_GFG
 #undef BIC_GFS
+}
+
+// the RGB frame count pass's grid (workgroups); 0: it would not fit 31 bits
+static uint32_t rgb_frames_grid(const Geom& g, uint64_t nframes, int predict, bool store_resid) {
+  const uint32_t rpw = predict && store_resid ? gray_rows_per_wave<true, true>() : gray_rows_per_wave<true, false>();
+  const uint64_t wpf = (uint64_t)((g.rows + rpw - 1) / rpw) * gray_strips(g);
+  const uint64_t grid = (nframes * wpf * 3 + kWaves - 1) / kWaves;  // (nframes < 2^16, wpf < 2^31)
+  return grid < (1ull << 31) ? (uint32_t)grid : 0u;
+}
+bool rgb_frames_supported(const Geom& g, uint64_t nframes, int predict, bool store_resid) {
+  return rgb_frames_grid(g, nframes, predict, store_resid) != 0;
+}
+
+// g: the call's geometry, g.nplanes = nframes x 3 x one channel's planes
+void launch_rgb_frames(hipStream_t s, const uint8_t* rgb, size_t pitch, uint64_t frame_stride, uint32_t nframes,
+                       const Geom& g, int predict, int plane0, uint64_t* planes, uint32_t* sones, int4* krec,
+                       uint32_t* kpos, uint32_t* zero, bool store_resid, uint64_t* out_e, uint64_t eg_stride,
+                       bool gray_code, int color_transform) {
+  const uint32_t ns = gray_strips(g);
+  Geom gf = g;  // one frame's: its three channels' planes
+  gf.nplanes = g.nplanes / nframes;
+  const uint32_t grid = rgb_frames_grid(g, nframes, predict, store_resid);
+  // every frame's rows 16-byte aligned, or the misaligned-load form (e.g. P6 files one after the other)
+  const bool mis = pitch % 16 != 0 || reinterpret_cast<uintptr_t>(rgb) % 16 != 0 || (nframes > 1 && frame_stride % 16 != 0);
+  const bool egs = out_e && predict && store_resid && gray_eg_supported(g);
+#define BIC_RFC(P, R, E, M, G, C)                                                                                    \
+  k_gray_strips_rgb_frames<P, R, E, M, G, C><<<grid, kBlock, 0, s>>>(rgb, pitch, frame_stride, nframes, gf, ns,      \
+                                                                     (uint32_t)plane0, planes, sones, krec, kpos,    \
+                                                                     zero, out_e, eg_stride)
+#define BIC_RFG(P, R, E, M, G)                                  \
+  do {                                                          \
+    if (color_transform == 1) BIC_RFC(P, R, E, M, G, 1);        \
+    else if (color_transform == 2) BIC_RFC(P, R, E, M, G, 2);   \
+    else BIC_RFC(P, R, E, M, G, 0);                             \
+  } while (0)
+#define BIC_RF(P, R, E, M)                             \
+  do {                                                 \
+    if (gray_code) BIC_RFG(P, R, E, M, true);          \
+    else BIC_RFG(P, R, E, M, false);                   \
+  } while (0)
+#define BIC_RF2(P, R) { if (mis) BIC_RF(P, R, false, true); else BIC_RF(P, R, false, false); }
+  if (egs) { if (mis) BIC_RF(true, true, true, true); else BIC_RF(true, true, true, false); }
+  else if (predict) { if (store_resid) BIC_RF2(true, true) else BIC_RF2(true, false) }
+  else BIC_RF2(false, false)  // without prediction R = P
+#undef BIC_RF2
+#undef BIC_RF
+#undef BIC_RFG
+#undef BIC_RFC
 }
 
 void launch_med_rows(hipStream_t s, const Geom& g, const uint64_t* planes, int predict, uint64_t* resid,

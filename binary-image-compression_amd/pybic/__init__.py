@@ -34,6 +34,7 @@ EXPORTS = [
     "bic_encode_pbm", "bic_encode_pbm_packed", "bic_decode_pbm",
     "bic_encode_gray_frames", "bic_encode_gray_frames_packed", "bic_decode_gray_frames",
     "bic_encode_rgb", "bic_encode_rgb_packed", "bic_bitplanes_rgb", "bic_planes_to_rgb", "bic_decode_rgb",
+    "bic_encode_rgb_frames", "bic_encode_rgb_frames_packed", "bic_decode_rgb_frames",
     "bic_rgb_p00", "bic_gray_p00",
     "bic_bsvd_update_coefficients", "bic_bsvd_update_dictionary", "bic_bsvd_learn",
     "bic_dict_encode", "bic_set_dict_block",
@@ -204,6 +205,10 @@ def load(path=LIB_PATH):
                                         sz])
     sig("bic_encode_rgb", i32, [vp, vp, sz, sz, sz, i32, i32, vp, sz, i32, vp, sz, vp, vp, sz, vp])
     sig("bic_encode_rgb_packed", i32, [vp, vp, sz, sz, sz, i32, i32, vp, sz, i32, vp, sz, vp, vp, vp, sz, vp, vp, vp])
+    sig("bic_encode_rgb_frames", i32, [vp, vp, sz, i32, sz, sz, sz, i32, i32, vp, sz, i32, vp, sz, vp, vp, sz, vp])
+    sig("bic_encode_rgb_frames_packed", i32, [vp, vp, sz, i32, sz, sz, sz, i32, i32, vp, sz, i32, vp, sz, vp, vp, vp, sz,
+                                              vp, vp, vp])
+    sig("bic_decode_rgb_frames", i32, [vp, i32, vp, sz, vp, vp, vp, i32, i32, i32, sz, sz, i32, vp, vp, sz, sz])
     sig("bic_bitplanes_rgb", i32, [vp, vp, sz, sz, sz, i32, i32, vp, sz])
     sig("bic_planes_to_rgb", i32, [vp, vp, i32, i32, sz, sz, sz, vp, sz])
     sig("bic_decode_rgb", i32, [vp, i32, vp, sz, vp, vp, vp, i32, i32, sz, sz, i32, vp, vp, sz])
@@ -810,6 +815,67 @@ class Context:
                   "bic_decode_gray_frames")
         return out
 
+    def encode_rgb_frames(self, rgb, rows, cols, nframes=1, frame_stride=None, pitch=None, nplanes=8, plane0=0,
+                          predict=True, planes=None, golomb=True, eg=True, slots=(None, None), outs=(None, None),
+                          bits=(None, None), wpr=None):
+        """bic_encode_rgb_frames: rgb = a uint8 device tensor whose first byte is frame 0's first sample (any
+        alignment, e.g. concatenated P6 files' bytes [data_offset:]), frame f frame_stride bytes further (default
+        rows * pitch, pitch default 3 * cols) -> (planes, (out_g, bits_g) or None, (out_e, bits_e) or None); entry
+        (f * 3 + c) * nplanes + k of each is plane plane0 + k of channel c of frame f. planes: see _frames_args,
+        with 3 * nplanes planes per frame (None: not returned)."""
+        pitch, stride, planes, wpr = self._frames_args(rows, cols, nframes, 3 * nplanes, 3, pitch, frame_stride, planes,
+                                                       wpr)
+        n = nframes * 3 * nplanes
+        res = []
+        for on, coder, slot, out, b in ((golomb, CODER_GOLOMB, slots[0], outs[0], bits[0]),
+                                        (eg, CODER_EG, slots[1], outs[1], bits[1])):
+            if not on:
+                res.append((None, 0, None))
+                continue
+            slot = slot or self.slot_words(rows, cols, coder)
+            out = self.empty_i64(n, slot) if out is None else out
+            b = self.empty_i64(n) if b is None else b
+            res.append((out, slot, b))
+        (og, sg, bg), (oe, se, be) = res
+        self._bind_stream()
+        self._chk(self.lib.bic_encode_rgb_frames(self.h, _p(rgb), stride, nframes, pitch, rows, cols, plane0, nplanes,
+                                                 _p(planes), wpr, int(predict), _p(og), sg, _p(bg), _p(oe), se, _p(be)),
+                  "bic_encode_rgb_frames")
+        return planes, ((og, bg) if golomb else None), ((oe, be) if eg else None)
+
+    def encode_rgb_frames_packed(self, rgb, rows, cols, nframes=1, frame_stride=None, pitch=None, nplanes=8, plane0=0,
+                                 predict=True, planes=None, golomb=True, eg=True, slots=(None, None),
+                                 outs=(None, None), bits=(None, None), offs=(None, None), row_index=None, wpr=None):
+        """bic_encode_rgb_frames_packed -> (planes, (out_g, bits_g, off_g) or None, (out_e, bits_e, off_e) or
+        None); the offsets run through all nframes * 3 * nplanes streams"""
+        pitch, stride, planes, wpr = self._frames_args(rows, cols, nframes, 3 * nplanes, 3, pitch, frame_stride, planes,
+                                                       wpr)
+        (og, sg, bg, fg), (oe, se, be, fe) = self._packed_bufs(nframes * 3 * nplanes, rows, cols, golomb, eg, slots,
+                                                               outs, bits, offs)
+        self._bind_stream()
+        self._chk(self.lib.bic_encode_rgb_frames_packed(self.h, _p(rgb), stride, nframes, pitch, rows, cols, plane0,
+                                                        nplanes, _p(planes), wpr, int(predict), _p(og), sg, _p(bg),
+                                                        _p(fg), _p(oe), se, _p(be), _p(fe), _p(row_index)),
+                  "bic_encode_rgb_frames_packed")
+        return planes, ((og, bg, fg) if golomb else None), ((oe, be, fe) if eg else None)
+
+    def decode_rgb_frames(self, coder, streams, plane_bits, nframes, nplanes, rows, cols, predict=True, word_off=None,
+                          row_index=None, p00=None, plane0=0, out=None, pitch=None, frame_stride=None):
+        """bic_decode_rgb_frames: the nframes * 3 * nplanes streams of encode_rgb_frames (as for decode_planes) ->
+        uint8 device tensor of interleaved samples, frame f at byte f * frame_stride (default rows * pitch), rows
+        `pitch` apart (default 3 * cols). out: a uint8 device tensor whose first byte is frame 0's first (any
+        alignment). p00: uint8 device tensor [nframes * 3 * nplanes] (rgb_frames_p00) or None."""
+        pitch = pitch or 3 * cols
+        stride = rows * pitch if frame_stride is None else frame_stride
+        if out is None:
+            out = self.torch.zeros((nframes - 1) * stride + rows * pitch, dtype=self.torch.uint8, device=self.dev)
+        slot = streams.shape[-1] if (word_off is None and streams.dim() == 2) else 0
+        self._bind_stream()
+        self._chk(self.lib.bic_decode_rgb_frames(self.h, coder, _p(streams), slot, _p(word_off), _p(plane_bits),
+                                                 _p(row_index), nframes, plane0, nplanes, rows, cols, int(predict),
+                                                 _p(p00), _p(out), pitch, stride), "bic_decode_rgb_frames")
+        return out
+
     def _packed_bufs(self, n, rows, cols, golomb, eg, slots, outs, bits, offs):
         res = []
         for i, (on, coder) in enumerate(((golomb, CODER_GOLOMB), (eg, CODER_EG))):
@@ -1318,6 +1384,13 @@ def rgb_p00(color_transform, gray_code, pixel, plane0=0, nplanes=8):
     if rc != BIC_OK:
         raise BicError(rc, "bic_rgb_p00")
     return out
+
+
+def rgb_frames_p00(color_transform, gray_code, first_pixels, plane0=0, nplanes=8):
+    """the p00 bytes decode_rgb_frames needs: rgb_p00 of each frame's first pixel (first_pixels: one (R, G, B) per
+    frame), one after the other -> uint8 numpy array [nframes * 3 * nplanes] (host only)"""
+    parts = [rgb_p00(color_transform, gray_code, px, plane0, nplanes) for px in first_pixels]
+    return np.concatenate(parts) if parts else np.zeros(0, np.uint8)
 
 
 def gray_p00(sample_predict, gray_code, sample, plane0=0, nplanes=8):

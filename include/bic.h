@@ -359,6 +359,35 @@ int bic_encode_gray_frames_packed(bic_ctx* ctx, const void* gray, size_t frame_s
                                   uint64_t* planes, size_t wpr, int predict, uint64_t* out_golomb, size_t slot_golomb,
                                   uint64_t* bits_golomb, uint64_t* off_golomb, uint64_t* out_eg, size_t slot_eg,
                                   uint64_t* bits_eg, uint64_t* off_eg, uint64_t* row_index);
+/* A batch of RGB frames -> streams in one call: nframes interleaved RGB images of one geometry (video frames,
+ * tiles of a colour scan), each coded as bic_encode_rgb / bic_encode_rgb_packed codes it alone -- fresh coders
+ * per plane, no row above a frame's row 0, R(0,0) = 0 in every frame -- bit for bit. Frame f is rows rows of cols
+ * pixels of three one-byte samples R, G, B at rgb + f * frame_stride, row pitch `pitch` bytes (>= 3 * cols);
+ * rgb, pitch and frame_stride of any byte alignment (a buffer of concatenated P6 files + data_offset works as it
+ * lies); frame_stride >= rows * pitch (ignored when nframes = 1). plane0, nplanes: the range within each channel
+ * (plane0 + nplanes <= 8). There are nframes * 3 * nplanes outputs: plane, slot, bit count, offset and row-index
+ * entry (f * 3 + c) * nplanes + k belongs to plane plane0 + k of channel c of frame f, so frame f's block of
+ * 3 * nplanes entries is what bic_encode_rgb* returns for that frame; off_* have nframes * 3 * nplanes + 1 entries
+ * and run through all streams as bic_pack_streams would lay them out; planes, when given, holds nframes * 3 *
+ * nplanes * rows * wpr words. BIC_OPT_GRAY_CODE and BIC_OPT_COLOR_TRANSFORM as in the single-image RGB calls
+ * (a pixel's green is its own frame's); BIC_OPT_SAMPLE_PREDICT is ignored, as in every RGB call. Nullable planes
+ * and coders, BIC_ENOSPC, the domain rows * (cols + 1) < 2^31 per plane, the 15-byte read round-out, rows = 0 and
+ * the argument errors as for bic_encode_gray_frames_packed. BIC_EINVAL also for nframes < 1, nframes * 3 *
+ * nplanes > 65535 and a frame_stride below rows * pitch. nframes = 1 is the single-image call itself.
+ * The staged encoder (>= 32768 rows in all planes, or BIC_OPT_STAGED), an even wpr, cols <= 16384 and rows that
+ * hold ceil(cols/64)*192 readable bytes: one count kernel reads every frame once (with planes NULL, predict and
+ * the EG stream into slots it writes the EG streams itself); otherwise the same result through bic_bitplanes_rgb
+ * per frame and one bic_encode_planes2 / bic_encode_planes_packed. The device round trip is RGB frames ->
+ * bic_encode_rgb_frames_packed -> bic_decode_rgb_frames. */
+int bic_encode_rgb_frames(bic_ctx* ctx, const uint8_t* rgb, size_t frame_stride, int nframes, size_t pitch,
+                          size_t rows, size_t cols, int plane0, int nplanes, uint64_t* planes, size_t wpr,
+                          int predict, uint64_t* out_golomb, size_t slot_golomb, uint64_t* bits_golomb,
+                          uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg);
+int bic_encode_rgb_frames_packed(bic_ctx* ctx, const uint8_t* rgb, size_t frame_stride, int nframes, size_t pitch,
+                                 size_t rows, size_t cols, int plane0, int nplanes, uint64_t* planes, size_t wpr,
+                                 int predict, uint64_t* out_golomb, size_t slot_golomb, uint64_t* bits_golomb,
+                                 uint64_t* off_golomb, uint64_t* out_eg, size_t slot_eg, uint64_t* bits_eg,
+                                 uint64_t* off_eg, uint64_t* row_index);
 
 /* ---- f1: decoders on the device (GolombDecoder.cpp:15-23 read order, eg.cpp:20-37 as written) --
  * row_index (device, nplanes * rows * 2 u64; nullable in the encoders above): per row of each plane,
@@ -426,6 +455,18 @@ int bic_decode_gray_frames(bic_ctx* ctx, int coder, const uint64_t* streams, siz
 int bic_decode_rgb(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words, const uint64_t* word_off,
                    const uint64_t* plane_bits, const uint64_t* row_index, int plane0, int nplanes, size_t rows,
                    size_t cols, int predict, const uint8_t* p00, uint8_t* rgb, size_t pitch);
+/* bic_decode_rgb for every frame of a batch in one call: the nframes * 3 * nplanes streams in
+ * bic_encode_rgb_frames' order (stream (f * 3 + c) * nplanes + k sets bit plane0 + k of channel c of frame f;
+ * p00 one byte per stream, frame f's 3 * nplanes bytes being bic_rgb_p00 of its first pixel), frame f written at
+ * rgb + f * frame_stride (>= rows * pitch, ignored when nframes = 1; any byte alignment). Only the first 3 * cols
+ * bytes of each row of each frame are written: pitch padding and the gap between frames keep the caller's bytes.
+ * Coders (BIC_CODER_EG_ADAPTIVE with bic_egad_row_index's index included), row_index, BIC_EDATA from bic_sync,
+ * cols <= 16384 and rows = 0 as for bic_decode_rgb; BIC_EINVAL also for nframes < 1 and nframes * 3 * nplanes >
+ * 65535. */
+int bic_decode_rgb_frames(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot_words,
+                          const uint64_t* word_off, const uint64_t* plane_bits, const uint64_t* row_index,
+                          int nframes, int plane0, int nplanes, size_t rows, size_t cols, int predict,
+                          const uint8_t* p00, uint8_t* rgb, size_t pitch, size_t frame_stride);
 /* streams -> P4 rasters in one call: bic_decode_planes followed by bic_pbm_pack per frame, without the
  * planes. coder, streams, slot_words, word_off, plane_bits, row_index, predict, the limit cols <= 16384
  * and BIC_EDATA from bic_sync (the rasters are then undefined) as for bic_decode_gray; stream f is frame
