@@ -244,6 +244,10 @@ int bic_ctx_set_option(bic_ctx* ctx, int option, long value) {
       if (value < BIC_SP_NONE || value > BIC_SP_LEFT_FOLDED) return BIC_EINVAL;  // (likewise)
       ctx->sample_predict = (int)value;
       return BIC_OK;
+    case BIC_OPT_RGB_PREDICT:
+      if (value < BIC_SP_NONE || value > BIC_SP_LEFT_FOLDED) return BIC_EINVAL;  // (likewise)
+      ctx->rgb_predict = (int)value;
+      return BIC_OK;
     default: return BIC_EINVAL;
   }
 }
@@ -255,8 +259,14 @@ size_t bic_encode_slot_words(size_t rows, size_t cols, int coder) {
 }
 
 int bic_rgb_p00(int color_transform, int gray_code, const uint8_t pixel[3], int plane0, int nplanes, uint8_t* p00) {
-  if (color_transform < BIC_CT_NONE || color_transform > BIC_CT_SUBTRACT_GREEN_FOLDED || (gray_code != 0 && gray_code != 1) ||
-      !pixel || !p00 || plane0 < 0 || nplanes < 1 || plane0 + nplanes > 8)
+  return bic_rgb_p00_predict(color_transform, BIC_SP_NONE, gray_code, pixel, plane0, nplanes, p00);
+}
+
+int bic_rgb_p00_predict(int color_transform, int rgb_predict, int gray_code, const uint8_t pixel[3], int plane0,
+                        int nplanes, uint8_t* p00) {
+  if (color_transform < BIC_CT_NONE || color_transform > BIC_CT_SUBTRACT_GREEN_FOLDED || rgb_predict < BIC_SP_NONE ||
+      rgb_predict > BIC_SP_LEFT_FOLDED || (gray_code != 0 && gray_code != 1) || !pixel || !p00 || plane0 < 0 ||
+      nplanes < 1 || plane0 + nplanes > 8)
     return BIC_EINVAL;
   for (int c = 0; c < 3; ++c) {
     uint32_t v = pixel[c];
@@ -264,6 +274,8 @@ int bic_rgb_p00(int color_transform, int gray_code, const uint8_t pixel[3], int 
       v = (v - pixel[1]) & 0xffu;
       if (color_transform == BIC_CT_SUBTRACT_GREEN_FOLDED) v = ((v << 1) ^ (v & 0x80u ? 0xffu : 0u)) & 0xffu;
     }
+    // (no left neighbour: the transformed sample is its own difference)
+    if (rgb_predict == BIC_SP_LEFT_FOLDED) v = ((v << 1) ^ (v & 0x80u ? 0xffu : 0u)) & 0xffu;
     if (gray_code) v ^= v >> 1;
     for (int k = 0; k < nplanes; ++k) p00[c * nplanes + k] = (uint8_t)((v >> (plane0 + k)) & 1u);
   }

@@ -41,6 +41,11 @@ int run_decode(bic_ctx* ctx, const char* name, bic::DecodeCall& c) {
       bic::launch_sample_unpredict(ctx->cur, c.gray.sample_predict, c.gray.gray, c.gray.pitch, c.gray.frame_stride,
                                    c.gray.nframes, c.rows, c.cols);
     });
+  if (c.sink == bic::DecodeCall::kRgb && c.rgb.rgb_predict)  // the z bytes just stored -> the pixels, in place
+    timed(ctx, "rgb_unpredict", [&] {
+      bic::launch_rgb_unpredict(ctx->cur, c.rgb.rgb_predict, c.rgb.ct_inverse, c.rgb.rgb, c.rgb.pitch, c.rgb.frame_stride,
+                                c.rgb.nframes, c.rows, c.cols);
+    });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
 }
@@ -115,7 +120,10 @@ int bic_decode_rgb(bic_ctx* ctx, int coder, const uint64_t* streams, size_t slot
                         (cols + 63) / 64, predict, p00, rgb)) || !c.rows)
     return rc;
   c.sink = bic::DecodeCall::kRgb;
-  c.rgb = {rgb, (uint64_t)pitch, plane0, ctx->gray_code ? 1 : 0, ctx->color_transform};
+  // (BIC_OPT_RGB_PREDICT: the sink stores the z bytes, the inverse colour transform follows the scan)
+  c.rgb = {rgb, (uint64_t)pitch, plane0, ctx->gray_code ? 1 : 0, ctx->rgb_predict ? 0 : ctx->color_transform};
+  c.rgb.rgb_predict = ctx->rgb_predict;
+  c.rgb.ct_inverse = ctx->color_transform;
   return run_decode(ctx, "decode_rgb", c);
 }
 
@@ -134,8 +142,10 @@ int bic_decode_rgb_frames(bic_ctx* ctx, int coder, const uint64_t* streams, size
                         (cols + 63) / 64, predict, p00, rgb)) || !c.rows)
     return rc;
   c.sink = bic::DecodeCall::kRgb;
-  c.rgb = {rgb, (uint64_t)pitch, plane0, ctx->gray_code ? 1 : 0, ctx->color_transform, (uint32_t)nframes,
-           nframes > 1 ? (uint64_t)frame_stride : 0};
+  c.rgb = {rgb, (uint64_t)pitch, plane0, ctx->gray_code ? 1 : 0, ctx->rgb_predict ? 0 : ctx->color_transform,
+           (uint32_t)nframes, nframes > 1 ? (uint64_t)frame_stride : 0};
+  c.rgb.rgb_predict = ctx->rgb_predict;
+  c.rgb.ct_inverse = ctx->color_transform;
   return run_decode(ctx, "decode_rgb_frames", c);
 }
 

@@ -108,7 +108,7 @@ int bic_bitplanes_rgb(bic_ctx* ctx, const uint8_t* rgb, size_t pitch, size_t row
   if (rows == 0) return BIC_OK;
   timed(ctx, "bitplanes_rgb", [&] {
     bic::launch_raster_planes(ctx->cur, rgb, 3, (uint32_t)rows, (uint32_t)cols, plane0, nplanes, planes, (uint32_t)wpr,
-                              (uint64_t)pitch, 0, ctx->gray_code, ctx->color_transform);
+                              (uint64_t)pitch, 0, ctx->gray_code, ctx->color_transform, ctx->rgb_predict);
   });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
@@ -124,8 +124,13 @@ int bic_planes_to_rgb(bic_ctx* ctx, const uint64_t* planes, int plane0, int npla
   if (rows == 0) return BIC_OK;
   timed(ctx, "planes_to_rgb", [&] {
     bic::launch_planes_gray(ctx->cur, planes, (uint32_t)rows, (uint32_t)cols, (uint32_t)wpr, plane0, nplanes, 3, rgb,
-                            (uint64_t)pitch, ctx->gray_code, ctx->color_transform);
+                            (uint64_t)pitch, ctx->gray_code, ctx->rgb_predict ? 0 : ctx->color_transform);
   });
+  if (ctx->rgb_predict)  // the z bytes just stored -> the pixels, in place (the inverse colour transform behind the scan)
+    timed(ctx, "rgb_unpredict", [&] {
+      bic::launch_rgb_unpredict(ctx->cur, ctx->rgb_predict, ctx->color_transform, rgb, (uint64_t)pitch, 0, 1,
+                                (uint32_t)rows, (uint32_t)cols);
+    });
   BIC_HIP(hipGetLastError());
   return BIC_OK;
 }

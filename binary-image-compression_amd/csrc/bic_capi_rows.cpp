@@ -230,7 +230,7 @@ int encode_gray_impl(bic_ctx* ctx, const GrayImage& img, int plane0, uint64_t* p
          bic::launch_gray_rows(ctx->cur, img.data, img.pitch, g, predict ? 1 : 0, plane0, planes, ar.sones, ar.krec,
                                ar.kpos, ar.counter, store_resid, eg_src ? oe.out : nullptr, oe.slot, bps,
                                img.big_endian, ctx->gray_code, bps == 3 ? ctx->color_transform : 0,
-                               bps == 1 ? ctx->sample_predict : 0);
+                               bps == 1 ? ctx->sample_predict : bps == 3 ? ctx->rgb_predict : 0);
        })))
     return rc;
   if (row_index && !og.out) return bic_row_index(ctx, planes, nplanes, rows, cols, wpr, pr, row_index);
@@ -298,7 +298,8 @@ int encode_gray_frames_impl(bic_ctx* ctx, const GrayImage& img, size_t stride, i
              if (bps == 3)
                bic::launch_rgb_frames(ctx->cur, img.data, img.pitch, stride, (uint32_t)nframes, g, predict ? 1 : 0,
                                       plane0, planes, ar.sones, ar.krec, ar.kpos, ar.counter, store_resid,
-                                      eg_src ? oe.out : nullptr, oe.slot, ctx->gray_code, ctx->color_transform);
+                                      eg_src ? oe.out : nullptr, oe.slot, ctx->gray_code, ctx->color_transform,
+                                      ctx->rgb_predict);
              else
                bic::launch_gray_frames(ctx->cur, img.data, img.pitch, stride, (uint32_t)nframes, g, predict ? 1 : 0,
                                        plane0, planes, ar.sones, ar.krec, ar.kpos, ar.counter, store_resid,

@@ -104,6 +104,7 @@ struct bic_ctx {
   bool gray_code = false;      // BIC_OPT_GRAY_CODE: samples <-> planes go through G(v) = v ^ (v >> 1)
   int color_transform = 0;     // BIC_OPT_COLOR_TRANSFORM: the RGB calls' per-pixel transform in front of G
   int sample_predict = 0;      // BIC_OPT_SAMPLE_PREDICT: one-byte gray samples minus their left neighbour, in front of G
+  int rgb_predict = 0;         // BIC_OPT_RGB_PREDICT: the same on each channel of the RGB calls, behind the colour transform
   struct Rec { std::string name; hipEvent_t a, b; };
   std::vector<Rec> recs;
   std::vector<hipEvent_t> pool;

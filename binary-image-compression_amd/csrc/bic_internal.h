@@ -91,6 +91,11 @@ struct RgbOut {
   // bic_decode_rgb_frames: the call's planes are nframes groups of 3 np, group f those of the image at rgb + f * frame_stride
   uint32_t nframes = 1;
   uint64_t frame_stride = 0;
+  // BIC_OPT_RGB_PREDICT: the planes are T_sp(T_ct(row))'s per channel; the sink then runs with color_transform 0 and
+  // stores the z bytes, and the entry point turns them into the pixels in place with launch_rgb_unpredict (the
+  // scan and ct_inverse, the transform kept here), a pass of its own after the decode
+  int rgb_predict = 0;
+  int ct_inverse = 0;
 };
 // bic_decode_pbm: the P4 rasters the decoded planes go to (plane f = frame f at raster + f * stride)
 struct PbmOut {
@@ -290,7 +295,7 @@ uint32_t gray_strips(const Geom& g);
 // (pnm.cpp:71-74) or the host's order, planes plane0 .. of 16 (k_gray_strips16). bps = 3 (bic_encode_rgb):
 // interleaved RGB pixels of one-byte samples; g.nplanes = 3 np, output plane c * np + k is plane plane0 + k
 // of channel c (k_gray_strips_rgb; color_transform: BIC_OPT_COLOR_TRANSFORM, bps = 3 only).
-// sample_predict: BIC_OPT_SAMPLE_PREDICT (bps = 1 only)
+// sample_predict: BIC_OPT_SAMPLE_PREDICT (bps = 1), BIC_OPT_RGB_PREDICT (bps = 3: per channel, behind color_transform)
 void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Geom& g, int predict, int plane0,
                       uint64_t* planes, uint32_t* sones, int4* krec, uint32_t* kpos, uint32_t* zero,
                       bool store_resid = false, uint64_t* out_e = nullptr, uint64_t eg_stride = 0, int bps = 1,
@@ -312,7 +317,7 @@ bool rgb_frames_supported(const Geom& g, uint64_t nframes, int predict, bool sto
 void launch_rgb_frames(hipStream_t s, const uint8_t* rgb, size_t pitch, uint64_t frame_stride, uint32_t nframes,
                        const Geom& g, int predict, int plane0, uint64_t* planes, uint32_t* sones, int4* krec,
                        uint32_t* kpos, uint32_t* zero, bool store_resid, uint64_t* out_e, uint64_t eg_stride,
-                       bool gray_code, int color_transform);
+                       bool gray_code, int color_transform, int rgb_predict = 0);
 
 void launch_patch_search(hipStream_t s, const uint64_t* plane, uint32_t rows, uint32_t cols, uint32_t wpr,
                          uint32_t W, uint32_t* besti, uint32_t* bestj, uint32_t* bestd);
@@ -369,6 +374,11 @@ void launch_planes_gray(hipStream_t s, const uint64_t* planes, uint32_t rows, ui
 // `cols` bytes are touched.
 void launch_sample_unpredict(hipStream_t s, int sample_predict, uint8_t* gray, uint64_t pitch, uint64_t frame_stride,
                              uint32_t nframes, uint32_t rows, uint32_t cols);
+// BIC_OPT_RGB_PREDICT on the way back, in place on the interleaved z bytes launch_planes_gray (bps 3) or the RGB
+// decoder sink stored with color_transform 0 (k_rgb_unpredict: the per-channel scan, then the inverse colour
+// transform; 0: no launch). Only the rows' first 3 * cols bytes are touched.
+void launch_rgb_unpredict(hipStream_t s, int rgb_predict, int color_transform, uint8_t* rgb, uint64_t pitch,
+                          uint64_t frame_stride, uint32_t nframes, uint32_t rows, uint32_t cols);
 
 // GF(2) algebra (bic_gf2.hip). Both launches spread their rows over gridDim.y (at most 65,535): the transpose
 // four 64-row blocks per unit, the product 256 rows per unit, so either takes at most kGf2MaxRows source rows

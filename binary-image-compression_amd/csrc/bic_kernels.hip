@@ -756,7 +756,8 @@ struct Raw16 {
 // of the same twelve uint4 and subtract them byte-wise (ct_forward4) before G. T is not linear over XOR,
 // where the split, med and G are: the pixel before the strip is T of it and its green (src[-2]), and the next
 // segment's D byte is T(cb, its green) ^ T(ub, its green), not T of cb ^ ub. The green wave runs as with CT 0.
-// SP (BIC_OPT_SAMPLE_PREDICT, S16 = 0 only): every sample becomes its difference from the sample on its left
+// SP (BIC_OPT_SAMPLE_PREDICT, S16 = 0; BIC_OPT_RGB_PREDICT, S16 = 3: per channel, after CT -- pick leaves G to the
+// step behind the difference, the left neighbours lie three bytes back and take their own green): every sample becomes its difference from the sample on its left
 // (1: mod 256, 2: folded) before G. In the lane's 64 bytes the left neighbour is the byte before (sp_forward4 down
 // the 16 dwords); the left of byte 0 is lane - 1's byte 63 (a one-lane DPP shift), for lane 0 the raw pixel before
 // the strip, 0 at column 0. Like CT it is not linear over XOR: the pixel before the strip becomes T of it (its own
@@ -805,7 +806,7 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
         uint32_t x = rgb_pick4(d0, d1, d2, s1, s2);
         if constexpr (CT != 0)
           if (bo != 1) x = ct_forward4<CT>(x, rgb_pick4(d0, d1, d2, rgb_sel1(1), rgb_sel2(1)));  // (wave-uniform)
-        if constexpr (GC) x ^= (x >> 1) & 0x7f7f7f7fu;
+        if constexpr (GC && SP == 0) x ^= (x >> 1) & 0x7f7f7f7fu;  // (SP: G comes after the difference, below)
         return x;
       };
 #pragma unroll
@@ -859,13 +860,33 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = in ? reinterpret_cast<const uint4*>(src)[q] : make_uint4(0, 0, 0, 0);
     }
-    if constexpr (S16 == 3) lb = (lane == 0 && s > 0) ? (uint32_t)src[(int)bo - 3] : 0u;  // the pixel before the strip
+    // (RGB prediction on 16-byte aligned rows: the two pixels before the strip -- the strip's left neighbour and that
+    // one's own -- come as one wave-uniform 8-byte load, bytes -8 .. -1 of the strip, and stay scalar: every use of
+    // lb is lane 0's. Byte loads per lane as below cost the forms at a VGPR step one wave of occupancy)
+    constexpr bool ULB = S16 == 3 && SP != 0 && !MIS;
+    uint32_t ll = 0;  // (S16 3 with SP) the pixel two before the strip, after CT
+    if constexpr (ULB) {
+      lb = 0;
+      if (s > 0) {
+        const uint8_t* us = gray + (uint64_t)row * pitch + (uint64_t)s * 12288u;  // lane 0's src
+        const uint2 pb = *reinterpret_cast<const uint2*>(us - 8);
+        const uint64_t t = ((uint64_t)pb.y << 32) | pb.x;
+        auto before = [&](uint32_t k) { return (uint32_t)(t >> (8 * (8 - k))) & 0xffu; };  // the byte k before the strip
+        lb = before(3 - bo);
+        ll = before(6 - bo);
+        if constexpr (CT != 0)
+          if (bo != 1) {
+            lb = ct_forward4<CT>(lb, before(2)) & 0xffu;
+            ll = ct_forward4<CT>(ll, before(5)) & 0xffu;
+          }
+      }
+    } else if constexpr (S16 == 3) lb = (lane == 0 && s > 0) ? (uint32_t)src[(int)bo - 3] : 0u;  // the pixel before the strip
     else if constexpr (S16) lb = (lane == 0 && s > 0) ? (uint32_t)src[(int)bo - 2] : 0u;  // the sample before the strip
     else lb = (lane == 0 && s > 0) ? (uint32_t)src[-1] : 0u;
-    if constexpr (S16 == 3 && CT != 0)
+    if constexpr (S16 == 3 && CT != 0 && !ULB)
       if (bo != 1 && lane == 0 && s > 0) lb = ct_forward4<CT>(lb, (uint32_t)src[-2]) & 0xffu;
     if constexpr (SP != 0) {
-      static_assert(S16 == 0 || SP == 0, "sample prediction: one-byte gray samples only");
+      static_assert(S16 == 0 || S16 == 3 || SP == 0, "sample prediction: one-byte samples only");
       uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v[3].w, 0x138, 0xf, 0xf, true);  // lane - 1's last dword
       if (lane == 0) prev = lb << 24;  // the raw pixel before the strip (0 in strip 0)
 #pragma unroll
@@ -875,10 +896,21 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
                           sp_forward4<SP>(x.w, x.z));
         prev = x.w;
       }
-      if (lane == 0 && s > 0) lb = ct_forward4<SP>(lb, (uint32_t)src[-2]) & 0xffu;
+      if constexpr (ULB) {
+        lb = ct_forward4<SP>(lb, ll) & 0xffu;
+      } else if constexpr (S16 == 3) {  // the pixel before the strip minus the one before it: the same channel of it, T_ct'ed
+        if (lane == 0 && s > 0) {
+          ll = (uint32_t)src[(int)bo - 6];
+          if constexpr (CT != 0)
+            if (bo != 1) ll = ct_forward4<CT>(ll, (uint32_t)src[-5]) & 0xffu;
+          lb = ct_forward4<SP>(lb, ll) & 0xffu;
+        }
+      } else {
+        if (lane == 0 && s > 0) lb = ct_forward4<SP>(lb, (uint32_t)src[-2]) & 0xffu;
+      }
     }
     if constexpr (GC) {
-      if constexpr (!S16) gray4(v);
+      if constexpr (!S16 || (S16 == 3 && SP != 0)) gray4(v);
       lb ^= lb >> 1;
       if constexpr (S16 == 1 || S16 == 2)
         if (lo16 && lane == 0 && s > 0) lb ^= ((uint32_t)src[(int)(bo ^ 1u) - 2] & 1u) << 7;
@@ -938,8 +970,24 @@ __device__ __forceinline__ void gray_strip_rows(const uint8_t* __restrict__ gray
         }
       if constexpr (SP != 0) {  // each byte with its own left one (the next row's column 0 has none)
         const bool nl = lastS && lane == 0;
-        cb = ct_forward4<SP>(cb, nl ? 0u : (uint32_t)cp[-1]) & 0xffu;
-        if (rn) ub = ct_forward4<SP>(ub, nl ? 0u : (uint32_t)cp[-1 - (int64_t)pitch]) & 0xffu;
+        if constexpr (S16 == 3) {  // the left pixel's same channel, three bytes back, T_ct'ed with its own green
+          uint32_t cl = 0, ul = 0;
+          if (!nl) {
+            cl = cp[-3];
+            if (rn) ul = cp[-3 - (int64_t)pitch];
+            if constexpr (CT != 0)
+              if (bo != 1) {
+                const int64_t o = -2 - (int64_t)bo;
+                cl = ct_forward4<CT>(cl, cp[o]) & 0xffu;
+                if (rn) ul = ct_forward4<CT>(ul, cp[o - (int64_t)pitch]) & 0xffu;
+              }
+          }
+          cb = ct_forward4<SP>(cb, cl) & 0xffu;
+          if (rn) ub = ct_forward4<SP>(ub, ul) & 0xffu;
+        } else {
+          cb = ct_forward4<SP>(cb, nl ? 0u : (uint32_t)cp[-1]) & 0xffu;
+          if (rn) ub = ct_forward4<SP>(ub, nl ? 0u : (uint32_t)cp[-1 - (int64_t)pitch]) & 0xffu;
+        }
       }
       uint32_t gd0 = cb ^ ub;
       if constexpr (GC) {
@@ -1169,7 +1217,7 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips16(const 
 // same 192 bytes per lane (the second and third from L1 / L2) and keep their own 64; gray_strip_rows then runs on that channel's bytes as on an
 // 8-bit image, its plane-indexed outputs advanced by c * np (RGB in one call).
 // CT (BIC_OPT_COLOR_TRANSFORM): 0, or 1 (subtract green) / 2 (folded), an instantiation each.
-template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false, int CT = 0>
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false, int CT = 0, int SP = 0>
 __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_rgb(const uint8_t* __restrict__ rgb, size_t pitch, Geom g,
                                                             uint32_t ns, uint32_t plane0, uint64_t* __restrict__ planes,
                                                             uint32_t* __restrict__ sones, int4* __restrict__ krec,
@@ -1192,15 +1240,15 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_rgb(cons
   uint64_t* pl = planes + (uint64_t)skip * g.plane_words;
   uint64_t* oe = out_e + (uint64_t)skip * eg_stride;
   if ((s + 1) * 64 <= g.used && g.trail == ~0ull && gg.nplanes == 8)
-    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 3, GC, CT>(rgb, pitch, gg, ns, s, r0, plane0, pl,
+    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 3, GC, CT, SP>(rgb, pitch, gg, ns, s, r0, plane0, pl,
                                                                        sones + rskip, krec + rskip, kpos + rskip, tw,
                                                                        oe, eg_stride, ch);
   else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
-    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 3, GC, CT>(rgb, pitch, gg, ns, s, r0, plane0, pl,
+    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 3, GC, CT, SP>(rgb, pitch, gg, ns, s, r0, plane0, pl,
                                                                         sones + rskip, krec + rskip, kpos + rskip, tw,
                                                                         oe, eg_stride, ch);
   else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
-    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 3, GC, CT>(rgb, pitch, gg, ns, s, r0, plane0, pl,
+    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 3, GC, CT, SP>(rgb, pitch, gg, ns, s, r0, plane0, pl,
                                                                            sones + rskip, krec + rskip, kpos + rskip, tw,
                                                                            nullptr, 0, ch);
 }
@@ -1258,7 +1306,7 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_frames(
 // and share their 192 bytes per lane through L1 / L2; then the strip, the row block, the frame. The wave's index
 // / (3 x a frame's row blocks x strips) is its frame, so r0 = 0 is every frame's own first row (no row above,
 // R(0,0) = 0) and a channel's green (CT) is its own frame's. All offsets 64-bit.
-template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false, int CT = 0>
+template <bool PREDICT, bool STORE_R, bool EGS, bool MIS = false, bool GC = false, int CT = 0, int SP = 0>
 __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_rgb_frames(
     const uint8_t* __restrict__ rgb, size_t pitch, uint64_t frame_stride, uint32_t nframes, Geom g, uint32_t ns,
     uint32_t plane0, uint64_t* __restrict__ planes, uint32_t* __restrict__ sones, int4* __restrict__ krec,
@@ -1285,15 +1333,15 @@ __global__ __launch_bounds__(kBlock, BIC_GRAY_WAVES) void k_gray_strips_rgb_fram
   uint64_t* pl = planes + skip * g.plane_words;
   uint64_t* oe = out_e + skip * eg_stride;
   if ((s + 1) * 64 <= g.used && g.trail == ~0ull && gg.nplanes == 8)
-    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 3, GC, CT>(fr, pitch, gg, ns, s, r0, plane0, pl,
+    gray_strip_rows<PREDICT, true, STORE_R, true, EGS, MIS, 3, GC, CT, SP>(fr, pitch, gg, ns, s, r0, plane0, pl,
                                                                        sones + rskip, krec + rskip, kpos + rskip, tw,
                                                                        oe, eg_stride, ch);
   else if ((s + 1) * 64 <= g.used && g.trail == ~0ull)
-    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 3, GC, CT>(fr, pitch, gg, ns, s, r0, plane0, pl,
+    gray_strip_rows<PREDICT, true, STORE_R, false, EGS, MIS, 3, GC, CT, SP>(fr, pitch, gg, ns, s, r0, plane0, pl,
                                                                         sones + rskip, krec + rskip, kpos + rskip, tw,
                                                                         oe, eg_stride, ch);
   else if constexpr (!EGS)  // (EGS launches have whole strips only: gray_eg_supported)
-    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 3, GC, CT>(fr, pitch, gg, ns, s, r0, plane0, pl,
+    gray_strip_rows<PREDICT, false, STORE_R, false, false, MIS, 3, GC, CT, SP>(fr, pitch, gg, ns, s, r0, plane0, pl,
                                                                            sones + rskip, krec + rskip, kpos + rskip, tw,
                                                                            nullptr, 0, ch);
 }
@@ -1321,9 +1369,21 @@ void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Ge
   const uint32_t ngrp = bps == 3 ? 3u : bps == 2 && !both && plane0 < 8 && plane0 + (int)g.nplanes > 8 ? 2u : 1u;
   const uint32_t grid = (uint32_t)((units * ns * ngrp + kWaves - 1) / kWaves);
   const bool egs = out_e && predict && store_resid && gray_eg_supported(g);
+  // (bps = 3 with sample_predict: BIC_OPT_RGB_PREDICT, an instantiation per (CT, SP))
+#define BIC_GSRS(P, R, E, M, G, C, S)                                                                              \
+  k_gray_strips_rgb<P, R, E, M, G, C, S><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes,      \
+                                                                 sones, krec, kpos, zero, out_e, eg_stride)
+#define BIC_GSR(P, R, E, M, G, S)                              \
+  do {                                                         \
+    if (color_transform == 1) BIC_GSRS(P, R, E, M, G, 1, S);    \
+    else if (color_transform == 2) BIC_GSRS(P, R, E, M, G, 2, S); \
+    else BIC_GSRS(P, R, E, M, G, 0, S);                        \
+  } while (0)
 #define BIC_GSG(P, R, E, M, G)                                                                                     \
   do {                                                                                                             \
-    if (bps == 3 && color_transform == 1)                                                                          \
+    if (bps == 3 && sample_predict == 1) BIC_GSR(P, R, E, M, G, 1);                                                \
+    else if (bps == 3 && sample_predict == 2) BIC_GSR(P, R, E, M, G, 2);                                           \
+    else if (bps == 3 && color_transform == 1)                                                                     \
       k_gray_strips_rgb<P, R, E, M, G, 1><<<grid, kBlock, 0, s>>>(gray, pitch, g, ns, (uint32_t)plane0, planes,     \
                                                                   sones, krec, kpos, zero, out_e, eg_stride);      \
     else if (bps == 3 && color_transform == 2)                                                                     \
@@ -1358,6 +1418,8 @@ void launch_gray_rows(hipStream_t s, const uint8_t* gray, size_t pitch, const Ge
 #undef BIC_GS2
 #undef BIC_GS
 #undef BIC_GSG
+#undef BIC_GSR
+#undef BIC_GSRS
 }
 
 // the frame-aware count pass's grid (workgroups); 0: it would not fit 31 bits
@@ -1423,7 +1485,7 @@ bool rgb_frames_supported(const Geom& g, uint64_t nframes, int predict, bool sto
 void launch_rgb_frames(hipStream_t s, const uint8_t* rgb, size_t pitch, uint64_t frame_stride, uint32_t nframes,
                        const Geom& g, int predict, int plane0, uint64_t* planes, uint32_t* sones, int4* krec,
                        uint32_t* kpos, uint32_t* zero, bool store_resid, uint64_t* out_e, uint64_t eg_stride,
-                       bool gray_code, int color_transform) {
+                       bool gray_code, int color_transform, int rgb_predict) {
   const uint32_t ns = gray_strips(g);
   Geom gf = g;  // one frame's: its three channels' planes
   gf.nplanes = g.nplanes / nframes;
@@ -1431,10 +1493,16 @@ void launch_rgb_frames(hipStream_t s, const uint8_t* rgb, size_t pitch, uint64_t
   // every frame's rows 16-byte aligned, or the misaligned-load form (e.g. P6 files one after the other)
   const bool mis = pitch % 16 != 0 || reinterpret_cast<uintptr_t>(rgb) % 16 != 0 || (nframes > 1 && frame_stride % 16 != 0);
   const bool egs = out_e && predict && store_resid && gray_eg_supported(g);
-#define BIC_RFC(P, R, E, M, G, C)                                                                                    \
-  k_gray_strips_rgb_frames<P, R, E, M, G, C><<<grid, kBlock, 0, s>>>(rgb, pitch, frame_stride, nframes, gf, ns,      \
-                                                                     (uint32_t)plane0, planes, sones, krec, kpos,    \
-                                                                     zero, out_e, eg_stride)
+#define BIC_RFS(P, R, E, M, G, C, S)                                                                                 \
+  k_gray_strips_rgb_frames<P, R, E, M, G, C, S><<<grid, kBlock, 0, s>>>(rgb, pitch, frame_stride, nframes, gf, ns,   \
+                                                                        (uint32_t)plane0, planes, sones, krec, kpos, \
+                                                                        zero, out_e, eg_stride)
+#define BIC_RFC(P, R, E, M, G, C)                             \
+  do {                                                        \
+    if (rgb_predict == 1) BIC_RFS(P, R, E, M, G, C, 1);       \
+    else if (rgb_predict == 2) BIC_RFS(P, R, E, M, G, C, 2);  \
+    else BIC_RFS(P, R, E, M, G, C, 0);                        \
+  } while (0)
 #define BIC_RFG(P, R, E, M, G)                                  \
   do {                                                          \
     if (color_transform == 1) BIC_RFC(P, R, E, M, G, 1);        \
@@ -1454,6 +1522,7 @@ void launch_rgb_frames(hipStream_t s, const uint8_t* rgb, size_t pitch, uint64_t
 #undef BIC_RF
 #undef BIC_RFG
 #undef BIC_RFC
+#undef BIC_RFS
 }
 
 void launch_med_rows(hipStream_t s, const Geom& g, const uint64_t* planes, int predict, uint64_t* resid,

@@ -78,7 +78,8 @@ __global__ __launch_bounds__(256) void k_pbm_pack2(const uint64_t* __restrict__ 
 // CT (BIC_OPT_COLOR_TRANSFORM, BPP 3): channels 0 and 2 also pick the green bytes and go through ct_forward4
 // before G (1: subtract green, 2: folded; an instantiation each).
 // SP (BIC_OPT_SAMPLE_PREDICT, BPP 1): every sample minus the one on its left (2: folded) before G, as in
-// k_bitplanes_u8; the left of the word's first sample is one more byte load, 0 at column 0.
+// k_bitplanes_u8; the left of the word's first sample is one more byte load, 0 at column 0. With BPP 3
+// (BIC_OPT_RGB_PREDICT) the same on the wave's channel after CT: the left pixel lies three bytes back.
 template <int BPP, bool GC, int CT = 0, int SP = 0>
 __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict__ base, uint32_t off, uint32_t rows,
                                                        uint32_t cols, int plane0, int nplanes,
@@ -127,8 +128,18 @@ __global__ __launch_bounds__(256) void k_raster_planes(const uint8_t* __restrict
     }
   }
   if constexpr (SP != 0) {
-    static_assert(BPP == 1 || SP == 0, "sample prediction: one-byte gray samples only");
-    uint32_t prev = w ? (uint32_t)base[p0 - 1] << 24 : 0u;
+    static_assert(BPP == 1 || BPP == 3 || SP == 0, "sample prediction: one-byte samples only");
+    uint32_t prev = 0;
+    if constexpr (BPP == 3) {  // the pixel left of the word: the same channel of it, T_ct'ed with its own green
+      if (w) {
+        prev = (uint32_t)base[p0 - 3 + blockIdx.y];
+        if constexpr (CT != 0)
+          if (blockIdx.y != 1) prev = ct_forward4<CT>(prev, (uint32_t)base[p0 - 2]) & 0xffu;
+        prev <<= 24;
+      }
+    } else {
+      prev = w ? (uint32_t)base[p0 - 1] << 24 : 0u;
+    }
 #pragma unroll
     for (int g = 0; g < 8; ++g) {  // (samples past the row's end: `mask` below)
       const uint32_t lo = (uint32_t)lo8[g], hi = (uint32_t)(lo8[g] >> 32);
@@ -332,6 +343,22 @@ void launch_raster_planes(hipStream_t s, const uint8_t* raster, int bpp, uint32_
   const uint64_t waves = (uint64_t)rows * ((cols + 4095) / 4096);
   const uint32_t grid = (uint32_t)((waves + 3) / 4);
   if (!grid) return;
+  if (bpp == 3 && sample_predict) {  // BIC_OPT_RGB_PREDICT; grid.y: the channel
+#define BIC_RPP(G, C, S) \
+  k_raster_planes<3, G, C, S><<<dim3(grid, 3), 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, \
+                                                            wpr, pitch, 0, 0)
+#define BIC_RPP2(G, S)                               \
+  do {                                               \
+    if (color_transform == 1) BIC_RPP(G, 1, S);      \
+    else if (color_transform == 2) BIC_RPP(G, 2, S); \
+    else BIC_RPP(G, 0, S);                           \
+  } while (0)
+    if (sample_predict == 1) { if (gray_code) BIC_RPP2(true, 1); else BIC_RPP2(false, 1); }
+    else { if (gray_code) BIC_RPP2(true, 2); else BIC_RPP2(false, 2); }
+#undef BIC_RPP2
+#undef BIC_RPP
+    return;
+  }
   if (bpp == 3 && color_transform) {  // grid.y: the channel
 #define BIC_RPC(G, C) \
   k_raster_planes<3, G, C><<<dim3(grid, 3), 256, 0, s>>>(base, (uint32_t)(r & 7), rows, cols, plane0, nplanes, planes, wpr, \
@@ -428,6 +455,109 @@ void launch_sample_unpredict(hipStream_t s, int sample_predict, uint8_t* gray, u
   const dim3 grid((rows + 3) / 4, nframes);  // (nframes <= 65535)
   if (sample_predict == 1) k_sample_unpredict<1><<<grid, 256, 0, s>>>(gray, pitch, frame_stride, rows, cols);
   else k_sample_unpredict<2><<<grid, 256, 0, s>>>(gray, pitch, frame_stride, rows, cols);
+}
+
+// BIC_OPT_RGB_PREDICT on the way back, in place on the interleaved z bytes k_planes_gray<3> / k_col_apply_rgb have
+// just stored (both run as with CT 0 then: they store R' G' B' z bytes): per channel c'(j) = (c'(j - 1) + d(j)) & 0xff
+// along the row from c'(-1) = 0, d = z (SP 1) or its unfolding (SP 2), then the inverse colour transform CT on
+// (R', G', B'). k_sample_unpredict's shape: one wave per (frame, row), pieces of 1024 pixels, 16 pixels = 48 bytes
+// per lane -- three uint4 when they lie inside the row and the row is 16-byte aligned, bytes otherwise; nothing
+// past the row's first 3 * cols bytes is read or written. The 12 dwords are de-interleaved to four dwords per
+// channel (rgb_pick4), scanned (sp_scan4, the totals down the lane), the three channel totals packed into one dword
+// and scanned across the wave by the same DPP steps with sp_add4 in the place of + (no carry crosses a byte), the
+// exclusive form by a one-lane shift; a wave-uniform packed carry goes into the next piece.
+template <int SP, int CT>
+__global__ __launch_bounds__(256) void k_rgb_unpredict(uint8_t* __restrict__ rgb, uint64_t pitch, uint64_t frame_stride,
+                                                       uint32_t rows, uint32_t cols) {
+  const uint32_t row = blockIdx.x * 4 + wave_id();
+  if (row >= rows) return;  // whole wave
+  const uint32_t lane = lane_id();
+  uint8_t* p = rgb + (uint64_t)blockIdx.y * frame_stride + (uint64_t)row * pitch;
+  const bool al = reinterpret_cast<uintptr_t>(p) % 16 == 0;  // (wave-uniform)
+  const uint64_t nb = 3ull * cols;                             // the row's bytes
+  uint32_t carry = 0;  // the pixel left of the piece: R' | G' << 8 | B' << 16
+  for (uint32_t c0 = 0; c0 < cols; c0 += 1024) {
+    const uint32_t j = c0 + 16 * lane;
+    const uint64_t jb = 3ull * j;
+    const bool vec = al && j + 16 <= cols;
+    uint32_t x[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) x[q] = 0;
+    if (vec) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const uint4 t = reinterpret_cast<const uint4*>(p + jb)[q];
+        x[4 * q] = t.x, x[4 * q + 1] = t.y, x[4 * q + 2] = t.z, x[4 * q + 3] = t.w;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 48; ++i)
+        if (jb + i < nb) x[i >> 2] |= (uint32_t)p[jb + i] << (8 * (i & 3));
+    }
+    uint32_t ch[3][4], tot = 0;  // per channel: the 16 pixels' bytes; the lane's three totals, packed
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      uint32_t run = 0;  // the lane's bytes of the channel before the dword, summed
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const uint32_t z = rgb_pick4(x[3 * q], x[3 * q + 1], x[3 * q + 2], rgb_sel1(c), rgb_sel2(c));
+        ch[c][q] = sp_add4(sp_scan4<SP>(z), run * 0x01010101u);
+        run = ch[c][q] >> 24;
+      }
+      tot |= run << (8 * c);
+    }
+    // the lanes' packed totals, inclusive across the wave, byte-wise mod 256
+    uint32_t t = tot;
+    t = sp_add4(t, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x111, 0xf, 0xf, true));
+    t = sp_add4(t, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x112, 0xf, 0xf, true));
+    t = sp_add4(t, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x114, 0xf, 0xf, true));
+    t = sp_add4(t, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x118, 0xf, 0xf, true));
+    t = sp_add4(t, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x142, 0xa, 0xf, false));  // rows 1, 3 += row 0's, 2's
+    t = sp_add4(t, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x143, 0xc, 0xf, false));  // rows 2, 3 += rows 0-1's
+    // what lies left of the lane's pixels: lane - 1's inclusive totals (0 for lane 0) plus the carry
+    const uint32_t left = sp_add4((uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x138, 0xf, 0xf, true), carry);
+    carry = sp_add4((uint32_t)__builtin_amdgcn_readlane((int)t, 63), carry);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const uint32_t add = ((left >> (8 * c)) & 0xffu) * 0x01010101u;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ch[c][q] = sp_add4(ch[c][q], add);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if constexpr (CT != 0) {
+        ch[0][q] = ct_inverse4<CT>(ch[0][q], ch[1][q]);
+        ch[2][q] = ct_inverse4<CT>(ch[2][q], ch[1][q]);
+      }
+      rgb_interleave4(ch[0][q], ch[1][q], ch[2][q], x[3 * q], x[3 * q + 1], x[3 * q + 2]);
+    }
+    if (vec) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        reinterpret_cast<uint4*>(p + jb)[q] = make_uint4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 48; ++i)
+        if (jb + i < nb) p[jb + i] = (uint8_t)(x[i >> 2] >> (8 * (i & 3)));
+    }
+  }
+}
+
+void launch_rgb_unpredict(hipStream_t s, int rgb_predict, int color_transform, uint8_t* rgb, uint64_t pitch,
+                          uint64_t frame_stride, uint32_t nframes, uint32_t rows, uint32_t cols) {
+  if (!rgb_predict || !rows || !cols || !nframes) return;
+  const dim3 grid((rows + 3) / 4, nframes);  // (nframes <= 65535)
+#define BIC_RU(S, C) k_rgb_unpredict<S, C><<<grid, 256, 0, s>>>(rgb, pitch, frame_stride, rows, cols)
+#define BIC_RU2(S)                                \
+  do {                                            \
+    if (color_transform == 1) BIC_RU(S, 1);       \
+    else if (color_transform == 2) BIC_RU(S, 2);  \
+    else BIC_RU(S, 0);                            \
+  } while (0)
+  if (rgb_predict == 1) BIC_RU2(1);
+  else BIC_RU2(2);
+#undef BIC_RU2
+#undef BIC_RU
 }
 
 }  // namespace bic

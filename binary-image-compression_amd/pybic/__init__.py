@@ -35,7 +35,7 @@ EXPORTS = [
     "bic_encode_gray_frames", "bic_encode_gray_frames_packed", "bic_decode_gray_frames",
     "bic_encode_rgb", "bic_encode_rgb_packed", "bic_bitplanes_rgb", "bic_planes_to_rgb", "bic_decode_rgb",
     "bic_encode_rgb_frames", "bic_encode_rgb_frames_packed", "bic_decode_rgb_frames",
-    "bic_rgb_p00", "bic_gray_p00",
+    "bic_rgb_p00", "bic_gray_p00", "bic_rgb_p00_predict",
     "bic_bsvd_update_coefficients", "bic_bsvd_update_dictionary", "bic_bsvd_learn",
     "bic_dict_encode", "bic_set_dict_block",
     "bic_bsvd_update_dictionary_proximus", "bic_bsvd_learn_du", "bic_set_bsvd_rounds",
@@ -55,6 +55,8 @@ _CT_NAMES = {"none": CT_NONE, "subtract_green": CT_SUBTRACT_GREEN, "subtract_gre
 OPT_SAMPLE_PREDICT = 9
 SP_NONE, SP_LEFT, SP_LEFT_FOLDED = 0, 1, 2
 _SP_NAMES = {"none": SP_NONE, "left": SP_LEFT, "left_folded": SP_LEFT_FOLDED}
+# BIC_OPT_RGB_PREDICT (include/bic.h): the SP_* values on each channel of the RGB calls
+OPT_RGB_PREDICT = 10
 
 # bic_bsvd_learn_du rules (include/bic.h)
 BSVD_DU_STEEPEST, BSVD_DU_PROXIMUS = 0, 1
@@ -214,6 +216,7 @@ def load(path=LIB_PATH):
     sig("bic_decode_rgb", i32, [vp, i32, vp, sz, vp, vp, vp, i32, i32, sz, sz, i32, vp, vp, sz])
     sig("bic_rgb_p00", i32, [i32, i32, C.c_char_p, i32, i32, vp])
     sig("bic_gray_p00", i32, [i32, i32, C.c_uint8, i32, i32, vp])
+    sig("bic_rgb_p00_predict", i32, [i32, i32, i32, C.c_char_p, i32, i32, vp])
     sig("bic_bsvd_update_coefficients", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_update_dictionary", i32, [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp])
     sig("bic_bsvd_learn", i32, [vp, vp, sz, vp, sz, sz, sz, vp, sz, sz, vp, sz, sz, C.POINTER(sz)])
@@ -937,6 +940,17 @@ class Context:
             mode = _SP_NAMES[mode]
         self._chk(self.lib.bic_ctx_set_option(self.h, OPT_SAMPLE_PREDICT, int(mode)), "bic_ctx_set_option")
 
+    def set_rgb_predict(self, mode):
+        """left-neighbour prediction on each channel of the RGB calls, behind the colour transform and in front of
+        the Gray code, and its inverse on the way back (BIC_OPT_RGB_PREDICT, default 0): 0 / "none", 1 / "left",
+        2 / "left_folded" as in set_sample_predict. Any other value raises BicError and leaves the mode as it was.
+        The gray, 16-bit, PBM and planes-only calls ignore it; the RGB calls ignore set_sample_predict."""
+        if isinstance(mode, str):
+            if mode not in _SP_NAMES:
+                raise BicError(BIC_EINVAL, "bic_ctx_set_option")
+            mode = _SP_NAMES[mode]
+        self._chk(self.lib.bic_ctx_set_option(self.h, OPT_RGB_PREDICT, int(mode)), "bic_ctx_set_option")
+
     def set_multipass(self, on=True):
         self._chk(self.lib.bic_ctx_set_option(self.h, 1, int(on)), "bic_ctx_set_option")
 
@@ -1383,6 +1397,20 @@ def rgb_p00(color_transform, gray_code, pixel, plane0=0, nplanes=8):
     rc = load().bic_rgb_p00(int(color_transform), int(gray_code), px, int(plane0), int(nplanes), out.ctypes.data)
     if rc != BIC_OK:
         raise BicError(rc, "bic_rgb_p00")
+    return out
+
+
+def rgb_p00_predict(color_transform, rgb_predict, gray_code, pixel, plane0=0, nplanes=8):
+    """bic_rgb_p00_predict: rgb_p00 under BIC_OPT_RGB_PREDICT as well (the first pixel has no left neighbour: its
+    transformed bytes, folded in mode 2) -> uint8 numpy array [3 * nplanes] (host only)"""
+    px = bytes(bytearray(int(v) & 0xFF for v in pixel))
+    if len(px) != 3:
+        raise BicError(BIC_EINVAL, "bic_rgb_p00_predict")
+    out = np.zeros(3 * max(int(nplanes), 1), np.uint8)
+    rc = load().bic_rgb_p00_predict(int(color_transform), int(rgb_predict), int(gray_code), px, int(plane0),
+                                    int(nplanes), out.ctypes.data)
+    if rc != BIC_OK:
+        raise BicError(rc, "bic_rgb_p00_predict")
     return out
 
 

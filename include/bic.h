@@ -156,6 +156,27 @@ int bic_reserve(bic_ctx* ctx, int nplanes, size_t rows, size_t cols);
 #define BIC_SP_NONE 0
 #define BIC_SP_LEFT 1
 #define BIC_SP_LEFT_FOLDED 2
+/* BIC_OPT_RGB_PREDICT: the same left-neighbour prediction T_sp on each channel of the RGB calls, behind the colour
+ * transform T_ct of BIC_OPT_COLOR_TRANSFORM and in front of the Gray code. Values BIC_SP_NONE (0, default: every
+ * call as it was), BIC_SP_LEFT (1), BIC_SP_LEFT_FOLDED (2); any other value is BIC_EINVAL and leaves the setting as
+ * it was. An option of its own: the RGB calls go on ignoring BIC_OPT_SAMPLE_PREDICT, and a context that sets only
+ * that one produces the streams it always did.
+ *  - Samples to planes (bic_encode_rgb, bic_encode_rgb_packed, bic_bitplanes_rgb, bic_encode_rgb_frames,
+ *    bic_encode_rgb_frames_packed): per pixel T_ct, giving R', G', B'; then on each of the three channels
+ *    separately d_c(i,j) = (c'(i,j) - c'(i,j-1)) mod 256 with c'(i,-1) = 0 in every row of every frame (G is
+ *    differenced too), folded in mode 2 with z = ((d << 1) ^ (d >> 7)) & 0xFF; then the Gray code per channel if
+ *    BIC_OPT_GRAY_CODE is on, then the plane0 shift and the split. Planes, streams, bit counts, packed offsets and
+ *    the row index equal those of the same call with options 8 and 10 both off on the image U(img) = T_sp(T_ct(img)).
+ *  - Planes to samples (bic_planes_to_rgb, bic_decode_rgb, bic_decode_rgb_frames): each channel's z is assembled
+ *    from the given planes as with the option off (bits no plane covers count as 0, then the un-Gray step and its
+ *    mask), unfolded in mode 2 to d, then c'(j) = (c'(j-1) + d(j)) & 0xFF along the row from c'(-1) = 0 per channel,
+ *    then the inverse colour transform on (R', G', B'), and all eight bits of the result are written (a pass of its
+ *    own over the stored rows' first 3 * cols bytes; pitch padding and the gap between frames keep the caller's
+ *    bytes). The result is the image exactly when plane0 = 0 and nplanes = 8; for any other range it is this formula.
+ * Use mode 2 with BIC_CT_NONE or BIC_CT_SUBTRACT_GREEN. BIC_CT_SUBTRACT_GREEN_FOLDED folds before the difference:
+ * allowed and exact, and a poor choice. The decoder's first-pixel bytes are bic_rgb_p00_predict's.
+ * The gray, 16-bit, PBM and planes-only calls ignore option 10; the RGB calls ignore option 9. */
+#define BIC_OPT_RGB_PREDICT 10
 int bic_ctx_set_option(bic_ctx* ctx, int option, long value);
 
 /* ---- a2: bitplane extraction (bitplane_tool.cpp:24-30) -----------------------------------
@@ -306,6 +327,12 @@ int bic_rgb_p00(int color_transform, int gray_code, const uint8_t pixel[3], int 
  * sample in modes 0 and 1, after the Gray code. Host code, no context. p00: host, nplanes bytes. BIC_EINVAL: a
  * mode outside 0..2, gray_code outside 0..1, a NULL p00, plane0 < 0, nplanes < 1 or plane0 + nplanes > 8. */
 int bic_gray_p00(int sample_predict, int gray_code, uint8_t sample, int plane0, int nplanes, uint8_t* p00);
+/* bic_rgb_p00 under BIC_OPT_RGB_PREDICT as well: the first pixel has no left neighbour, so its bytes are
+ * T_ct(pixel), folded on all three channels in mode 2 and unchanged in modes 0 and 1; then the Gray code, then the
+ * bits plane0 + k. With rgb_predict = 0 the result is bic_rgb_p00's. Host code, no context. p00: host, 3 * nplanes
+ * bytes. BIC_EINVAL: as for bic_rgb_p00, or rgb_predict outside 0..2. */
+int bic_rgb_p00_predict(int color_transform, int rgb_predict, int gray_code, const uint8_t pixel[3], int plane0,
+                        int nplanes, uint8_t* p00);
 /* P4 rasters -> streams in one call: bic_pbm_unpack per frame followed by bic_encode_planes2 /
  * bic_encode_planes_packed, bit-identical streams, bit counts, offsets and row index. Frame f's raster
  * (pbm.cpp:29-77: rows x ceil(cols/8) bytes, MSB = leftmost pixel) lies at raster + f * frame_stride:
